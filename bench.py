@@ -14,6 +14,12 @@ splits ONE model's layers over the ranks by LPT on layer cost (strong scaling, c
 by the largest layer: the line reports the cap), no data-path collective, and the
 converged factors are gathered to rank 0 with one RCCL gather per step. `--shard
 replica` instead gives every rank its own weight set (seeds 1000+l+100r, weak scaling).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and
+prints the result line. `--full` adds everything else the benchmark reports: the live
+HIP-event kernel timing inside the timed steps with the per-kernel rooflines, the CPU
+baseline and the parity leg against the CPU oracle. `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -134,6 +140,43 @@ def run_step(work, max_iter_admm, num_attempts=200):
     runs = [LayerRun(s.name, W, R, [f.clone() for f in init]) for (s, W, R, init) in work]
     als_sweep(runs, max_iter_admm, 0.0, 4, MSE, num_attempts=num_attempts)
     return runs
+
+
+DUMP_BUDGET = 60 * 2 ** 20   # bytes of --dump-outputs, all files of all ranks together
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirpath, runs, rank=0, world=1, budget=DUMP_BUDGET):
+    """--dump-outputs: what the last timed step handed back, as float32 / float64 .npy files
+    (suffix _rank<r> when there are several ranks): `factors`, `quantized` and `duals` are
+    every layer's per-mode arrays of the LayerRun (run_step's return value) flattened and
+    concatenated in (layer, mode) order - the order gather_factors ships them in; `errors`
+    is the (layers, 2) float64 table of the sweep's two reconstruction errors (plain,
+    quantized). Arrays too large for the byte budget are written as a fixed sample: one
+    element from each of `cap` equal strata of the flat array, at an offset drawn from a
+    generator seeded with DUMP_SEED, so two builds dump the same positions. Returns
+    {file name: [elements written, elements of the whole array]}."""
+    os.makedirs(dirpath, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    flat = {"factors": [f for r in runs for f in r.factors],
+            "quantized": [q for r in runs for q in r.quantized],
+            "duals": [u for r in runs for u in r.duals]}
+    cap = max(int(budget // world // (4 * len(flat))), 1)
+    written = {}
+    for name, parts in flat.items():
+        v = torch.cat([t.reshape(-1) for t in parts]) if parts else torch.zeros(0)
+        n = v.numel()
+        if n > cap:
+            edges = (np.arange(cap + 1, dtype=np.int64) * n) // cap
+            off = np.random.default_rng(DUMP_SEED).integers(0, edges[1:] - edges[:-1])
+            v = v[torch.from_numpy(edges[:-1] + off).to(v.device)]
+        arr = v.detach().cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(dirpath, f"{name}{sfx}.npy"), arr)
+        written[f"{name}{sfx}.npy"] = [int(arr.size), int(n)]
+    err = np.array([[float(r.loss[-1]), float(r.lossq[-1])] for r in runs], dtype=np.float64).reshape(len(runs), 2)
+    np.save(os.path.join(dirpath, f"errors{sfx}.npy"), err)
+    written[f"errors{sfx}.npy"] = [int(err.size), int(err.size)]
+    return written
 
 
 USE_DIST = False   # torch.distributed (RCCL) on: world > 1, or --force-dist (exercises the collectives at N = 1)
@@ -513,10 +556,18 @@ def main():
     ap.add_argument("--max-iter-admm", type=int, default=1000)
     ap.add_argument("--shard", choices=["layers", "replica"], default="layers",
                     help="layers: LPT-shard one model's layers over the ranks (default); replica: every rank its own copy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the live HIP-event kernel timing inside the timed "
+                         "steps with the per-kernel rooflines, the CPU baseline and the parity leg against the CPU "
+                         "oracle (a plain run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (factors, quantized "
+                         "factors, duals, reconstruction errors) as DIR/<name>.npy; inputs are seeded, so two "
+                         "builds run with the same arguments can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity leg")
     ap.add_argument("--cpu-sample-iters", type=int, default=None,
                     help="inner iterations timed per (layer, mode) on the CPU (default 20; 1 for llama7b)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the live HIP-event kernel timing")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the live HIP-event kernel timing")
     ap.add_argument("--prof-every", type=int, default=16,
                     help="HIP-event timing of one ADMM iteration in N (GEMM and search: events recorded by the "
                          "dispatch itself, the kernel's own time; the other classes: an event pair per launch)")
@@ -560,6 +611,8 @@ def main():
                     help="tests only: no GPU, no kernels - the launcher, the shard plan and the factor gather over "
                          "gloo on CPU tensors (the factors are the init, unchanged)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.emulate_world > 0:
         return emulate_shards(a)
 
@@ -610,7 +663,7 @@ def main():
     torch.cuda.synchronize()
 
     _lib.fault_repairs(reset=True)   # fused-path faults repaired by a re-run inside the timed steps (expected 0)
-    prof = not a.no_profile
+    prof = a.full and not a.no_profile
     if prof:
         n_launch = a.steps * 3 * 6 * (a.max_iter_admm // a.prof_every + 1) + 64
         _lib.check(lib.admmq_profile_begin(n_launch, a.prof_every), "profile_begin")
@@ -634,6 +687,7 @@ def main():
         kern = {"ms": list(ms), "launches": list(cnt)}
 
     repairs = _lib.fault_repairs()
+    dumped = dump_outputs(a.dump_outputs, runs, rank, world) if a.dump_outputs else None
     elapsed_max, total_fi = reduce_over_ranks(elapsed, fi_per_step * a.steps, world, device)
 
     if rank == 0:
@@ -650,6 +704,8 @@ def main():
                           "solve": a.solve}}
         out["step_roofline"] = step_roofline(work, a.max_iter_admm, out["ms_per_step"])
         out["finalize_repairs"] = repairs   # rank 0's calls re-run after a fused-path internal fault
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "files": dumped}
         if shard_info:
             out["config"]["shard"] = shard_info
         if kern is not None:
@@ -679,7 +735,7 @@ def main():
             out["kernel_ms_per_step"] = per_step
             out["kernel_avg_us"] = avg_us
             out["prof_every"] = a.prof_every
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # cpu_baseline leg: the CPU reference port timed on host cores, and the
             # metric's "rel-Frob err vs CPU ref" (oracle comparison of one ADMM step)
             si = a.cpu_sample_iters if a.cpu_sample_iters is not None else (1 if a.model == "llama7b" else 20)

@@ -148,3 +148,38 @@ def test_bench_gpus_one_unchanged_and_mismatch_refused():
     assert line["n_gpus"] == 1 and line["rank_factors_match"] == [True]
     rc, line, err = _bench_cli("--gpus", "4", "--cpu-dry-run", env_extra={"WORLD_SIZE": "2"})
     assert rc == 2 and line is None and "refusing" in err
+
+
+def test_bench_dump_outputs_fixed_sample(tmp_path):
+    """bench.dump_outputs (--dump-outputs): the last step's factors, quantized factors and
+    duals flattened in (layer, mode) order as float32, the two reconstruction errors as a
+    (layers, 2) float64 table; over the byte budget, the same in-order sample of the flat
+    arrays on every call (one element per stratum)."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    runs = [types.SimpleNamespace(factors=[torch.randn(7, 5, generator=g), torch.randn(3, 5, generator=g)],
+                                  quantized=[torch.randn(7, 5, generator=g), torch.randn(3, 5, generator=g)],
+                                  duals=[torch.randn(7, 5, generator=g), torch.randn(3, 5, generator=g)],
+                                  loss=[0.9, 0.5 + k], lossq=[0.95, 0.6 + k]) for k in range(3)]
+    whole = bench.dump_outputs(str(tmp_path / "a"), runs)
+    assert whole == {"factors.npy": [150, 150], "quantized.npy": [150, 150], "duals.npy": [150, 150],
+                     "errors.npy": [6, 6]}
+    for name in ("factors", "quantized", "duals"):
+        arr = np.load(tmp_path / "a" / f"{name}.npy")
+        ref = torch.cat([t.reshape(-1) for r in runs for t in getattr(r, name)]).numpy()
+        assert arr.dtype == np.float32 and np.array_equal(arr, ref)
+    err = np.load(tmp_path / "a" / "errors.npy")
+    assert err.dtype == np.float64 and np.array_equal(err, [[0.5 + k, 0.6 + k] for k in range(3)])
+    # 40 of 150 elements per array: one per stratum, in order, the same on every call
+    part = bench.dump_outputs(str(tmp_path / "b"), runs, budget=3 * 4 * 40)
+    assert part["factors.npy"] == [40, 150]
+    bench.dump_outputs(str(tmp_path / "c"), runs, budget=3 * 4 * 40)
+    ref = torch.cat([t.reshape(-1) for r in runs for t in r.factors]).numpy()
+    b, c = np.load(tmp_path / "b" / "factors.npy"), np.load(tmp_path / "c" / "factors.npy")
+    assert np.array_equal(b, c) and b.shape == (40,)
+    edges = (np.arange(41) * 150) // 40
+    assert all(b[k] in ref[edges[k]:edges[k + 1]] for k in range(40))
+    assert sum(np.load(tmp_path / "b" / f).nbytes for f in part) <= 3 * 4 * 40 + err.nbytes

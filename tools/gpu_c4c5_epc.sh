@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 T=gpurun_out/${1:-c4c5_epc}
 export TMPDIR=/tmp
 for m in resnet50 llama7b; do
-  timeout -k 10 400 python -u bench.py --model $m --steps 3 --warmup 1 --no-cpu-baseline > ${T}_bench_$m.json 2> ${T}_bench_$m.err || { tail ${T}_bench_$m.err; exit 5; }
+  timeout -k 10 400 python -u bench.py --full --model $m --steps 3 --warmup 1 --no-cpu-baseline > ${T}_bench_$m.json 2> ${T}_bench_$m.err || { tail ${T}_bench_$m.err; exit 5; }
   python3 - ${T}_bench_$m.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
