@@ -134,6 +134,7 @@ def load() -> ctypes.CDLL:
         "admmq_get_solve_mode": (I32, []),
         "admmq_debug_set_legacy_stage1": (I32, [I32]),
         "admmq_debug_admm_plan_bytes": (S, [P, I32, I32, P]),
+        "admmq_debug_admm_plan_digest": (I32, [P, I32, I32, I32, P, P]),
         "admmq_debug_check_thresholds": (I32, [ctypes.c_uint32, I32]),
         "admmq_debug_set_fused_finalize": (I32, [I32]),
         "admmq_debug_set_search_units_per_block": (I32, [I32]),

@@ -108,11 +108,11 @@ struct QJob {
 
 // Work-unit tables (built on the host, uploaded once per call)
 // GEMM tile: rows tm, columns tn of problem prob, K-steps nk. The operands' addresses
-// and strides ride along (filled at upload), so a tile's first loads depend on the
+// and strides ride along (admm_plan.hip fill_tile_pointers), so a tile's first loads depend on the
 // tile entry only, not on a further descriptor read. Split form: P / M point at the
 // fp16 planes (row strides in floats are unchanged), eP / eM at the row exponents.
 // K-split pieces (fp32 64 x 64 tiles; the piece count np is fixed by the factor's shape:
-// api.hip ksplit_pieces): piece p covers K-steps [p nk / np, (p + 1) nk / np) of the tile
+// admm_plan.hip ksplit_pieces): piece p covers K-steps [p nk / np, (p + 1) nk / np) of the tile
 // in its own accumulator chain and the tile is ((p0 + p1) + p2) + ... Two execution forms
 // with the same bits: parallel (launches that leave CUs idle: np workgroups per tile, piece
 // pc of np runs K-steps [k0, k0 + nk), `part` holds the tile's np partial images, `ctr` its

@@ -7,14 +7,13 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <array>
-#include <map>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/admmq.h"
 #include "admmq_internal.h"
+#include "admm_plan.h"
 
 namespace admmq {
 
@@ -110,9 +109,6 @@ int upload_async(void* dst, const void* src, size_t n, hipStream_t s) {
 }
 static int h2d(void* dst, const void* src, size_t n, hipStream_t s) { return upload_async(dst, src, n, s); }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline int rup(int v, int a) { return (v + a - 1) / a * a; }
-
 // Optional per-launch HIP-event timing (bench.py measures the dominant kernel live on
 // the stream it runs on). Events are created in admmq_profile_begin, never in a launch path.
 struct Prof {
@@ -149,35 +145,14 @@ static std::atomic<int> g_fin_nv3{1};   // diagnostics: 0 = never three float4 g
 // workgroups wherever allowed (exercises that form on batches that fit without it)
 static std::atomic<int> g_thin_loop{1};
 
-// Tile rows of the persistent fp32 solve per problem (fixed by the problem's shape, never
-// by the batch, so every element's result is batch-independent): 0 = 64 x 64 tiles
-// (32-row factors: 32 x 64); 1 = 128 x 64 tiles for the factors with ld >= 1024 whose I
-// is a multiple of 128, 32 x 64 tiles for the others (finer filler tiles: the CU-level
-// LPT of a launch then balances to ~0.99 at C3 instead of 0.89, where the 36-K-step 64 x 64
-// tiles of the R = 1141 layers left gaps only coarse tiles could not fill); 2 = 64 x 64 for
-// ld >= 1024, 32 x 64 for the others; 3 = 128 x 64 for ld >= 1024, 64 x 64 for the others.
-static std::atomic<int> g_f32_rule{1};
 // fp32 solve kernel: 0 = k_gemm (64 x 64 tiles), 1 = persistent tile lists (k_gemm_f32p,
-// slower: DESIGN §7), 2 = one tile per workgroup with per-problem tile rows (k_gemm_f32t)
+// slower: DESIGN §7), 2 = one tile per workgroup with per-problem tile rows (k_gemm_f32t);
+// and the tile-row rule of kernels 1 / 2 (admm_plan.hip f32_tile_rows)
 static std::atomic<int> g_f32_kernel{0};
+static std::atomic<int> g_f32_rule{1};
 static std::atomic<int> g_even_units{1};   // big-job stage-1 units sized to fill the resident round evenly
-static int f32_tile_rows(int I, int ld) {
-  if (I <= 32) return 32;
-  const int rule = g_f32_rule.load();
-  const bool big = ld >= 1024;
-  switch (rule) {
-    case 0: return 64;
-    case 2: return big ? 64 : 32;
-    case 3: return (big && I % 128 == 0) ? 128 : 64;
-    default: return (big && I % 128 == 0) ? 128 : 32;
-  }
-}
-static constexpr int kF32Slots = 2;   // k_gemm_f32p workgroups per CU (72 KB of LDS each)
-
-// K-split of the fp32 64 x 64 solve tiles (gemm_kernels.hip ksplit_combine): 1 = by
-// ksplit_pieces, 0 = never (A/B). A factor whose tiles alone leave most of the chip idle
-// (a lone layer4 conv: 144 tiles of 36 K-steps on 256 CUs, the busiest shard of a
-// multi-GPU run) splits every tile's K range into np pieces summed in piece order.
+// K-split of the fp32 64 x 64 solve tiles (admm_plan.hip ksplit_pieces): 1 = by the factor's
+// shape, 0 = never (A/B)
 static std::atomic<int> g_ksplit{1};
 // 64x64 tiles of a launch from which its I > 64 factors without a K-split take the 256x128
 // tiles (default kWideMinTiles; diagnostics: admmq_debug_set_wide_min_tiles; same bits)
@@ -185,85 +160,27 @@ static std::atomic<long long> g_wide_min_tiles{kWideMinTiles};
 // execution form of the pieces (same bits either way): 1 = parallel only where the 64 x 64
 // launch's whole tiles leave CUs idle, else serial (default); 0 = always serial; 2 = always parallel
 static std::atomic<int> g_ksplit_par{1};
-// Pieces per tile, a function of (I, R) ONLY (never of the batch, the device or the
-// launch), so a factor's bits are the same in every batch: the np in 1..kKsplitMax with
-// pieces of >= kKsplitMinSteps K-steps that minimises the factor's own launch length on
-// a 256-CU chip, ceil(tiles np / 256) ceil(nk / np) K-steps plus kKsplitCost for the
-// partial hand-off, ties to the smaller np. Only factors with fewer tiles than CUs split.
-static constexpr int kKsplitChipCUs = 256;
-static constexpr int kKsplitCost = 4;   // K-steps (~2.5 us): partial stores, arrival, sc1 reads
-// Balance (launches that fill the chip): 1 = run the pieces of the longest split tiles in
-// parallel where that lowers the launch's CU-level LPT makespan (same bits), 0 = never;
-// a parallel piece is priced kKsplitCost... g_ksplit_cost K-steps above its own.
+// Balance (admm_plan.hip ksplit_balance): on / off, and the price of a parallel piece in K-steps
 static std::atomic<int> g_ksplit_bal{1};
 static std::atomic<int> g_ksplit_cost{1};
-// Resident 64 x 64 fp32 solve workgroups per CU (the LPT's slots): 3 for the default 3-deep
-// staging ring (48 KB of LDS), 4 for the 2-deep ring (k_gemm_f32b<2>, 32 KB, 4 waves per SIMD)
-static int f32_slots() { return g_gemm_f32_stage == 2 ? 4 : 3; }
-// Makespan (K-steps of the busiest CU) of an LPT placement of `costs` over ncu CUs with at
-// most `slots` items each (order_tiles_for_cus' rule without its XCD tie-break); -1 when
-// the items do not fit one resident round.
-static long long lpt_makespan(std::vector<long long> costs, int ncu, int slots) {
-  if ((long long)costs.size() > (long long)ncu * slots) return -1;
-  std::sort(costs.begin(), costs.end(), std::greater<long long>());
-  // min-heap of (load, cu) over the CUs with a free slot
-  std::vector<std::pair<long long, int>> heap;
-  std::vector<int> used(ncu, 0);
-  for (int b = 0; b < ncu; ++b) heap.push_back({0, b});
-  auto cmp = [](const std::pair<long long, int>& a, const std::pair<long long, int>& b) { return a > b; };
-  std::make_heap(heap.begin(), heap.end(), cmp);
-  long long mx = 0;
-  for (long long c : costs) {
-    std::pop_heap(heap.begin(), heap.end(), cmp);
-    auto [ld, b] = heap.back();
-    heap.pop_back();
-    ld += c;
-    mx = std::max(mx, ld);
-    if (++used[b] < slots) {
-      heap.push_back({ld, b});
-      std::push_heap(heap.begin(), heap.end(), cmp);
-    }
-  }
-  return mx;
-}
-// How many of the split tiles `cand` (longest first; (nk, np)) to run as parallel pieces so
-// that the launch's LPT makespan is smallest (ties: fewer), `whole` = every tile's K-steps.
-static long long ksplit_balance(const std::vector<long long>& whole, std::vector<std::pair<int, int>> cand, int ncu,
-                                int slots, int cost) {
-  if (cand.empty() || (long long)whole.size() <= ncu) return 0;
-  std::stable_sort(cand.begin(), cand.end(), [](auto& a, auto& b) { return a.first > b.first; });
-  long long best_m = lpt_makespan(whole, ncu, slots);
-  if (best_m < 0) return 0;
-  long long best_k = 0;
-  std::vector<long long> costs = whole;
-  // remove one whole tile of each split candidate as it is split: keep a multiset by value
-  for (long long k = 1; k <= (long long)cand.size(); ++k) {
-    const int nk = cand[k - 1].first, np = cand[k - 1].second;
-    auto it = std::find(costs.begin(), costs.end(), (long long)nk);
-    if (it == costs.end()) break;
-    costs.erase(it);
-    for (int pc = 0; pc < np; ++pc) costs.push_back((pc + 1) * nk / np - pc * nk / np + cost);
-    const long long m = lpt_makespan(costs, ncu, slots);
-    if (m < 0) break;
-    if (m < best_m) { best_m = m; best_k = k; }
-  }
-  return best_k;
-}
 
-static int ksplit_pieces(int I, int R) {
-  if (I <= 32) return 1;   // 32 x 64 tiles
-  const int nk = rup(R, 32) / 32;
-  const long long tiles = (long long)((I + 63) / 64) * ((rup(R, 32) + 63) / 64);
-  if (tiles >= kKsplitChipCUs) return 1;
-  int best = 1;
-  long long best_cost = nk;
-  for (int np = 2; np <= kKsplitMax; ++np) {
-    const int len = (nk + np - 1) / np;
-    if (len < kKsplitMinSteps) break;
-    const long long cost = (tiles * np + kKsplitChipCUs - 1) / kKsplitChipCUs * len + kKsplitCost;
-    if (cost < best_cost) { best = np; best_cost = cost; }
-  }
-  return best;
+// The planner's inputs among the switches, read once per entry-point call
+static PlanSwitches plan_switches() {
+  PlanSwitches sw;
+  sw.ksplit = g_ksplit.load();
+  sw.ksplit_form = g_ksplit_par.load();
+  sw.ksplit_bal = g_ksplit_bal.load();
+  sw.ksplit_cost = g_ksplit_cost.load();
+  sw.f32_kernel = g_f32_kernel.load();
+  sw.f32_rule = g_f32_rule.load();
+  sw.gemm_stage = g_gemm_f32_stage;
+  sw.gemm_ks = g_gemm_ks_f32;
+  sw.wide_min_tiles = g_wide_min_tiles.load();
+  sw.even_units = g_even_units.load();
+  sw.fin_nv3 = g_fin_nv3.load();
+  sw.thin_loop = g_thin_loop.load();
+  sw.hist_reps = g_hist_reps.load();
+  return sw;
 }
 
 // CUs of the current device (looked up once per device)
@@ -278,54 +195,6 @@ static int device_cus() {
     cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
   });
   return cus[dev];
-}
-
-// Persistent fp32 solve lists: every tile goes, largest MFMA work first, to the CU with the
-// least work so far (ties: the CU whose XCD already holds tiles of the same M column / P row
-// panel, which then come from that XCD's L2), then each CU's tiles are split over its
-// kF32Slots workgroups (LPT again). Workgroup b runs on CU b mod ncu (round-robin dispatch;
-// a different placement only costs speed). Fills `tiles` in list order and `off`.
-static void plan_f32_lists(std::vector<GemmTile>& tiles, std::vector<int>& off, int ncu) {
-  std::vector<GemmTile> sorted = tiles;
-  auto work = [](const GemmTile& t) { return (long long)t.bm * t.nk; };
-  std::stable_sort(sorted.begin(), sorted.end(), [&](const GemmTile& a, const GemmTile& b) { return work(a) > work(b); });
-  constexpr int kXcd = 8;
-  std::vector<std::vector<GemmTile>> bins(ncu);
-  std::vector<long long> load(ncu, 0);
-  std::map<std::pair<int, int>, std::array<int, kXcd>> col_on, row_on;
-  for (const GemmTile& t : sorted) {
-    auto& cx = col_on[{t.prob, t.tn}];
-    auto& rx = row_on[{t.prob, t.tm * t.bm}];
-    int best = 0;
-    long long best_key = 0;
-    for (int b = 0; b < ncu; ++b) {
-      const long long key = load[b] * 1000000LL - cx[b % kXcd] * 1000LL - rx[b % kXcd];
-      if (b == 0 || key < best_key) { best = b; best_key = key; }
-    }
-    bins[best].push_back(t);
-    load[best] += work(t);
-    cx[best % kXcd] += 1;
-    rx[best % kXcd] += 1;
-  }
-  const int nslots = ncu * kF32Slots;
-  std::vector<std::vector<GemmTile>> lists(nslots);
-  for (int c = 0; c < ncu; ++c) {
-    long long sl[kF32Slots] = {};
-    for (const GemmTile& t : bins[c]) {   // already largest first
-      int k = 0;
-      for (int j = 1; j < kF32Slots; ++j)
-        if (sl[j] < sl[k]) k = j;
-      lists[c + (size_t)k * ncu].push_back(t);
-      sl[k] += work(t);
-    }
-  }
-  tiles.clear();
-  off.assign(nslots + 1, 0);
-  for (int b = 0; b < nslots; ++b) {
-    off[b] = (int)tiles.size();
-    tiles.insert(tiles.end(), lists[b].begin(), lists[b].end());
-  }
-  off[nslots] = (int)tiles.size();
 }
 
 // What each prepare recorded for its workspace: the solve mode (the run must use the operand
@@ -417,665 +286,9 @@ static inline void prof_pair(int c, hipEvent_t* e0, hipEvent_t* e1) {
   *e1 = g_prof.ev[g_prof.next++];
 }
 
-// Carves the workspace in a fixed order so that size and run agree exactly.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  template <class T>
-  T* take(size_t n) {
-    off = align_up(off, 256);
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
-// Per-slot quantizer search state of one job.
-static void carve_view(Carver& cv, MseView& v, int nslot, int ncand) {
-  v.stat = cv.take<unsigned>(4 * (size_t)nslot);
-  v.sse = cv.take<unsigned long long>((size_t)nslot * ncand);
-  v.h1 = cv.take<unsigned long long>((size_t)nslot * kHistRep * (ncand + 1));
-  v.h2 = cv.take<unsigned long long>((size_t)nslot * kHistRep * (ncand + 1));
-  v.s2 = cv.take<double>((size_t)nslot);
-  v.sel = cv.take<int>((size_t)nslot * (2 + kMaxSel));
-  v.ticket = cv.take<unsigned>((size_t)nslot);
-  v.ready = cv.take<unsigned long long>((size_t)nslot);
-
-}
-
-struct AdmmPlan {
-  std::vector<ProbDesc> desc;
-  std::vector<GemmTile> tiles;
-  std::vector<Chunk> sse_chunks, fin_chunks, hist_chunks;
-  std::vector<Chunk> hist_multi;   // the same units, several per block (launches without the fused finalize)
-  Chunk* d_hist_multi = nullptr;
-  int nhm_big = 0;                 // hist_multi blocks of the big jobs (listed first)
-  ProbDesc* d_desc = nullptr;
-  GemmTile* d_tiles = nullptr;
-  Chunk* d_sse = nullptr;
-  Chunk* d_fin = nullptr;
-  Chunk* d_hist = nullptr;
-  bool split = false;            // per-iteration solve on the split fp16 planes (kSolveSplit)
-  std::vector<ThinLoopUnit> thin;   // solve workgroups (32 columns each) of the thin (I <= kThinRows) factors
-  ThinLoopUnit* d_thin = nullptr;
-  int thin_nr = 0, thin_maxld = 0;
-  unsigned short* d_rank0 = nullptr;    // merged stage-1 order (kMaxMerged), then the cell index (kCells + 2)
-  unsigned short* d_groups = nullptr;   // merged stage-1 tie groups (3 kMaxMerged)
-  size_t bytes = 0;
-  int maxIp = 0, maxld = 0, maxldm = 0, maxnbk = 0, maxI = 0, maxR = 0;
-  int ntiles_wide = 0, ntiles_big = 0, ntiles_small = 0;   // 256x128, 64x64, 32x64 tiles (in that order)
-  // persistent fp32 solve (k_gemm_f32p): tiles in list order, workgroup b's list [off[b], off[b+1])
-  bool f32p = false;
-  bool f32t = false;   // one tile per workgroup, tile rows per problem (k_gemm_f32t)
-  std::vector<int> list_off;
-  int* d_list_off = nullptr;
-  int nslots = 0;
-  int ntiles_f32t = 0;
-  bool wide = false;                                       // I > 64 factors take 256x128 tiles (k_gemm<8, 1, 3, *, 2>)
-  int fin_groups = 1;             // float4 groups per thread of the finalize units
-  int hist_nv = 1;
-  std::vector<int> small;         // jobs with I <= kThinRows (one-block fused search + finalize)
-  int* d_small = nullptr;
-  int nfin_big = 0, nhist_big = 0;   // finalize / stage-1 units of the other jobs (listed first)
-  bool rows_aligned = true;          // every big job's stage-1 units are whole rows (fused finalize possible)
-  unsigned long long* d_ready = nullptr;   // [nprob][2] fused-finalize ready words (zeroed per run)
-  unsigned* d_kctr = nullptr;        // K-split arrival counters (zeroed per run)
-  size_t nkctr = 0;
-  bool ksplit_par = false;           // this launch runs the K-split pieces in parallel (else serially)
-  int small_groups = 0;              // float4 groups per thread of the fused kernel (0: too large)
-  // persistent thin-factor loop (k_thin_loop, one team of workgroups per problem): possible
-  // when every problem is thin, ld <= 1152 and the workgroups fit the CUs (64-column
-  // workgroups for some ld <= 512 problems where 32-column ones would not)
-  std::vector<ThinLoopUnit> tl_units;
-  ThinLoopUnit* d_tl_units = nullptr;
-  ThinSync* d_tl_sync = nullptr;
-  bool tl_ok = false;
-};
-
-static GemmTile mk_tile(int prob, int tm, int tn, int first, int nk) {
-  GemmTile t;
-  std::memset(&t, 0, sizeof(t));
-  t.prob = prob; t.tm = tm; t.tn = tn; t.first = first; t.nk = nk; t.bm = 0;
-  t.k0 = 0; t.np = 1; t.pc = 0; t.ser = 1;
-  t.P = nullptr; t.M = nullptr; t.U = nullptr; t.eP = nullptr; t.eM = nullptr; t.ld = 0; t.ldm = 0;   // set at upload
-  return t;
-}
-
-// CU-balanced order of the big GEMM tiles. When every tile of a launch is resident at
-// once (at most `slots` workgroups per CU), workgroup b lands on CU b mod ncu (round
-// robin over the XCDs, then over each XCD's CUs; tools/gemm_timeline.py checks it), so
-// the tiles at positions b, b + ncu, b + 2 ncu share one CU's MFMA pipes. Longest-first
-// order alone gives some CUs three long tiles and others two; instead every tile, longest
-// first, goes to the CU with the fewest K-steps that still has a free slot.
-// The grid is padded with empty tiles (nk = 0: the workgroup returns at once) to a whole
-// number of rounds, so every CU may take up to `slots` tiles, not only the CUs whose
-// positions exist in a partial last round (C3 mode 1: 645 tiles, max CU load 90 -> 84).
-static void order_tiles_for_cus(std::vector<GemmTile>& tiles, int ncu, int slots) {
-  const int n = (int)tiles.size();
-  if (n <= ncu || n > ncu * slots) return;
-  std::vector<GemmTile> sorted = tiles;
-  auto cost = [](const GemmTile& t) { return (long long)t.nk * ((t.bm > 0 ? t.bm : 64) / 32); };   // 32-row K-steps
-  std::stable_sort(sorted.begin(), sorted.end(), [&](const GemmTile& a, const GemmTile& b) { return cost(a) > cost(b); });
-  std::vector<std::vector<GemmTile>> bins(ncu);
-  std::vector<long long> load(ncu, 0);
-  // Among the least-loaded CUs, prefer the XCD (CU b mod 8) that already holds tiles of
-  // the same column tile of M (they share its B panel through that XCD's L2), then of
-  // the same row tile of P.
-  constexpr int kXcd = 8;
-  std::map<std::pair<int, int>, std::array<int, kXcd>> col_on, row_on;
-  for (const GemmTile& t : sorted) {
-    auto& cx = col_on[{t.prob, t.tn}];
-    auto& rx = row_on[{t.prob, t.tm}];
-    int best = -1;
-    long long best_key = 0;
-    for (int b = 0; b < ncu; ++b) {
-      if ((int)bins[b].size() >= slots) continue;
-      // smaller is better: load first, then affinity (column, row)
-      const long long key = load[b] * 1000000LL - cx[b % kXcd] * 1000LL - rx[b % kXcd];
-      if (best < 0 || key < best_key) { best = b; best_key = key; }
-    }
-    bins[best].push_back(t);
-    load[best] += cost(t);
-    cx[best % kXcd] += 1;
-    rx[best % kXcd] += 1;
-  }
-  size_t rounds = 0;
-  for (int b = 0; b < ncu; ++b) rounds = std::max(rounds, bins[b].size());
-  GemmTile empty = mk_tile(0, 0, 0, 0, 0);
-  tiles.assign(rounds * ncu, empty);
-  for (int b = 0; b < ncu; ++b)
-    for (int r = 0; r < (int)bins[b].size(); ++r) tiles[b + (size_t)r * ncu] = bins[b][r];
-}
-
-// Finalize units hold whole rows (the split solve needs each row's exponent in one pass):
-// at most 1024 G elements, G in {1, 2, 4, 8}. Returns G.
-static int fin_groups_for(const std::vector<ProbDesc>& desc, const std::vector<int>& jobs) {
-  long long units4k = 0;
-  int maxld = 0;
-  for (int i : jobs) {
-    units4k += ((long long)desc[i].I * desc[i].ld + kFinElems - 1) / kFinElems;
-    maxld = std::max(maxld, desc[i].ld);
-  }
-  int g = units4k >= kFinMinUnits ? 4 : 1;   // small problem sets keep their parallelism
-  while (g < 8 && 1024 * g < maxld) g *= 2;
-  return g;
-}
-
-// Teams of the persistent thin-factor loop: 32-column workgroups, and while they would
-// not all fit on the CUs at once, the shortest problems with ld <= 512 take 64-column ones
-// (two k classes per thread, the same chains and sums: thin_loop.hip), whose per-iteration
-// work (64 ld) stays below the largest team's (32 x 1152).
-static bool plan_thin_teams(AdmmPlan& pl, int ncu) {
-  pl.tl_units.clear();
-  const int nprob = (int)pl.desc.size();
-  if ((int)pl.small.size() != nprob || nprob == 0 || pl.thin_maxld > 1152) return false;
-  std::vector<int> cw(nprob, 32);
-  auto nwg = [&](int i) { const int ld = pl.desc[i].ld; return cw[i] == 64 ? ld / 64 + (ld % 64 ? 1 : 0) : ld / 32; };
-  long long total = 0;
-  for (int i = 0; i < nprob; ++i) total += nwg(i);
-  const bool wide_all = g_thin_loop.load() == 2;
-  while (total > ncu || wide_all) {
-    int best = -1;
-    for (int i = 0; i < nprob; ++i)
-      if (cw[i] == 32 && pl.desc[i].ld <= 512 && pl.desc[i].ld >= 64 && (best < 0 || pl.desc[i].ld < pl.desc[best].ld))
-        best = i;
-    if (best < 0) {
-      if (total > ncu) return false;
-      break;
-    }
-    total -= nwg(best);
-    cw[best] = 64;
-    total += nwg(best);
-  }
-  for (const ThinLoopUnit& u0 : pl.thin) {   // the problems in the planner's order
-    if (u0.col0 != 0) continue;
-    const int i = u0.job, ld = pl.desc[i].ld;
-    const int n = nwg(i);
-    for (int c = 0, r = 0; c < ld; ++r) {
-      const int w = std::min(cw[i], ld - c);
-      ThinLoopUnit u;
-      std::memset(&u, 0, sizeof(u));
-      u.job = i; u.col0 = c; u.cw = w; u.rank = r; u.nteam = n;
-      pl.tl_units.push_back(u);
-      c += w;
-    }
-  }
-  return true;
-}
-
-// The fp32 64 x 64 tile list of a plan (pl.desc, pl.split set; not f32p / f32t): whole
-// tiles in problem order (XCD-aware within each problem), K-split pieces in parallel or
-// folded serially, then the CU-level LPT order. part / ctr are left for the caller.
-template <class WideFn>
-static void build_big_tiles(AdmmPlan& pl, const std::vector<int>& order, WideFn wide_prob) {
-  pl.tiles.clear();
-  // The K-split pieces of a factor (fixed by its shape) run in parallel, np workgroups per
-  // tile, only in a launch whose whole tiles leave CUs idle (a lone large factor, as in a
-  // multi-GPU shard); otherwise one workgroup folds them serially (same bits, no hand-off).
-  long long whole64 = 0;
-  for (int i : order) {
-    const ProbDesc& d = pl.desc[i];
-    if (d.I <= kThinRows || d.Ip == 32 || wide_prob(d)) continue;
-    whole64 += (long long)(d.Ip / 64) * ((d.ld + 63) / 64);
-  }
-  pl.ksplit_par = g_ksplit_par.load() == 2 || (g_ksplit_par.load() == 1 && whole64 <= kKsplitChipCUs);
-  // A launch that fills the chip runs the pieces serially, except the `npar` longest split
-  // tiles (balance): their pieces in parallel fill the gaps a CU-level LPT of whole tiles
-  // leaves (C3 mode 0: 36-K-step tiles, max CU load 90 against a mean of 80).
-  long long npar = pl.ksplit_par ? (1LL << 40) : 0;
-  if (!pl.ksplit_par && g_ksplit_par.load() == 1 && g_ksplit_bal.load()) {
-    std::vector<long long> whole;   // K-steps of every 64 x 64 tile of the launch
-    std::vector<std::pair<int, int>> cand;   // (nk, np) of the split tiles, longest first
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      if (d.I <= kThinRows || d.Ip == 32 || wide_prob(d)) continue;
-      const long long nt = (long long)(d.Ip / 64) * ((d.ld + 63) / 64);
-      for (long long t = 0; t < nt; ++t) whole.push_back(d.ld / 32);
-      if (d.ksplit > 1)
-        for (long long t = 0; t < nt; ++t) cand.push_back({d.ld / 32, d.ksplit});
-    }
-    npar = ksplit_balance(whole, cand, 256, f32_slots(), g_ksplit_cost.load());
-  }
-  long long nsplit = 0;   // split tiles emitted so far (the first npar of them run in parallel)
-  for (int i : order) {
-    const ProbDesc& d = pl.desc[i];
-    if (d.I <= kThinRows || d.Ip == 32 || wide_prob(d)) continue;   // thin / 32-row / wide: elsewhere
-    const int TM = d.Ip / 64, TN = (d.ld + 63) / 64;
-    const int nk = d.ld / 32;
-    for (int g0 = 0; g0 < TN; g0 += 8)
-      for (int tm = 0; tm < TM; ++tm)
-        for (int tn = g0; tn < std::min(TN, g0 + 8); ++tn) {
-          const int np = (d.ksplit > 1 && nsplit++ < npar) ? d.ksplit : 1;
-          for (int pc = 0; pc < np; ++pc) {   // parallel K-split pieces: [pc nk / np, (pc + 1) nk / np)
-            const int k0 = pc * nk / np, k1 = (pc + 1) * nk / np;
-            GemmTile t = mk_tile(i, tm, tn, (tm == 0 && tn == 0 && pc == 0) ? 1 : 0, k1 - k0);
-            if (np > 1) {
-              t.k0 = k0; t.np = np; t.pc = pc;   // (part / ctr: filled per call)
-            } else {
-              t.ser = d.ksplit;   // serial form (1: no K-split)
-            }
-            pl.tiles.push_back(t);
-          }
-        }
-  }
-  {
-    // a launch of more tiles than resident slots (K-split pieces, C4) is dispatched in
-    // order as slots free up: longest first (a no-op without pieces: problems are in ld order)
-    if (pl.tiles.size() > 256 * 3)
-      std::stable_sort(pl.tiles.begin(), pl.tiles.end(), [](const GemmTile& a, const GemmTile& b) { return a.nk > b.nk; });
-    order_tiles_for_cus(pl.tiles, 256, f32_slots());
-  }
-}
-
-// Memo of build_big_tiles by a hash of its inputs (bounded; cleared when full)
-static std::mutex g_tile_mu;
-static std::unordered_map<unsigned long long, std::pair<std::vector<GemmTile>, bool>> g_tile_cache;
-static bool tile_cache_get(unsigned long long key, std::vector<GemmTile>& tiles, bool& par) {
-  std::lock_guard<std::mutex> g(g_tile_mu);
-  auto it = g_tile_cache.find(key);
-  if (it == g_tile_cache.end()) return false;
-  tiles.insert(tiles.end(), it->second.first.begin(), it->second.first.end());
-  par = it->second.second;
-  return true;
-}
-static void tile_cache_put(unsigned long long key, const std::vector<GemmTile>& tiles, bool par) {
-  std::lock_guard<std::mutex> g(g_tile_mu);
-  if (g_tile_cache.size() >= 64) g_tile_cache.clear();
-  g_tile_cache[key] = {tiles, par};
-}
-
-static int plan_admm(const admmq_problem* probs, int nprob, int ncand, void* ws, AdmmPlan& pl, int solve_mode) {
-  if (nprob <= 0 || !probs) return fail(ADMMQ_ERR_ARG, "no problems");
-  if (ncand < 1) return fail(ADMMQ_ERR_ARG, "num_attempts must be >= 1");
-  Carver cv(ws);
-  pl.desc.resize(nprob);
-  pl.thin_nr = 0;
-  for (int i = 0; i < nprob; ++i)
-    if (probs[i].I > 0 && probs[i].I <= kThinRows) pl.thin_nr = std::max(pl.thin_nr, probs[i].I);
-  pl.split = solve_mode == kSolveSplit;
-  // Wide tiles when the 64x64 tiles would take many rounds of the resident slots
-  // (256 CUs x 3): then a CU's bytes per MAC matter more than the number of tiles, and
-  // 256x128 tiles read 3/8 of the operand bytes per MAC (the Llama shapes of C5). The
-  // element results do not depend on the tile shape (same K order per element).
-  {
-    long long t64 = 0;
-    for (int i = 0; i < nprob; ++i)
-      if (probs[i].I > 32) t64 += (long long)((probs[i].I + 63) / 64) * ((rup(std::max(probs[i].R, 1), 32) + 63) / 64);
-    pl.wide = t64 >= g_wide_min_tiles.load();
-  }
-  auto wide_prob = [&](const ProbDesc& d) { return pl.wide && d.I > 64 && d.ksplit == 1; };
-  for (int i = 0; i < nprob; ++i)   // the split finalize needs whole rows in one unit
-    if (probs[i].I > kThinRows && rup(std::max(probs[i].R, 1), 32) > 8192) pl.split = false;
-  for (int i = 0; i < nprob; ++i) {
-    const admmq_problem& a = probs[i];
-    if (a.I <= 0 || a.R <= 0) return fail(ADMMQ_ERR_ARG, "I and R must be positive");
-    if ((long long)a.I * a.R > (1LL << 30)) return fail(ADMMQ_ERR_ARG, "factor too large");
-    ProbDesc& d = pl.desc[i];
-    std::memset(&d, 0, sizeof(d));
-    d.F_user = a.F; d.G_user = a.G; d.H0_user = a.H0; d.H_out = a.H_out; d.U_user = a.U;
-    d.HT_dbg = a.HT_out; d.X_dbg = a.X_out;
-    d.I = a.I; d.R = a.R;
-    d.ld = rup(a.R, 32);
-    // K-split pieces (fp32 64 x 64 tiles only; by shape alone): such a factor never takes
-    // the wide tiles, whatever its launch, so its bits stay those of its own shape
-    d.ksplit = (!pl.split && g_ksplit.load() != 0 && g_f32_kernel.load() == 0 && g_gemm_ks_f32 == 1 &&
-                a.I > kThinRows) ? ksplit_pieces(a.I, a.R) : 1;
-    const bool f32p_prob = !pl.split && g_f32_kernel.load() != 0 && !wide_prob(d) && a.I > kThinRows;
-    d.Ip = a.I <= 32 ? 32 : rup(a.I, wide_prob(d) ? kWideRows : (f32p_prob ? std::max(64, f32_tile_rows(a.I, rup(a.R, 32))) : 64));
-    d.ldm = rup(a.R, 64);
-    d.nbk = d.ldm / 32;
-    d.nq = a.I * ((a.R + 3) / 4);
-    // 32-bit element offsets inside a problem's padded buffers (admm_finalize_block)
-    if ((long long)d.Ip * d.ld >= (1LL << 31)) return fail(ADMMQ_ERR_ARG, "factor too large");
-    const bool thin = a.I <= kThinRows;
-    d.split = (pl.split && !thin) ? 1 : 0;
-    const size_t fe = (size_t)d.Ip * d.ld;
-    d.Fp = cv.take<float>(fe); d.H = cv.take<float>(fe); d.U = cv.take<float>(fe);
-    d.P = cv.take<float>(fe); d.X = cv.take<float>(fe); d.HT = cv.take<float>(fe);
-    d.M = cv.take<float>((size_t)d.ldm * d.ldm);
-    d.A64 = cv.take<double>((size_t)d.ldm * d.ldm);
-    d.L64 = cv.take<double>((size_t)d.ldm * d.ldm);
-    d.D64 = cv.take<double>((size_t)d.ldm * 32);
-    if (d.split) {
-      d.P2 = cv.take<_Float16>(2 * fe);
-      d.eP = cv.take<int>(d.Ip);
-      d.M2 = cv.take<_Float16>(2 * (size_t)d.ldm * d.ldm);
-      d.eM = cv.take<int>(d.ldm);
-    }
-    if (d.ksplit > 1) {   // the partial images of every 64 x 64 tile (the counters are carved below)
-      const long long nt = (long long)(d.Ip / 64) * ((d.ld + 63) / 64);
-      d.kpart = cv.take<float>((size_t)nt * d.ksplit * 4096);
-    }
-    d.res = cv.take<double>(2 * kResRep * 4);
-    d.flags = cv.take<int>(4);
-    d.rho = cv.take<float>(4);
-    carve_view(cv, d.mv, 2, ncand);
-    d.mv.X = d.HT; d.mv.U = d.U; d.mv.rows = d.I; d.mv.cols = d.R; d.mv.ld = d.ld; d.mv.qpr = (d.R + 3) / 4;
-    d.mv.nq = d.nq; d.mv.nelem = d.I * d.R; d.mv.done = d.flags;
-    pl.maxIp = std::max(pl.maxIp, d.Ip); pl.maxld = std::max(pl.maxld, d.ld);
-    pl.maxldm = std::max(pl.maxldm, d.ldm); pl.maxnbk = std::max(pl.maxnbk, d.nbk);
-    pl.maxI = std::max(pl.maxI, d.I); pl.maxR = std::max(pl.maxR, d.R);
-  }
-  // GEMM tiles, longest K first (LPT over the grid); `first` marks tile (0,0).
-  // 64x64 tiles (Ip > 32) first, then the 32x64 tiles of the 17..32-row factors.
-  // XCD-aware order: workgroups b and b+8 share an XCD (round-robin dispatch), so the
-  // row tiles that read the same B tile (one column tile tn of M) are laid out 8 apart:
-  // within each group of up to 8 column tiles, positions run tm-major, tn-minor.
-  pl.tiles.clear();
-  std::vector<int> order(nprob);
-  for (int i = 0; i < nprob; ++i) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pl.desc[a].ld > pl.desc[b].ld; });
-  // Wide tiles (kWideRows x 128, pl.wide, I > 64), placed by XCD: workgroup b runs on XCD
-  // b mod 8, in order of b within the XCD. These launches have I >> R (the Llama shapes),
-  // so the P row panel (kWideRows x ld) is the big operand: every row panel goes to ONE
-  // XCD (least K-step load first), which runs all of its column tiles back to back, so P is
-  // fetched once into that XCD's L2 instead of once per XCD (the column-major order kept
-  // a column tile of M per XCD and made all 8 XCDs fetch every P panel: 3.5x the
-  // algorithmic bytes at C5). Queue x fills positions x, x + 8, ...; a queue that runs
-  // out early takes tiles from the tail of the longest one.
-  std::vector<GemmTile> wide;
-  {
-    constexpr int kXcd = 8;
-    std::vector<std::vector<GemmTile>> q(kXcd);
-    std::vector<long long> qload(kXcd, 0);
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      if (!wide_prob(d)) continue;
-      const int TM = d.Ip / kWideRows, TN = (d.ld + 127) / 128;
-      for (int tm = 0; tm < TM; ++tm) {
-        const int x = (int)(std::min_element(qload.begin(), qload.end()) - qload.begin());
-        for (int tn = 0; tn < TN; ++tn) q[x].push_back(mk_tile(i, tm, tn, (tm == 0 && tn == 0) ? 1 : 0, d.ld / 32));
-        qload[x] += (long long)TN * (d.ld / 32);
-      }
-    }
-    std::vector<size_t> head(kXcd, 0);
-    size_t left = 0;
-    for (auto& v : q) left += v.size();
-    for (size_t b = 0; left > 0; ++b, --left) {
-      int x = (int)(b % kXcd);
-      if (head[x] >= q[x].size()) {   // exhausted: the longest remaining queue donates its last tile
-        int y = 0;
-        for (int z = 1; z < kXcd; ++z)
-          if (q[z].size() - head[z] > q[y].size() - head[y]) y = z;
-        wide.push_back(q[y].back());
-        q[y].pop_back();
-        continue;
-      }
-      wide.push_back(q[x][head[x]++]);
-    }
-  }
-  // persistent fp32 solve: every non-thin, non-wide factor in per-workgroup lists
-  pl.f32p = !pl.split && g_f32_kernel.load() == 1;
-  pl.f32t = !pl.split && g_f32_kernel.load() == 2;
-  pl.list_off.clear();
-  pl.nslots = 0;
-  if (pl.f32p) {
-    std::vector<GemmTile> ft;
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      if (d.I <= kThinRows || wide_prob(d)) continue;
-      const int bm = f32_tile_rows(d.I, d.ld);
-      const int TM = (d.I + bm - 1) / bm, TN = (d.ld + 63) / 64;
-      for (int tm = 0; tm < TM; ++tm)
-        for (int tn = 0; tn < TN; ++tn) {
-          GemmTile t = mk_tile(i, tm, tn, (tm == 0 && tn == 0) ? 1 : 0, d.ld / 32);
-          t.bm = bm;
-          ft.push_back(t);
-        }
-    }
-    if (!ft.empty()) {
-      const int ncu = device_cus();
-      plan_f32_lists(ft, pl.list_off, ncu);
-      pl.nslots = ncu * kF32Slots;
-    }
-    pl.tiles = ft;   // the wide tiles (if any) are inserted in front below
-  }
-  if (pl.f32t) {
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      if (d.I <= kThinRows || wide_prob(d)) continue;
-      const int bm = f32_tile_rows(d.I, d.ld);
-      const int TM = (d.I + bm - 1) / bm, TN = (d.ld + 63) / 64;
-      for (int tm = 0; tm < TM; ++tm)
-        for (int tn = 0; tn < TN; ++tn) {
-          GemmTile t = mk_tile(i, tm, tn, (tm == 0 && tn == 0) ? 1 : 0, d.ld / 32);
-          t.bm = bm;
-          pl.tiles.push_back(t);
-        }
-    }
-    order_tiles_for_cus(pl.tiles, 256, 3);
-    pl.ntiles_f32t = (int)pl.tiles.size();
-  }
-  // K-split arrival counters: one per split tile, contiguous (zeroed at the start of every run)
-  pl.nkctr = 0;
-  for (int i = 0; i < nprob; ++i)
-    if (pl.desc[i].ksplit > 1) pl.nkctr += (size_t)(pl.desc[i].Ip / 64) * ((pl.desc[i].ld + 63) / 64);
-  pl.d_kctr = cv.take<unsigned>(std::max<size_t>(pl.nkctr, 1));
-  // The 64 x 64 tile list (pieces, serial folds, CU order) is a pure function of the
-  // problems' shapes and the switches: memoised, so repeated calls (prepare and run of one
-  // call, every ALS sweep) skip the LPT placement; the per-call pointers are filled after.
-  std::vector<size_t> ctrbase(nprob, 0);
-  {
-    size_t n = 0;
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      if (d.I <= kThinRows || d.Ip == 32 || wide_prob(d) || d.ksplit <= 1) continue;
-      ctrbase[i] = n;
-      n += (size_t)(d.Ip / 64) * ((d.ld + 63) / 64);
-    }
-  }
-  if (!pl.f32p && !pl.f32t) {
-    unsigned long long key = 1469598103934665603ull;
-    auto mix = [&](long long v) {
-      for (int b = 0; b < 8; ++b) { key ^= (unsigned long long)((v >> (8 * b)) & 0xFF); key *= 1099511628211ull; }
-    };
-    mix(g_ksplit_par.load()); mix(g_ksplit_bal.load()); mix(g_ksplit_cost.load()); mix(f32_slots());
-    for (int i : order) {
-      const ProbDesc& d = pl.desc[i];
-      mix(i); mix(d.I); mix(d.Ip); mix(d.ld); mix(d.ksplit); mix(wide_prob(d) ? 1 : 0);
-    }
-    if (!tile_cache_get(key, pl.tiles, pl.ksplit_par)) {
-      build_big_tiles(pl, order, wide_prob);
-      tile_cache_put(key, pl.tiles, pl.ksplit_par);
-    }
-    for (GemmTile& t : pl.tiles)   // this call's partial images and counters
-      if (t.np > 1) {
-        const ProbDesc& d = pl.desc[t.prob];
-        const int TN = (d.ld + 63) / 64;
-        t.part = d.kpart + (size_t)(t.tm * TN + t.tn) * t.np * 4096;
-        t.ctr = pl.d_kctr + ctrbase[t.prob] + (size_t)(t.tm * TN + t.tn);
-      }
-  }
-  std::vector<GemmTile> small;
-  for (int i : order) {   // 32 x 64 tiles of the 17..32-row factors
-    const ProbDesc& d = pl.desc[i];
-    if (pl.f32p || pl.f32t) break;
-    if (d.I <= kThinRows || d.Ip != 32) continue;
-    const int TN = (d.ld + 63) / 64;
-    for (int tn = 0; tn < TN; ++tn) small.push_back(mk_tile(i, 0, tn, tn == 0 ? 1 : 0, d.ld / 32));
-  }
-  pl.ntiles_big = (pl.f32p || pl.f32t) ? 0 : (int)pl.tiles.size();   // f32p / f32t: their own launches
-  pl.ntiles_small = (int)small.size();
-  pl.ntiles_wide = (int)wide.size();
-  pl.tiles.insert(pl.tiles.end(), small.begin(), small.end());
-  pl.tiles.insert(pl.tiles.begin(), wide.begin(), wide.end());
-  // thin factors: one solve workgroup per 32 columns (thin_loop.hip), longest rows first;
-  // the same list is the persistent loop's teams (rank = column block)
-  pl.thin.clear();
-  pl.thin_maxld = 0;
-  for (int i : order) {
-    const ProbDesc& d = pl.desc[i];
-    if (d.I > kThinRows) continue;
-    pl.thin_maxld = std::max(pl.thin_maxld, d.ld);
-    for (int c = 0; c < d.ld; c += 32) {
-      ThinLoopUnit u;
-      std::memset(&u, 0, sizeof(u));
-      u.job = i; u.col0 = c; u.cw = 32; u.rank = c / 32; u.nteam = d.ld / 32;
-      pl.thin.push_back(u);
-    }
-  }
-  pl.sse_chunks.clear();
-  pl.fin_chunks.clear();
-  pl.hist_chunks.clear();
-  long long hist_units = 0;
-  std::vector<int> big_jobs;
-  for (int i = 0; i < nprob; ++i) {
-    hist_units += ((long long)pl.desc[i].I * pl.desc[i].ld + kHistElems - 1) / kHistElems;
-    if (pl.desc[i].I > kThinRows) big_jobs.push_back(i);
-  }
-  pl.fin_groups = fin_groups_for(pl.desc, big_jobs.empty() ? order : big_jobs);
-  pl.hist_nv = hist_units > kHistMaxUnits ? 2 : 1;   // one round of resident stage-1 blocks
-  // Stage-1 unit size of the big jobs: kHistElems x hist_nv, or smaller when that would
-  // leave the one round of resident blocks (2 per CU) partly filled: C3 mode 0 had 371
-  // units of ~8 k elements, so 115 CUs ran two blocks (16 k elements) and 141 one; units
-  // of about total / (2 x CUs) elements give every CU the same share (unit boundaries move
-  // only the order of the fp64 residual partial sums, never an element's result)
-  long long big_elems = 0;
-  for (int i : big_jobs) big_elems += (long long)pl.desc[i].I * pl.desc[i].ld;
-  // whole-row units of at most t elements of the big jobs
-  auto big_units = [&](long long t) {
-    long long units = 0;
-    for (int i : big_jobs) {
-      const ProbDesc& d = pl.desc[i];
-      const long long st = d.ld <= t ? (t / d.ld) * d.ld : t;
-      units += ((long long)d.I * d.ld + st - 1) / st;
-    }
-    return units;
-  };
-  // three float4 groups per thread (k_mse_hist3<.., 3, ..>) when the units at two would
-  // outnumber the fused search's resident blocks (2 per CU) and at three would not: the
-  // finalize then stays in the search launch (C4: 5.7 M elements per mode, 722 units of
-  // 8 k against 512 slots; without this, the separate k_finalize_admm launch)
-  if (pl.hist_nv == 2 && g_fin_nv3.load() && big_units((long long)kHistElems * 2) > 2LL * device_cus() &&
-      big_units((long long)kHistElems * 3) <= 2LL * device_cus())
-    pl.hist_nv = 3;
-  // (not with hist_nv = 1: a lone layer4 factor's 589 k elements in 512 one-row units
-  // instead of 171 three-row ones made its search 22 -> 27 us - the flush atomics and the
-  // ticket chain grow with the block count faster than the per-block phases shrink)
-  long long hu_big = (long long)kHistElems * pl.hist_nv;
-  if (pl.hist_nv >= 2 && g_even_units.load()) {
-    const long long slots = 2LL * device_cus();
-    int big_maxld = 0;
-    for (int i : big_jobs) big_maxld = std::max(big_maxld, pl.desc[i].ld);
-    for (long long t = std::max<long long>(big_maxld, (big_elems + slots - 1) / slots); t < hu_big; t += 256)
-      if (big_units(t) <= slots) { hu_big = t; break; }
-  }
-  // stage-1 / finalize units of the small jobs (I <= kThinRows) go last: when their
-  // fused one-block path runs (k_mse_small_admm), the launches take only the others
-  pl.small.clear();
-  pl.rows_aligned = true;
-  const long long fin_cap = 1024LL * pl.fin_groups;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int i : order) {
-      ProbDesc& d = pl.desc[i];
-      if ((d.I <= kThinRows) != (pass == 1)) continue;
-      if (pass == 1) pl.small.push_back(i);
-      for (int q = 0; q < d.nq; q += kSseQuads) pl.sse_chunks.push_back({i, q});
-      const long long tot = (long long)d.I * d.ld;
-      // whole rows per unit (rows longer than a unit: plain chunks; never a split problem)
-      const long long step = d.ld <= fin_cap ? (fin_cap / d.ld) * d.ld : fin_cap;
-      d.fin_rows = d.ld <= fin_cap ? (int)(fin_cap / d.ld) : 0;
-      for (long long e = 0; e < tot; e += step)
-        pl.fin_chunks.push_back({i, (int)e, d.mv.stat, d.flags, d.HT, d.U, std::min(tot, e + step), d.H, d.Fp, d.mv.sel});
-      // stage-1 units: whole rows where a row fits (the fused finalize needs them), each
-      // with the job's finalize inputs; `total` is the unit's end
-      const long long hu = pass == 0 ? hu_big : (long long)kHistElems * pl.hist_nv;
-      const long long hstep = d.ld <= hu ? (hu / d.ld) * d.ld : hu;
-      if (pass == 0 && d.ld > hu) pl.rows_aligned = false;
-      int nh = 0;
-      for (long long e = 0; e < tot; e += hstep, ++nh)
-        pl.hist_chunks.push_back({i, (int)e, d.mv.stat, d.flags, d.HT, d.U, std::min(tot, e + hstep), d.H, d.Fp, d.mv.sel});
-      d.mv.nhist = nh;
-    }
-    if (pass == 0) { pl.nfin_big = (int)pl.fin_chunks.size(); pl.nhist_big = (int)pl.hist_chunks.size(); }
-  }
-  // Without the fused finalize (the search launch cannot hold every unit at once, e.g.
-  // C5: ~6800 units) every block repeats the table setup (~6 us) and the histogram flush
-  // for one 8192-element unit; instead a block takes `reps` consecutive units of its job,
-  // sized for about kHistMultiRounds rounds of resident blocks.
-  pl.hist_multi.clear();
-  pl.nhm_big = 0;
-  {
-    const long long nu_all = (long long)pl.hist_chunks.size();
-    const int forced = g_hist_reps.load();
-    const int reps = forced > 0 ? forced
-                                : (int)std::max(1LL, std::min<long long>(kHistMultiMaxReps,
-                                                                         nu_all / (kHistMultiRounds * kHistMaxUnits)));
-    for (size_t a = 0; a < pl.hist_chunks.size();) {
-      size_t b = a;   // the job's units are contiguous
-      while (b < pl.hist_chunks.size() && pl.hist_chunks[b].job == pl.hist_chunks[a].job) ++b;
-      const int nblk = (int)((b - a + reps - 1) / reps);
-      for (size_t c = a; c < b; c += reps) {
-        const size_t e = std::min(b, c + reps) - 1;
-        Chunk k = pl.hist_chunks[c];
-        k.reps = (int)(e - c + 1);
-        k.step = (int)(pl.hist_chunks[c].total - pl.hist_chunks[c].start);   // a full unit unless it is the last
-        k.total = pl.hist_chunks[e].total;
-        k.nblk = nblk;
-        pl.hist_multi.push_back(k);
-      }
-      if ((int)a < pl.nhist_big) pl.nhm_big = (int)pl.hist_multi.size();
-      a = b;
-    }
-  }
-  long long small_max = 0;
-  for (int i : pl.small) small_max = std::max(small_max, (long long)pl.desc[i].I * pl.desc[i].ld);
-  pl.small_groups = small_admm_groups(small_max);
-  pl.d_ready = cv.take<unsigned long long>(2 * (size_t)nprob);
-  for (int i = 0; i < nprob; ++i) pl.desc[i].mv.ready = pl.d_ready ? pl.d_ready + 2 * i : nullptr;
-  pl.d_desc = cv.take<ProbDesc>(nprob);
-  pl.d_tiles = cv.take<GemmTile>(pl.tiles.size());
-  pl.d_list_off = cv.take<int>(pl.list_off.size() + 1);
-  pl.d_sse = cv.take<Chunk>(pl.sse_chunks.size());
-  pl.d_fin = cv.take<Chunk>(pl.fin_chunks.size());
-  pl.d_hist = cv.take<Chunk>(pl.hist_chunks.size());
-  pl.d_hist_multi = cv.take<Chunk>(pl.hist_multi.size());
-  pl.d_small = cv.take<int>(std::max<size_t>(pl.small.size(), 1));
-  pl.d_thin = cv.take<ThinLoopUnit>(pl.thin.size());
-  if ((int)pl.small.size() == nprob) {   // sized by the problems alone (not by the device's CUs)
-    pl.d_tl_sync = cv.take<ThinSync>(nprob);
-    pl.d_tl_units = cv.take<ThinLoopUnit>(pl.thin.size());   // >= the loop's workgroups
-    pl.tl_ok = plan_thin_teams(pl, device_cus());
-  }
-  pl.d_rank0 = cv.take<unsigned short>(kMaxMerged + kCells + 2);
-  pl.d_groups = cv.take<unsigned short>(3 * kMaxMerged);
-  pl.bytes = align_up(cv.off, 256);
-  return ADMMQ_OK;
-}
-
-// Fingerprint of a plan's carve (FNV-1a over the byte count, the shapes and the offsets of
-// each problem's buffers from the workspace base): equal iff prepare and run lay it out alike
-static unsigned long long plan_fingerprint(const AdmmPlan& pl, const void* ws) {
-  unsigned long long h = 1469598103934665603ull;
-  auto mix = [&](long long v) {
-    for (int b = 0; b < 8; ++b) { h ^= (unsigned long long)((v >> (8 * b)) & 0xFF); h *= 1099511628211ull; }
-  };
-  const char* base = static_cast<const char*>(ws);
-  auto off = [&](const void* p) { return p ? (long long)(static_cast<const char*>(p) - base) : -1LL; };
-  mix((long long)pl.bytes);
-  mix((long long)pl.desc.size());
-  for (const ProbDesc& d : pl.desc) {
-    mix(d.I); mix(d.R); mix(d.Ip); mix(d.ld); mix(d.ldm); mix(d.split); mix(d.ksplit);
-    mix(off(d.Fp)); mix(off(d.M)); mix(off(d.P2)); mix(off(d.kpart)); mix(off(d.mv.h1)); mix(off(d.flags));
-  }
-  mix(off(pl.d_desc)); mix(off(pl.d_tiles)); mix(off(pl.d_kctr)); mix(off(pl.d_rank0)); mix(pl.hist_nv);
-  return h;
-}
-
-static int upload_admm(AdmmPlan& pl, hipStream_t s) {
+static int upload_admm(const AdmmPlan& pl, hipStream_t s) {
   int rc;
   if ((rc = h2d(pl.d_desc, pl.desc.data(), pl.desc.size() * sizeof(ProbDesc), s))) return rc;
-  for (GemmTile& t : pl.tiles) {
-    const ProbDesc& d = pl.desc[t.prob];
-    t.U = d.U; t.ld = d.ld; t.ldm = d.ldm;
-    if (d.split) {   // the fp16 planes keep the fp32 rows' strides (in floats)
-      t.P = reinterpret_cast<const float*>(d.P2); t.M = reinterpret_cast<const float*>(d.M2);
-      t.eP = d.eP; t.eM = d.eM;
-    } else {
-      t.P = d.P; t.M = d.M;
-    }
-  }
   if ((rc = h2d(pl.d_tiles, pl.tiles.data(), pl.tiles.size() * sizeof(GemmTile), s))) return rc;
   if (!pl.list_off.empty() && (rc = h2d(pl.d_list_off, pl.list_off.data(), pl.list_off.size() * sizeof(int), s)))
     return rc;
@@ -1262,8 +475,22 @@ int32_t admmq_debug_set_fused_finalize(int32_t enable) {
 // and the real carve agree
 size_t admmq_debug_admm_plan_bytes(const admmq_problem* probs, int32_t nprob, int32_t num_attempts, void* base) {
   AdmmPlan pl;
-  if (plan_admm(probs, nprob, num_attempts, base, pl, g_solve_mode.load()) != ADMMQ_OK) return 0;
+  if (plan_admm(probs, nprob, num_attempts, base, plan_switches(), g_solve_mode.load(), device_cus(), pl) != ADMMQ_OK) return 0;
   return pl.bytes;
+}
+
+// diagnostics (not in include/admmq.h): eight per-section digests of the plan that
+// admmq_admm_prepare_ex would build with workspace = base (plan_digest; `base` is never
+// dereferenced), so a test can pin the planner's output
+int32_t admmq_debug_admm_plan_digest(const admmq_problem* probs, int32_t nprob, int32_t num_attempts,
+                                     int32_t solve_mode, void* base, uint64_t out[8]) {
+  if (!out || !base) return fail(ADMMQ_ERR_ARG, "plan digest: base and out must not be NULL");
+  if (solve_mode != kSolveF32 && solve_mode != kSolveSplit) return fail(ADMMQ_ERR_ARG, "solve mode must be 0 (fp32) or 1 (split)");
+  AdmmPlan pl;
+  const int rc = plan_admm(probs, nprob, num_attempts, base, plan_switches(), solve_mode, device_cus(), pl);
+  if (rc) return rc;
+  plan_digest(pl, base, out);
+  return ADMMQ_OK;
 }
 
 // diagnostics (not in include/admmq.h): 1 (default) = the search takes three float4 groups
@@ -1359,7 +586,7 @@ int64_t admmq_debug_ksplit_balance_count(const int32_t* IR, int32_t nprob) {
       if (np > 1) cand.push_back({ld / 32, np});
     }
   }
-  return ksplit_balance(whole, cand, 256, f32_slots(), g_ksplit_cost.load());
+  return ksplit_balance(whole, cand, kPlanChipCUs, f32_slots(g_gemm_f32_stage), g_ksplit_cost.load());
 }
 // diagnostics: the wide-tile threshold (64x64 tiles per launch; default 4 x 768)
 int32_t admmq_debug_set_wide_min_tiles(int64_t t) {
@@ -1457,7 +684,7 @@ size_t admmq_admm_workspace_size_ex(const admmq_problem* probs, int32_t nprob, i
                                     const admmq_admm_options* opt) {
   if (check_opts(opt)) return 0;
   AdmmPlan pl;
-  if (plan_admm(probs, nprob, num_attempts, nullptr, pl, opt->solve_mode) != ADMMQ_OK) return 0;
+  if (plan_admm(probs, nprob, num_attempts, nullptr, plan_switches(), opt->solve_mode, device_cus(), pl) != ADMMQ_OK) return 0;
   return pl.bytes;
 }
 
@@ -1471,7 +698,7 @@ int32_t admmq_admm_prepare_ex(const admmq_problem* probs, int32_t nprob, int32_t
   int rc = check_opts(opt);
   if (rc) return rc;
   AdmmPlan pl;
-  rc = plan_admm(probs, nprob, num_attempts, workspace, pl, opt->solve_mode);
+  rc = plan_admm(probs, nprob, num_attempts, workspace, plan_switches(), opt->solve_mode, device_cus(), pl);
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1510,7 +737,7 @@ int32_t admmq_admm_run_ex(const admmq_problem* probs, int32_t nprob, int32_t max
   const int rec = wr.mode;
   if (rec != opt->solve_mode) return fail(ADMMQ_ERR_ARG, "admm_run: solve_mode differs from the one its prepare used");
   AdmmPlan pl;
-  rc = plan_admm(probs, nprob, num_attempts, workspace, pl, rec);
+  rc = plan_admm(probs, nprob, num_attempts, workspace, plan_switches(), rec, device_cus(), pl);
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   if (plan_fingerprint(pl, workspace) != wr.fp)

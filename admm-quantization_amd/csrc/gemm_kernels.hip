@@ -110,7 +110,7 @@ __device__ __forceinline__ void wait_vmcnt() {
 __device__ __forceinline__ f16x8 as_h8(float4 v) { return __builtin_bit_cast(f16x8, v); }
 
 // K-split combine of a 64 x 64 fp32 tile (4 waves, 256 threads, one f32x16 accumulator
-// per thread in the 32x32x2 C/D layout; api.hip ksplit_pieces). Piece pc of np has summed
+// per thread in the 32x32x2 C/D layout; admm_plan.hip ksplit_pieces). Piece pc of np has summed
 // K-steps [k0, k0 + nk) of the tile. Every piece publishes its partial: 4 x 16-B sc1
 // (write-through) stores per thread into slot pc of the tile's partial images, laid out
 // by thread, so each thread later reads back exactly the elements it owns; each storing
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
 // ---------------------------------------------------------------------------
 // Persistent fp32 solve (kSolveF32, launches without wide tiles): kF32Slots workgroups
 // per CU, workgroup b runs the tiles list[off[b] .. off[b+1]) one after another. The host
-// (api.hip: plan_f32_lists) places the tiles by LPT over the CUs on their MFMA work
+// (admm_plan.hip: plan_f32_lists) places the tiles by LPT over the CUs on their MFMA work
 // (workgroups b and b + ncu share CU b, round-robin dispatch; placement is only for
 // speed), so a launch's length is set by the CU total rather than by how the largest
 // tiles happen to land. Tile shapes (fixed per problem, so every element's result is

@@ -134,7 +134,7 @@ def test_als_contractions_refuse_cpu_tensors():
 
 
 def test_ksplit_pieces_by_shape(lib):
-    """K-split pieces of the fp32 solve tiles (api.hip ksplit_pieces) depend on (I, R)
+    """K-split pieces of the fp32 solve tiles (admm_plan.hip ksplit_pieces) depend on (I, R)
     only: the resnet18 layer4 conv modes (512, 1141) take 3 pieces of 12 K-steps, the
     (512, 759) ones 2, the mid layers 2-4, factors whose tiles fill the chip (C5, resnet50
     (2048, 204)), 32-row and thin factors, and short K ranges none."""

@@ -318,7 +318,7 @@ def test_fp32_staging_forms_equal(torch_dev):
 
 
 def test_ksplit_factors(torch_dev):
-    """K-split solve tiles (api.hip ksplit_pieces: the pieces are fixed by the factor's
+    """K-split solve tiles (admm_plan.hip ksplit_pieces: the pieces are fixed by the factor's
     shape; gemm_kernels.hip: run in parallel by np workgroups with the ksplit_combine
     hand-off, or folded serially by one workgroup - the same float32 sums): the lone
     layer4 conv factor (512, 1141) -> 3 pieces, (512, 759) -> 2, (256, 759) -> 4,
