@@ -606,9 +606,23 @@ __device__ __forceinline__ void h3_load_order(const unsigned short* __restrict__
   (void)ngroups;
 }
 
+constexpr int kTsortPad = 4;   // +inf entries after the M sorted thresholds (LDS layout: hist3_lds_bytes)
+
+// The bucket arrays (sumA, sumN, cntA, cntN: contiguous from a 16-byte boundary, nb entries
+// each) zeroed with 16-byte LDS stores, by the kernel before it calls h3_setup (whose barriers
+// stand before the first insert): k_mse_hist3 before it first uses max|x|, so the stores
+// overlap the wait for that load.
+__device__ __forceinline__ void h3_zero_buckets(unsigned long long* sumA, int nb, int nt) {
+  const int nbytes = nb * 24;   // a multiple of 8
+  uint4* z4 = reinterpret_cast<uint4*>(sumA);
+  for (int i = threadIdx.x; i < nbytes / 16; i += nt) z4[i] = make_uint4(0u, 0u, 0u, 0u);
+  if ((nbytes & 8) && threadIdx.x == 0) sumA[nbytes / 8 - 1] = 0ull;
+}
+
 // Stage-1 table of one job in LDS (the setup of k_mse_hist3 and k_mse_small_admm): the
 // thresholds in the host's merged order with the tie groups ordered by value, L per
-// (level, candidate), the coarse cell index; the buckets zeroed. Returns the cell scale.
+// (level, candidate), the coarse cell index, kTsortPad entries of +inf after the sorted
+// thresholds (the caller zeroes the buckets: h3_zero_buckets). Returns the cell scale.
 //
 // L and the cell index come almost entirely from the host (they do not depend on mx):
 // distinct keys give distinct thresholds, so L = rank + 1 outside the tie groups, and
@@ -626,7 +640,6 @@ __device__ __forceinline__ float h3_setup(float mx, int n, const H3Pre& pre,
                                          unsigned* cntN, float* thr, float* tsort, unsigned short* rnk,
                                          unsigned short* cell, int nt) {
   const int M = QMAX * n;
-  const int nb = M + 1 + 64;
   ADMMQ_SETUP_STAMP(0);
   // the host cell index (kCells + 1 entries as u32 pairs), issued first: used only at
   // the end of the setup
@@ -645,18 +658,20 @@ __device__ __forceinline__ float h3_setup(float mx, int n, const H3Pre& pre,
   __syncthreads();
   // thresholds, each also scattered to its host-order rank (kR0 * nt >= kMaxMerged >= M);
   // L = rank + 1 (tie groups below)
+  // e / n as a multiply: with m = ceil(2^32 / n), floor(e m / 2^32) = floor(e / n) for e n < 2^32
+  // (e < kMaxMerged, n <= kMaxStage1)
+  const unsigned rcpn = 0xFFFFFFFFu / (unsigned)n + 1u;
 #pragma unroll
   for (int j = 0; j < kR0; ++j) {
     const int e = threadIdx.x + j * nt;
     if (e < M) {
-      const int k = 1 + e / n, c = e - (k - 1) * n;
+      const int k = 1 + (int)__umulhi((unsigned)e, rcpn), c = e - (k - 1) * n;
       const float v = level_threshold_fast(scand[c], k);
       thr[e] = v;
       tsort[pre.r0v[j]] = v;
       rnk[e] = (unsigned short)(pre.r0v[j] + 1);
     }
   }
-  for (int i = threadIdx.x; i < nb; i += nt) { sumA[i] = 0ull; sumN[i] = 0ull; cntA[i] = 0u; cntN[i] = 0u; }
   __syncthreads();
   ADMMQ_SETUP_STAMP(1);
   // exact-key ties: order by actual value, L = 1 + index of the last equal value (the
@@ -664,6 +679,16 @@ __device__ __forceinline__ float h3_setup(float mx, int n, const H3Pre& pre,
   // make the compiler wait for every outstanding load, the elements included)
   auto tie_group = [&](const unsigned short* gr) {
     const int r0 = gr[0], m = gr[1];
+    if (m == 2) {   // (nearly every group: 5 of 5 at 200 candidates and 4 bits) the same order and L, without the loops
+      const int e0 = gr[2], e1 = gr[3];
+      const float v0 = thr[e0], v1 = thr[e1];
+      const bool sw = v0 > v1;
+      tsort[r0] = sw ? v1 : v0;
+      tsort[r0 + 1] = sw ? v0 : v1;
+      rnk[sw ? e1 : e0] = (unsigned short)(r0 + (v0 == v1 ? 2 : 1));
+      rnk[sw ? e0 : e1] = (unsigned short)(r0 + 2);
+      return;
+    }
     int es[4];
     float vs[4];
     for (int j = 0; j < m; ++j) { es[j] = gr[2 + j]; vs[j] = thr[es[j]]; }
@@ -694,6 +719,8 @@ __device__ __forceinline__ float h3_setup(float mx, int n, const H3Pre& pre,
     const int i = threadIdx.x + j * nt;
     if (j < ncw && i < kCellWords) cell32[i] = cv[j];
   }
+  // +inf past the sorted thresholds: h3_insert_n's probes need neither a clamp nor a bound
+  if (threadIdx.x < kTsortPad) tsort[M + threadIdx.x] = __builtin_inff();
   __syncthreads();
   ADMMQ_SETUP_STAMP(2);
   // the order check (sorted thresholds non-decreasing); the cell scale from the largest
@@ -744,10 +771,10 @@ __device__ __forceinline__ void h3_insert_n(const float* xs, float inv, const fl
   bool more[N];
 #pragma unroll
   for (int j = 0; j < N; ++j) {
+    // (b0 <= M, and entries M .. M + 2 are +inf, h3_setup: the ranks past the last count nothing)
     const int b0 = B[j];
-    const float p0 = tsort[min(b0, M - 1)], p1 = tsort[min(b0 + 1, M - 1)], p2 = tsort[min(b0 + 2, M - 1)];
-    const int cnt = (b0 < hi[j] && p0 <= a[j] ? 1 : 0) + (b0 + 1 < hi[j] && p1 <= a[j] ? 1 : 0) +
-                    (b0 + 2 < hi[j] && p2 <= a[j] ? 1 : 0);   // sorted: the prefix of <= a
+    const float p0 = tsort[b0], p1 = tsort[b0 + 1], p2 = tsort[b0 + 2];
+    const int cnt = (p0 <= a[j] ? 1 : 0) + (p1 <= a[j] ? 1 : 0) + (p2 <= a[j] ? 1 : 0);   // sorted: the prefix of <= a
     B[j] = b0 + cnt;
     more[j] = cnt == 3;
   }
@@ -926,9 +953,11 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
     }
   }
   const MseView& v = mview(d, qj, ck.job);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  // the buckets zeroed while the loads above are in flight (nothing loaded is used yet)
+  h3_zero_buckets(reinterpret_cast<unsigned long long*>(smem), QMAX * ncand + 1 + 64, kH3Threads);
   if (stopped) return;
   int* sel = v.sel + (size_t)slot * (2 + kMaxSel);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ double red[8];
   __shared__ unsigned long long wtot[8], wtot2[8];
   __shared__ unsigned wtot32[8], wtot32b[8];
@@ -950,6 +979,7 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
   if (mse_degenerate(mx)) {     // the projection emits NaN for degenerate mx (no search)
     if (ck.start == 0 && threadIdx.x == 0) { sel[0] = 1; sel[1] = 0; }
     if constexpr (FIN) {   // (one unit per block)
+      __syncthreads();   // the zeroing above is done before the finalize reuses the LDS
       const ProbDesc& p = d[ck.job];
 #pragma unroll
       for (int hh = 0; hh < 2 * NV; ++hh) {
@@ -971,8 +1001,8 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
   unsigned* cntA = reinterpret_cast<unsigned*>(sumN + nb);
   unsigned* cntN = cntA + nb;
   float* thr = reinterpret_cast<float*>(cntN + nb);                          // M
-  float* tsort = thr + M;                                                    // M
-  unsigned short* rnk = reinterpret_cast<unsigned short*>(tsort + M);        // M: rank, then L
+  float* tsort = thr + M;                                                    // M, then kTsortPad of +inf
+  unsigned short* rnk = reinterpret_cast<unsigned short*>(tsort + M + kTsortPad);   // M: rank, then L
   unsigned short* cell = rnk + ((M + 1) & ~1);                               // kCells + 1
   const float inv = h3_setup<QMAX>(mx, n, pre, groups, ngroups, rank0 + kMaxMerged, sumA, sumN, cntA, cntN, thr, tsort,
                                    rnk, cell, kH3Threads);
@@ -1267,8 +1297,9 @@ __global__ __launch_bounds__(kSmallThreads) void k_mse_small_admm(const ProbDesc
     unsigned* cntN = cntA + nb;
     float* thr = reinterpret_cast<float*>(cntN + nb);
     float* tsort = thr + M;
-    unsigned short* rnk = reinterpret_cast<unsigned short*>(tsort + M);
+    unsigned short* rnk = reinterpret_cast<unsigned short*>(tsort + M + kTsortPad);
     unsigned short* cell = rnk + ((M + 1) & ~1);
+    h3_zero_buckets(sumA, nb, kSmallThreads);
     const float inv = h3_setup<QMAX>(mx, n, pre, groups, ngroups, rank0 + kMaxMerged, sumA, sumN, cntA, cntN, thr,
                                      tsort, rnk, cell, kSmallThreads);
     // the stop test after the (LDS-only) setup: tested earlier, the compiler would sink
@@ -1353,7 +1384,8 @@ void launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ng
 size_t hist3_lds_bytes(int ncand, int bits) {
   const size_t M = (size_t)ncand << (bits - 1);
   const size_t nb = M + 1 + 64;
-  const size_t bytes = nb * (8 + 8 + 4 + 4) + M * 8 + (((M + 1) & ~(size_t)1) + kCells + 2) * 2 + (size_t)ncand * 4;
+  const size_t bytes = nb * (8 + 8 + 4 + 4) + M * 8 + kTsortPad * 4 + (((M + 1) & ~(size_t)1) + kCells + 2) * 2 +
+                       (size_t)ncand * 4;
   return std::max((bytes + 15) & ~(size_t)15, (size_t)kSseQuads * 16);
 }
 
