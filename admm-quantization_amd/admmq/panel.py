@@ -22,6 +22,12 @@ from . import _lib
 # streams from racing on the same slots and counters. A workspace is allocated on its own
 # stream, so when it is grown the caching allocator reuses the old block only for later work
 # of that same stream - never while another stream's kernel may still read it.
+# The exception is the blocked EPC step (epc_step64_gen): it is not one call but a sequence
+# begin / rounds / end that keeps its search state and job tables in the workspace while the
+# generator is suspended, and other work of the same stream (another layer's step: PyTorch
+# hands the same stream handle to several torch.cuda.Stream objects) runs in between. Stream
+# order does not protect that, so every step allocates a workspace of its own
+# (_step_workspace) and no cache is involved.
 _WS: "OrderedDict[Tuple[torch.device, int], torch.Tensor]" = OrderedDict()
 _GWS: "OrderedDict[Tuple[torch.device, int], torch.Tensor]" = OrderedDict()
 
@@ -151,7 +157,7 @@ SPD_SMALL_MAX = 136   # n of the one-workgroup fp64 solves (csrc/epc_kernels.hip
 EPC_FIRST_ROUNDS = 3   # blocked EPC step: evaluation rounds queued before the first read of its done flag
 EPC_NEXT_ROUNDS = 2    # ... and between later reads
 
-_SWS: "OrderedDict[Tuple[torch.device, int], torch.Tensor]" = OrderedDict()   # blocked-solve workspaces
+_SWS: "OrderedDict[Tuple[torch.device, int], torch.Tensor]" = OrderedDict()   # spd_solve64's blocked-solve workspaces
 _CACHE_MAX = 64   # workspaces kept per cache (least recently used dropped; see _cached)
 
 
@@ -168,6 +174,20 @@ def _cached(cache, dev: torch.device, nbytes: int, zero: bool) -> torch.Tensor:
     while len(cache) > _CACHE_MAX:
         cache.popitem(last=False)
     return ws
+
+
+def _step_workspace(dev: torch.device, nbytes: int) -> torch.Tensor:
+    """A fresh workspace for one blocked EPC step (``epc_step64_gen``), allocated on the current
+    stream and owned by that step until it returns: two live steps never share one, whatever
+    stream handles they run on. The caching allocator makes this cheap and hands a released
+    block only to later work of the stream it was allocated on."""
+    return _lib.workspace(nbytes, dev)
+
+
+def epc64_max_evals() -> int:
+    """The blocked EPC step's evaluation budget on the device (``admmq_epc64_max_evals``): after
+    that many rounds the search is done, converged or not."""
+    return int(_lib.load().admmq_epc64_max_evals())
 
 
 def _check_solve(G: torch.Tensor, F: torch.Tensor, what: str):
@@ -196,7 +216,10 @@ def spd_solve64(G: torch.Tensor, F: torch.Tensor, info: Optional[torch.Tensor] =
     (``csrc/solve64.hip``). A G that is not numerically positive definite sets ``info`` (a
     one-element int32 device tensor) to 1 and leaves X undefined; without ``info`` it goes
     unnoticed, so the drivers always pass one (``admmq.parafac_epc`` retries such an update
-    with a small relative shift)."""
+    with a small relative shift). The blocked form's workspace is the current stream's cached
+    one: the solve is a single call that keeps nothing in it afterwards, and calls on one stream
+    handle are stream-ordered, so sharing it is safe. A blocked EPC step suspended on the same
+    stream is not disturbed: it has a workspace of its own (``epc_step64_gen``)."""
     G, F = _check_solve(G, F, "spd_solve64")
     m, n = F.shape
     X = torch.empty(F.shape, dtype=torch.float64, device=F.device)
@@ -252,10 +275,12 @@ def epc_step64_gen(G: torch.Tensor, F: torch.Tensor, normY2: float, delta2: floa
     device) and yields a ``torch.cuda.Event`` whenever it needs the done flag on the host
     (``EPC_FIRST_ROUNDS`` rounds, then ``EPC_NEXT_ROUNDS`` per read); resume it once the event has
     completed. Returns X = F (G + mu I)^-1; ``mu`` updated in place, ``info`` as ``epc_step64``.
-    The step's search state lives in the current stream's cached workspace, so one stream runs
-    one blocked step (or blocked solve) at a time: finish this generator before the next such
-    call on its stream. ``admmq.parafac_epc`` drives several of these at once, one layer per
-    stream."""
+    The step's search state, descriptor and GEMM job tables live in a workspace that this
+    generator allocates for itself (``_step_workspace``) and holds until it returns, never in a
+    per-stream cache: any number of steps, blocked solves and other work may be interleaved with
+    it on one stream handle between its yields. Every resume must run on the stream the
+    generator was started on. ``admmq.parafac_epc`` drives several of these at once, one layer
+    per ``torch.cuda.Stream`` (several of which can be the same HIP stream)."""
     G, F = _check_solve(G, F, "epc_step64")
     m, n = F.shape
     if mu.dtype != torch.float64 or mu.numel() != 1 or mu.device != F.device:
@@ -264,13 +289,14 @@ def epc_step64_gen(G: torch.Tensor, F: torch.Tensor, normY2: float, delta2: floa
     dev = F.device
     X = torch.empty(F.shape, dtype=torch.float64, device=dev)
     nb = lib.admmq_solve64_workspace_size(m, n)
-    ws = _cached(_SWS, dev, nb, zero=False)
+    ws = _step_workspace(dev, nb)   # this step's alone, from begin64 to end64
     done = torch.zeros(1, dtype=torch.int32, device=dev)
     st = _lib.stream_handle(dev)
+    budget = epc64_max_evals()
     _lib.check(lib.admmq_epc_begin64(_lib.ptr(G), _lib.ptr(F), m, n, float(normY2), float(delta2), _lib.ptr(mu),
                                      _lib.ptr(X), _lib.ptr(ws), ws.numel(), st), "epc_begin64")
     rounds, total = EPC_FIRST_ROUNDS, 0
-    while total < 96:   # the device search's evaluation budget (kS64MaxEvals, csrc/solve64.hip)
+    while total < budget:   # the device search's evaluation budget: done is set by then
         _lib.check(lib.admmq_epc_rounds64(_lib.ptr(G), _lib.ptr(F), m, n, _lib.ptr(X), rounds, _lib.ptr(done),
                                           _lib.ptr(ws), ws.numel(), st), "epc_rounds64")
         total += rounds

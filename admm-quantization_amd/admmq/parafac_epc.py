@@ -292,7 +292,12 @@ def _drive_many(gens: Sequence, device: torch.device) -> list:
     """Interleaves generators of this module, each on its own HIP stream (forked from the
     current stream): a generator resumes once the event it yielded has completed, so one
     layer's host reads never hold back another layer's queued work. The current stream
-    waits for all of them at the end, and the results are recorded as used on it."""
+    waits for all of them at the end, and the results are recorded as used on it. PyTorch
+    serves ``torch.cuda.Stream`` objects from a pool, so with many layers several of them
+    are the same HIP stream: those layers' work is then merely serialised (nothing here or
+    in ``admmq.panel`` keeps state per stream handle across a yield). When a layer raises,
+    the error propagates, but the current stream still waits for the side streams first:
+    whatever the other layers had queued is ordered before the caller's next work."""
     main = torch.cuda.current_stream(device)
     streams = [torch.cuda.Stream(device) for _ in gens]
     for s in streams:
@@ -300,23 +305,25 @@ def _drive_many(gens: Sequence, device: torch.device) -> list:
     pending = [None] * len(gens)   # the event each generator waits on (None: runnable)
     results = [None] * len(gens)
     active = list(range(len(gens)))
-    while active:
-        progressed = False
-        for i in list(active):
-            ev = pending[i]
-            if ev is not None and not ev.query():
-                continue
-            progressed = True
-            with torch.cuda.stream(streams[i]):
-                try:
-                    pending[i] = gens[i].send(None)
-                except StopIteration as stop:
-                    results[i] = stop.value
-                    active.remove(i)
-        if not progressed:   # every layer waits on the device: block on the oldest
-            pending[active[0]].synchronize()
-    for s in streams:
-        main.wait_stream(s)
+    try:
+        while active:
+            progressed = False
+            for i in list(active):
+                ev = pending[i]
+                if ev is not None and not ev.query():
+                    continue
+                progressed = True
+                with torch.cuda.stream(streams[i]):
+                    try:
+                        pending[i] = gens[i].send(None)
+                    except StopIteration as stop:
+                        results[i] = stop.value
+                        active.remove(i)
+            if not progressed:   # every layer waits on the device: block on the oldest
+                pending[active[0]].synchronize()
+    finally:
+        for s in streams:
+            main.wait_stream(s)
     for lm, us in results:
         for t in [lm, *us]:
             t.record_stream(main)

@@ -265,6 +265,8 @@ int32_t admmq_debug_s64_evals(unsigned long long* out, int32_t reset) {
   return ADMMQ_OK;
 }
 
+int32_t admmq_epc64_max_evals(void) { return kS64MaxEvals; }
+
 size_t admmq_solve64_workspace_size(int64_t m, int64_t n) {
   if (m < 1 || n < 1 || n > 8192 || m > (1LL << 24) || m * n >= (1LL << 31)) return 0;
   S64Layout L;

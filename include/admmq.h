@@ -337,9 +337,18 @@ int32_t admmq_epc_step64(const double* G, const double* F, int64_t m, int64_t n,
  *                          caller reads it when it chooses and asks for more rounds until then.
  *                          end writes *mu (device double) and *info (device int, may be NULL): 0
  *                          converged (X = F (G + mu I)^-1 at the returned mu), 1 no positive definite
- *                          G + mu I found or the evaluation budget (96) spent, 2 not done yet. The same
- *                          G, F, X, m, n and workspace for every call of one step. */
+ *                          G + mu I found or the evaluation budget (admmq_epc64_max_evals()) spent, 2 not
+ *                          done yet.
+ *                          Contract of one step: from begin to end the workspace belongs to that step. It
+ *                          holds the search state, the Cholesky's descriptor, the GEMM job tables and the
+ *                          A / L^-1 / product planes between the calls, so no other blocked solve or step
+ *                          may use it in between, not even on the same stream (stream order does not
+ *                          help: the step is not over when a call returns). rounds64 / end64 must be
+ *                          given begin's m and n, and rounds64 begin's G, F and X: the job tables keep
+ *                          begin's pointers and extents. Neither is checked.
+ *   admmq_epc64_max_evals  the search's evaluation budget: after that many rounds *done is 1. */
 size_t admmq_solve64_workspace_size(int64_t m, int64_t n);
+int32_t admmq_epc64_max_evals(void);
 int32_t admmq_spd_solve64_ws(const double* G, const double* F, int64_t m, int64_t n, double rel_shift, double* X,
                              int32_t* info, void* workspace, size_t workspace_bytes, void* stream);
 int32_t admmq_epc_begin64(const double* G, const double* F, int64_t m, int64_t n, double normY2, double delta2,

@@ -218,3 +218,19 @@ def test_blocked_solves_check_arguments(lib):
     assert lib.admmq_epc_rounds64(p, p, 4, 200, p, 1, None, p, 8, None) == ERR_WS
     assert lib.admmq_epc_end64(0, 200, p, None, p, 1 << 30, None) == ERR_ARG
     assert lib.admmq_epc_end64(4, 200, p, None, p, 8, None) == ERR_WS
+
+
+def test_epc64_budget_is_the_librarys(lib):
+    """The blocked EPC step's evaluation budget has one home, the library
+    (admmq_epc64_max_evals): the host loop of panel.epc_step64_gen reads it and carries no
+    number of its own, and the step takes its workspace from panel._step_workspace, not from
+    the per-stream cache."""
+    import inspect
+    from admmq import panel
+    budget = lib.admmq_epc64_max_evals()
+    assert budget > 0
+    assert panel.epc64_max_evals() == budget
+    src = inspect.getsource(panel.epc_step64_gen)
+    assert "while total < budget" in src and "budget = epc64_max_evals()" in src
+    assert not re.search(r"\b96\b", src)
+    assert "_step_workspace(" in src and "_cached(" not in src

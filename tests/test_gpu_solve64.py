@@ -186,6 +186,185 @@ def test_parafac_epc_many_equals_single():
             assert torch.equal(a, b)
 
 
+def _epc_problem(n, m, seed, over):
+    """(G, F, normY2, delta2) on the device, built as in test_blocked_epc_step_vs_eigen_form: the
+    target error is `over` times the least-squares step's, so the root mu is positive."""
+    G, g = _spd(n, seed)
+    F = torch.randn(m, n, generator=g, dtype=torch.float64)
+    s, V = torch.linalg.eigh(G)
+    Ft = F @ V
+    ls = float(torch.sum(torch.sum(Ft * Ft, dim=0) / s))
+    normY2 = ls * 1.5
+    return G.cuda(), F.cuda(), normY2, (normY2 - ls) * over
+
+
+def _step_args(prob):
+    G, F, normY2, delta2 = prob
+    mu = torch.zeros((), dtype=torch.float64, device="cuda")
+    info = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    return (G, F, normY2, delta2, mu), info
+
+
+def _interleave(gens, between=None):
+    """Advances the generators alternately on the current stream (each resumed once the event
+    it yielded has completed; `between` runs before every resume) and returns their values."""
+    waiting = {i: next(g) for i, g in enumerate(gens)}   # every step begun before any resumes
+    out = [None] * len(gens)
+    while waiting:
+        for i in list(waiting):
+            waiting[i].synchronize()
+            if between is not None:
+                between()
+            try:
+                waiting[i] = gens[i].send(None)
+            except StopIteration as stop:
+                out[i] = stop.value
+                del waiting[i]
+    torch.cuda.synchronize()
+    return out
+
+
+def _disjoint(a, b):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 + a.numel() * a.element_size() <= b0 or b0 + b.numel() * b.element_size() <= a0
+
+
+@pytest.mark.parametrize("n", [150, 300])
+def test_interleaved_blocked_steps_on_one_stream(n, monkeypatch):
+    """Two blocked EPC steps of one (m, n) advanced alternately on ONE stream, and one step with
+    blocked CP-ALS solves issued on that stream between its yields: every X, mu and info has the
+    bits of the same step (solve) run alone, and the live steps were given storage that overlaps
+    neither each other's nor the stream's cached solve workspace. (A workspace shared per stream
+    handle - which PyTorch's stream pool gives to layers i and i + 32 of parafac_epc_many - lets
+    the second step's begin overwrite the first's search state and GEMM job tables.)"""
+    from admmq import panel
+    m = 24
+    probs = [_epc_problem(n, m, 1000 + n, 1.5), _epc_problem(n, m, 2000 + n, 2.5)]
+    assert not torch.equal(probs[0][0], probs[1][0])
+    solo = []
+    for p in probs:
+        args, info = _step_args(p)
+        X = panel.epc_step64(*args, info=info)
+        torch.cuda.synchronize()
+        assert int(info) == 0 and float(args[4]) > 0.0
+        solo.append((X, args[4], info))
+    assert not torch.equal(solo[0][0], solo[1][0])
+
+    given = []
+    alloc = panel._step_workspace
+
+    def recording(dev, nbytes):
+        ws = alloc(dev, nbytes)
+        given.append(ws)   # kept alive here, so two entries can never be one reused block
+        return ws
+
+    monkeypatch.setattr(panel, "_step_workspace", recording)
+
+    # (1) A and B interleaved
+    runs = [_step_args(p) for p in probs]
+    Xs = _interleave([panel.epc_step64_gen(*args, info=info) for args, info in runs])
+    assert len(given) == 2 and _disjoint(given[0], given[1])
+    for (args, info), X, (X1, mu1, info1) in zip(runs, Xs, solo):
+        assert torch.equal(X, X1)
+        assert torch.equal(args[4], mu1)
+        assert torch.equal(info, info1)
+
+    # (2) A with a blocked solve (n = 150, m = 24) on the same stream before every resume
+    Gs, g = _spd(150, 77)
+    Gs, Fs = Gs.cuda(), torch.randn(m, 150, generator=g, dtype=torch.float64).cuda()
+    sinfo1 = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    Xs1 = panel.spd_solve64(Gs, Fs, info=sinfo1)
+    torch.cuda.synchronize()
+    assert int(sinfo1) == 0
+    del given[:]
+    solves = []
+
+    def solve():
+        sinfo = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        solves.append((panel.spd_solve64(Gs, Fs, info=sinfo), sinfo))
+
+    args, info = _step_args(probs[0])
+    (X,) = _interleave([panel.epc_step64_gen(*args, info=info)], between=solve)
+    assert len(given) == 1 and len(solves) >= 1
+    assert _disjoint(given[0], panel._SWS[panel._key(Gs.device)])
+    assert torch.equal(X, solo[0][0])
+    assert torch.equal(args[4], solo[0][1])
+    assert torch.equal(info, solo[0][2])
+    for Xs2, sinfo in solves:
+        assert torch.equal(Xs2, Xs1) and int(sinfo) == 0
+
+
+_MANY_KW = dict(als_maxiter=6, epc_maxiter=6, epc_rounds=2)
+
+
+def _assert_same_cp(got, want):
+    (lm, us), (lm1, us1) = got, want
+    assert torch.equal(lm, lm1)
+    assert len(us) == len(us1)
+    for a, b in zip(us, us1):
+        assert torch.equal(a, b)
+
+
+def test_parafac_epc_many_more_layers_than_pooled_streams():
+    """34 layers, more than the 32 streams of PyTorch's pool: layers i and i + 32 run on one HIP
+    stream handle, and the pairs (0, 32) and (1, 33) are both blocked steps (R = 150) of one
+    shape, i.e. of one workspace size. Every layer has the bits of its own parafac_epc call."""
+    from admmq import parafac_epc as pe
+    cycle = ((12, 10, 9), (16, 8, 9), (9, 14, 10))
+    shapes = [cycle[i % 3] for i in range(34)]
+    shapes[32], shapes[33] = shapes[0], shapes[1]
+    ranks = [150 if i in (0, 1, 32, 33) else 6 for i in range(34)]
+    g = torch.Generator().manual_seed(34)
+    Ys = [torch.randn(*s, generator=g, dtype=torch.float64).cuda() for s in shapes]
+    dev = Ys[0].device
+    handles = {s.cuda_stream for s in [torch.cuda.Stream(dev) for _ in range(34)]}
+    print(f"34 torch.cuda.Stream objects -> {len(handles)} distinct HIP stream handles")
+    many = pe.parafac_epc_many(Ys, ranks, **_MANY_KW)
+    assert len(many) == 34
+    for Y, R, got in zip(Ys, ranks, many):
+        _assert_same_cp(got, pe.parafac_epc(Y, R, **_MANY_KW))
+
+
+@pytest.mark.parametrize("init", ["random", "svd", "parafac-epc"])
+def test_init_factors_many_equals_per_layer(init):
+    """init_factors_many (what factorize_layers calls for a whole model) returns, layer by layer,
+    the float32 factors of init_factors with the same seed and device: 3-way and 2-way tensors,
+    ranks below and above the mode sizes, all at or below the one-workgroup solves' 136."""
+    from admmq import init_factors, init_factors_many
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(21)
+    Ws = [torch.randn(*s, generator=g).to(dev) for s in ((8, 6, 9), (16, 12, 9), (20, 14))]
+    ranks = [5, 20, 6]
+    many = init_factors_many(Ws, ranks, init=init, device=dev, seed=11)
+    assert isinstance(many, list) and len(many) == 3
+    for W, R, fs in zip(Ws, ranks, many):
+        one = init_factors(W, rank=R, init=init, device=dev, seed=11)
+        assert isinstance(fs, list) and len(fs) == len(one) == W.dim()
+        for d, (a, b) in enumerate(zip(fs, one)):
+            assert a.dtype == torch.float32 and a.device == W.device and a.shape == (W.shape[d], R)
+            assert torch.equal(a, b)
+    assert init_factors_many([], [], init=init, device=dev, seed=11) == []
+    with pytest.raises(ValueError):
+        init_factors_many(Ws, ranks[:2], init=init, device=dev, seed=11)
+
+
+def test_parafac_epc_many_failing_layer_leaves_others_usable():
+    """One layer that cannot be decomposed (a 4-D tensor: gram_mttkrp_f64 raises ValueError)
+    makes parafac_epc_many raise that error, with the other layers' queued work joined into the
+    current stream; the next call on the valid layers gives the single calls' bits. No layer
+    here takes the blocked step."""
+    from admmq import parafac_epc as pe
+    g = torch.Generator().manual_seed(9)
+    Ys = [torch.randn(*s, generator=g, dtype=torch.float64).cuda() for s in ((12, 10, 9), (16, 8, 9), (9, 14, 10))]
+    ranks = [6, 20, 6]
+    bad = torch.randn(4, 5, 3, 2, generator=g, dtype=torch.float64).cuda()
+    with pytest.raises(ValueError, match="2-D or 3-D"):
+        pe.parafac_epc_many([Ys[0], Ys[1], bad, Ys[2]], [6, 20, 3, 6], **_MANY_KW)
+    many = pe.parafac_epc_many(Ys, ranks, **_MANY_KW)
+    for Y, R, got in zip(Ys, ranks, many):
+        _assert_same_cp(got, pe.parafac_epc(Y, R, **_MANY_KW))
+
+
 def test_parafac_epc_layer4_timing():
     """init_factors('parafac-epc')'s call (50 ALS + 50 EPC iterations per round, source/admm.py:40-44)
     on resnet18 layer4.0.conv2 (512, 512, 9), R = 1141 - the layer of the reference's published
