@@ -52,6 +52,13 @@ class QTensor(ctypes.Structure):
                 ("has_minmax", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class QMeta(ctypes.Structure):
+    """admmq_qmeta (include/admmq.h): the device record of one packed tensor, 32 bytes."""
+    _fields_ = [("scheme", ctypes.c_int32), ("bits", ctypes.c_int32), ("scale", ctypes.c_float),
+                ("zero_point", ctypes.c_int32), ("mn", ctypes.c_float), ("rng", ctypes.c_float),
+                ("index", ctypes.c_int32), ("bad", ctypes.c_int32)]
+
+
 class CpLayer(ctypes.Structure):
     _fields_ = [("W", ctypes.c_void_p), ("factors", ctypes.c_void_p * 3), ("G", ctypes.c_void_p),
                 ("F", ctypes.c_void_p), ("dims", ctypes.c_int32 * 3), ("ndim", ctypes.c_int32),
@@ -124,6 +131,10 @@ def load() -> ctypes.CDLL:
         "admmq_debug_set_thin_loop": (I32, [I32]),
         "admmq_quantize_workspace_size": (S, [P, I32, I32]),
         "admmq_quantize_batched": (I32, [P, I32, I32, I32, I32, P, S, P]),
+        "admmq_packed_bytes": (S, [I64, I32]),
+        "admmq_quantize_packed_workspace_size": (S, [P, I32, I32]),
+        "admmq_quantize_packed": (I32, [P, P, P, I32, I32, I32, I32, P, S, P]),
+        "admmq_dequantize_packed": (I32, [P, P, P, P, I32, P]),
         "admmq_mse_sse_table": (I32, [P, I64, I64, I32, I32, P, P, S, P]),
         "admmq_quantize_channel_workspace_size": (S, [P, I32, I32]),
         "admmq_quantize_channel": (I32, [P, P, P, I32, I32, I32, I32, P, S, P]),

@@ -11,7 +11,8 @@ device they were produced on (the reference round-trips them through ``.pt`` fil
 * 2-way CP of a 1x1 conv / linear ``W = A B^T`` becomes two 1x1 convs / linears.
 
 ``load_factors`` reads the files ``admmq.factorize.main`` writes, with the
-``scripts/calibrate.py:169-184`` naming (``weights_only=True``).
+``scripts/calibrate.py:169-184`` naming (``weights_only=True``); ``packed=True`` reads the
+packed integer codes of ``--save-packed`` and de-quantizes them on the device.
 """
 from __future__ import annotations
 
@@ -127,8 +128,14 @@ def factor_prefix(outdir_root: str, bits: int, qscheme: str, method: str, seed: 
                         f"{layer}_{method}_{init}_rank_{rank}_")
 
 
-def load_factors(prefix: str, ndim: int, device=None) -> List[torch.Tensor]:
-    """``mode_0.pt`` .. ``mode_{ndim-1}.pt`` under ``prefix`` (scripts/calibrate.py:174-181)."""
+def load_factors(prefix: str, ndim: int, device=None, packed: bool = False) -> List[torch.Tensor]:
+    """``mode_0.pt`` .. ``mode_{ndim-1}.pt`` under ``prefix`` (scripts/calibrate.py:174-181).
+    ``packed``: read ``mode_{m}_packed.pt`` (``admmq.factorize --save-packed``) instead and
+    return the de-quantized float32 factors on ``device`` (a ROCm GPU; default ``cuda:0``)."""
+    if packed:
+        from .packed import dequantize_packed, load_packed
+        dev = torch.device("cuda:0") if device is None else torch.device(device)
+        return dequantize_packed([load_packed(prefix + f"mode_{m}_packed.pt", device=dev) for m in range(ndim)])
     out = []
     for m in range(ndim):
         t = torch.load(prefix + f"mode_{m}.pt", map_location="cpu", weights_only=True)

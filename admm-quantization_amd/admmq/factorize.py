@@ -268,6 +268,9 @@ def parse_args(argv=None):
     ap.add_argument("--qscheme", type=str, required=True)
     ap.add_argument("--weights", type=str, default=None, help="state_dict file (weights_only load); default synthetic")
     ap.add_argument("--outdir-root", type=str, default=".")
+    ap.add_argument("--save-packed", action="store_true",
+                    help="also write <prefix>_mode_<n>_packed.pt: the quantized factors as packed integer codes "
+                         "with their scale / zero-point (admmq.packed; tensor_* schemes, bits <= 8)")
     args = ap.parse_args(argv)
     if args.rank is None and args.reduction_rate is None:
         raise ValueError('One of [--rank, --reduction-rate] arguments must be specified.')
@@ -314,6 +317,10 @@ def main(argv=None):
     print('Factorization took {} minutes'.format((time.time() - start) / 60))
     for mode, factor in enumerate(factors):
         torch.save(factor.cpu(), os.path.join(outdir, fileprefix + f'_mode_{mode}.pt'))
+    if args.save_packed:   # the packed form of quantize(factors[n]), i.e. of factors_q[n]
+        from .packed import quantize_packed, save_packed
+        for mode, p in enumerate(quantize_packed(factors, args.bits, args.qscheme)):
+            save_packed(os.path.join(outdir, fileprefix + f'_mode_{mode}_packed.pt'), p)
     error, qerror = rel_error_batched([(weight, factors), (weight, factors_q)])
     print('Factorization error is {} for usual and {} for quantized'.format(error, qerror))
     return factors, factors_q

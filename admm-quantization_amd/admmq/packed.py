@@ -1,0 +1,222 @@
+"""Packed integer codes of the tensor quantization schemes (DESIGN.md "Packed codes").
+
+``quantize_packed`` returns, for each tensor, the unsigned ``bits``-wide codes the
+quantizer chose - packed into a little-endian bit stream in the tensor's flat row-major
+order - together with the scale / zero-point / range that turn them back into exactly
+what ``quantize_tensor`` returns (equal under ``torch.equal``; an integer code has no
+``-0.0``). The codes come from the kernel that chose the grid (``k_qfinal_pack``), not from
+a second guess at the float32 result.
+
+Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
+``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
+"""
+from __future__ import annotations
+
+import ctypes
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib
+
+__all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes"]
+
+_NAMES = {v: k for k, v in _lib.SCHEMES.items()}
+FORMAT = "admmq.packed.v1"
+
+
+def packed_bytes(numel: int, bits: int) -> int:
+    """Length of the code stream: ``ceil(numel * bits / 8)`` bytes."""
+    return (int(numel) * int(bits) + 7) // 8
+
+
+def _validate(bits: int, qscheme: str) -> int:
+    if qscheme in _lib.CHANNEL_SCHEMES:
+        raise ValueError(f"{qscheme}: per-channel schemes have no packed form (their output is a broadcast, "
+                         "not the tensor's shape)")
+    if qscheme not in _lib.SCHEMES:
+        raise NotImplementedError(qscheme)
+    bits = int(bits)
+    if bits < 1 or bits > 8:
+        raise ValueError(f"packed codes need 1 <= bits <= 8, got {bits}")
+    if qscheme == "tensor_minmax" and bits == 1:
+        raise ValueError("tensor_minmax with 1 bit has three output values (sign(x) - 1): no 1-bit code")
+    return _lib.SCHEMES[qscheme]
+
+
+def _meta_words(p: "PackedTensor") -> torch.Tensor:
+    """The 8 int32 words of ``admmq_qmeta`` for ``p`` (bad = 0)."""
+    f = torch.tensor([p.scale, p.mn, p.rng], dtype=torch.float32).view(torch.int32)
+    return torch.tensor([_lib.SCHEMES[p.qscheme], p.bits, int(f[0]), p.zero_point, int(f[1]), int(f[2]), p.index, 0],
+                        dtype=torch.int32)
+
+
+@dataclass
+class PackedTensor:
+    """One quantized tensor as ``bits``-wide unsigned codes.
+
+    ``codes``: uint8 ``[ceil(numel * bits / 8)]``; element ``i`` of the flat row-major order
+    occupies bits ``[i * bits, (i + 1) * bits)`` of the little-endian bit stream.
+    ``scale`` / ``zero_point`` (mse-minmax, symmetric, affine) and ``mn`` / ``rng`` (minmax)
+    are float32 values held as Python floats (exact); ``index`` is the MSE search's chosen
+    candidate, else -1; ``bad`` counts the elements whose result has no valid code (NaN or
+    unrepresentable): a tensor with ``bad > 0`` is not a valid packed tensor."""
+    codes: torch.Tensor
+    shape: Tuple[int, ...]
+    bits: int
+    qscheme: str
+    scale: float
+    zero_point: int
+    mn: float
+    rng: float
+    index: int
+    bad: int = 0
+
+    @property
+    def numel(self) -> int:
+        n = 1
+        for s in self.shape:
+            n *= int(s)
+        return n
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.codes.numel())
+
+    def dequantize(self) -> torch.Tensor:
+        """float32 tensor of ``shape`` on the codes' device (``k_dequant_pack``)."""
+        return dequantize_packed([self])[0]
+
+    def levels(self) -> torch.Tensor:
+        """The unpacked codes, uint8 of ``shape``, on the codes' device (unpacked on the host)."""
+        import numpy as np
+        b = np.unpackbits(self.codes.detach().cpu().numpy(), bitorder="little")[:self.numel * self.bits]
+        w = (1 << np.arange(self.bits, dtype=np.uint16))
+        lv = (b.reshape(self.numel, self.bits).astype(np.uint16) * w).sum(axis=1).astype(np.uint8)
+        return torch.from_numpy(lv).reshape(self.shape).to(self.codes.device)
+
+
+def _from_meta(codes, shapes, meta: torch.Tensor, check: bool) -> List[PackedTensor]:
+    m = meta.cpu()   # the call's one host sync
+    fl = m.view(torch.float32)
+    out = []
+    for i, (c, shape) in enumerate(zip(codes, shapes)):
+        row = m[i].tolist()
+        if check and row[7] > 0:
+            raise ValueError(f"quantize_packed: tensor {i} has {row[7]} element(s) without a valid code "
+                             "(NaN or unrepresentable result; meta.bad > 0)")
+        out.append(PackedTensor(codes=c, shape=tuple(shape), bits=row[1], qscheme=_NAMES[row[0]], scale=float(fl[i, 2]),
+                                zero_point=row[3], mn=float(fl[i, 4]), rng=float(fl[i, 5]), index=row[6], bad=row[7]))
+    return out
+
+
+def quantize_packed_raw(tensors: Sequence[torch.Tensor], bits: int, qscheme: str, num_attempts: int = 200,
+                        tmin: Optional[float] = None, tmax: Optional[float] = None):
+    """``(codes, meta)`` on the device without a host sync: uint8 code streams and the int32
+    ``[n, 8]`` words of ``admmq_qmeta`` (word 7 = bad)."""
+    code = _validate(bits, qscheme)
+    xs = []
+    for t in tensors:
+        _lib.require_device(t)
+        if t.numel() == 0:
+            raise ValueError("quantize_packed: empty tensor")
+        xs.append(t.contiguous())
+    if not xs:
+        raise ValueError("quantize_packed: no tensors")
+    has_kw = code == 3 and tmin is not None and tmax is not None
+    if _lib.use_ops():   # torch.ops.admmq.quantize_packed (csrc/torch_ops.cpp) -> admmq_quantize_packed
+        codes, meta = _lib.ops().quantize_packed(xs, int(bits), code, int(num_attempts),
+                                                 float(tmin) if has_kw else None, float(tmax) if has_kw else None)
+        return list(codes), meta
+    lib = _lib.load()
+    dev = xs[0].device
+    items = []
+    for x in xs:
+        cols = 1 if x.dim() == 0 else x.shape[-1]
+        items.append(_lib.QTensor(x.data_ptr(), 0, x.numel() // cols, cols, float(tmin) if has_kw else 0.0,
+                                  float(tmax) if has_kw else 0.0, 1 if has_kw else 0, 0))
+    arr = _lib.qtensor_array(items)
+    codes = [torch.empty(packed_bytes(x.numel(), bits), dtype=torch.uint8, device=dev) for x in xs]
+    cptr = (ctypes.c_void_p * len(xs))(*[c.data_ptr() for c in codes])
+    meta = torch.empty((len(xs), 8), dtype=torch.int32, device=dev)
+    nb = lib.admmq_quantize_packed_workspace_size(arr, len(items), int(num_attempts))
+    if nb == 0:
+        _lib.check(-1, "quantize workspace planning")
+    ws = _lib.workspace(nb, dev)
+    rc = lib.admmq_quantize_packed(arr, cptr, _lib.ptr(meta), len(items), int(bits), code, int(num_attempts),
+                                   _lib.ptr(ws), nb, _lib.stream_handle(dev))
+    _lib.check(rc, "quantize_packed")
+    return codes, meta
+
+
+def quantize_packed(tensors: Sequence[torch.Tensor], bits: int, qscheme: str, num_attempts: int = 200,
+                    tmin: Optional[float] = None, tmax: Optional[float] = None,
+                    check: bool = True) -> List[PackedTensor]:
+    """Packed form of ``quantize_tensor(t, bits, qscheme, ...)`` for every ``t`` in ``tensors``:
+    one launch sequence, one host sync (the meta records). ``check``: raise ``ValueError``
+    naming the first tensor whose result has no valid code (``bad > 0``: NaN outputs, e.g. an
+    all-zero tensor under mse-minmax); with ``check=False`` the count is in ``.bad``."""
+    tensors = list(tensors)
+    codes, meta = quantize_packed_raw(tensors, bits, qscheme, num_attempts, tmin, tmax)
+    return _from_meta(codes, [t.shape for t in tensors], meta, check)
+
+
+def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
+    """float32 tensors of the packed tensors' shapes, one launch for the whole list."""
+    packed = list(packed)
+    if not packed:
+        return []
+    dev = packed[0].codes.device
+    if dev.type != "cuda":
+        raise RuntimeError("admmq: packed codes must live on a ROCm GPU to be de-quantized (device 'cuda'); "
+                           "load_packed(path, device=...) puts them there")
+    codes, numel = [], []
+    for p in packed:
+        _validate(p.bits, p.qscheme)
+        if p.codes.dtype != torch.uint8 or p.codes.numel() != packed_bytes(p.numel, p.bits) or p.numel == 0:
+            raise ValueError(f"packed tensor of shape {tuple(p.shape)} with {p.bits} bits needs "
+                             f"{packed_bytes(p.numel, p.bits)} uint8 code bytes")
+        if p.codes.device != dev:
+            raise RuntimeError("admmq: the packed tensors of one call must share a device")
+        codes.append(p.codes.contiguous())
+        numel.append(p.numel)
+    meta = torch.stack([_meta_words(p) for p in packed]).to(dev)
+    if _lib.use_ops():
+        ys = _lib.ops().dequantize_packed(codes, meta, numel)
+    else:
+        lib = _lib.load()
+        ys = [torch.empty(n, dtype=torch.float32, device=dev) for n in numel]
+        cptr = (ctypes.c_void_p * len(codes))(*[c.data_ptr() for c in codes])
+        yptr = (ctypes.c_void_p * len(ys))(*[y.data_ptr() for y in ys])
+        ne = (ctypes.c_int64 * len(numel))(*numel)
+        rc = lib.admmq_dequantize_packed(cptr, _lib.ptr(meta), yptr, ne, len(codes), _lib.stream_handle(dev))
+        _lib.check(rc, "dequantize_packed")
+    return [y.view(p.shape) for y, p in zip(ys, packed)]
+
+
+def save_packed(path: str, p) -> None:
+    """Write one ``PackedTensor`` (or a list of them) as a plain dict of tensors and Python
+    scalars; ``load_packed`` reads it back with ``weights_only=True``."""
+    many = not isinstance(p, PackedTensor)
+    items = [{"codes": q.codes.detach().cpu(), "shape": [int(s) for s in q.shape], "bits": int(q.bits),
+              "qscheme": q.qscheme, "scale": float(q.scale), "zero_point": int(q.zero_point), "mn": float(q.mn),
+              "rng": float(q.rng), "index": int(q.index)} for q in (p if many else [p])]
+    torch.save({"format": FORMAT, "many": many, "tensors": items}, path)
+
+
+def load_packed(path: str, device=None):
+    """The ``PackedTensor`` (or list) ``save_packed`` wrote, with its codes on ``device``."""
+    d = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(d, dict) or d.get("format") != FORMAT:
+        raise ValueError(f"{path}: not a packed-tensor file ({FORMAT})")
+    out = []
+    for it in d["tensors"]:
+        c = it["codes"]
+        if c.dtype != torch.uint8:
+            raise TypeError(f"{path}: codes must be uint8, got {c.dtype}")
+        out.append(PackedTensor(codes=c.to(device) if device is not None else c, shape=tuple(it["shape"]),
+                                bits=int(it["bits"]), qscheme=it["qscheme"], scale=float(it["scale"]),
+                                zero_point=int(it["zero_point"]), mn=float(it["mn"]), rng=float(it["rng"]),
+                                index=int(it["index"])))
+    return out if d["many"] else out[0]

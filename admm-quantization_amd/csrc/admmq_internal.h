@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct admmq_qmeta;   // include/admmq.h
+
 // Diagnostic per-block timelines / counters (admmq_debug_*_trace, tools/*_timeline.py):
 // compiled in only with `make TRACE=1`; the production library makes no trace stores.
 #ifndef ADMMQ_TRACE
@@ -104,6 +106,19 @@ struct QJob {
   int has_kw, copy;         // copy: Xp is the workspace copy (k_qpack writes it)
   unsigned* pstat;          // k_qpack's per-unit {absmax, min, max} partials (3 per unit)
   int pu0, pun;             // this job's units in the statistics launch: first, count
+};
+
+// De-quantization of packed codes (pack_kernels.hip): the jobs of one launch, passed by
+// value in the kernel arguments (the entry point has no workspace). Job k owns the blocks
+// [blk0[k], blk0[k + 1]) of kDqBlockElems flat elements each; its meta is meta[meta0 + k].
+constexpr int kDqJobs = 32;
+constexpr int kDqBlockElems = 4096;
+struct DqBatch {
+  const unsigned char* codes[kDqJobs];
+  float* y[kDqJobs];
+  long long numel[kDqJobs];
+  int blk0[kDqJobs + 1];
+  int njobs, meta0;
 };
 
 // Work-unit tables (built on the host, uploaded once per call)
@@ -280,6 +295,10 @@ void launch_channel_quant(const float* x, float* y, long long A, int C, long lon
                           unsigned* stats, int bits, int scheme, hipStream_t s);
 void launch_qfinal(const QJob* jobs, const Chunk* chunks, int nchunks, int ncand, int bits, int qscheme,
                    hipStream_t s);
+// packed codes: `chunks` are units of 1024 ng flat elements (ng = 1: k_qfinal's, 4: the search launch's)
+void launch_qfinal_pack(const QJob* jobs, const Chunk* chunks, int nchunks, int ng, unsigned char* const* codes,
+                        ::admmq_qmeta* meta, int ncand, int bits, int qscheme, hipStream_t s);
+void launch_dequant_pack(const DqBatch& b, int nblocks, const ::admmq_qmeta* meta, hipStream_t s);
 
 constexpr int kSseQuads = 512;      // quads per stage-2 / exhaustive SSE work unit (8 KiB LDS)
 constexpr int kHistElems = 4096;    // elements per stage-1 work unit x hist_nv (1024 x 4 legacy, 512 x 8 merged)
@@ -288,6 +307,7 @@ constexpr int kHistMultiMaxReps = 8;  // ... at most 8 units per block
 constexpr int kHistMaxUnits = 512;  // stage-1 units that fit in one round (2 per CU): above, 2x larger units
 constexpr int kElemChunk = 1024;    // elements per elementwise work unit (256 threads x float4)
 constexpr int kPackElems = 16384;   // elements per k_qpack unit (256 threads x 16 float4): few partials
+constexpr int kPackMinUnits = 1024;   // packed final pass: kHistElems units from this many of them, else kElemChunk
 constexpr int kFinElems = 4096;     // elements per ADMM finalize work unit when there are >= kFinMinUnits of them
 constexpr int kFinMinUnits = 256;   //   (else kElemChunk: small problem sets keep their parallelism)
 

@@ -391,9 +391,19 @@ __global__ void k_copy_sse(const QJob* jobs, int ncand, unsigned long long* out)
 }
 
 // exhaustive: evaluate every candidate's canonical SSE (debug table / forced mode)
+// pack (optional): the final pass emits packed codes (k_qfinal_pack) instead of k_qfinal
+struct PackOut {
+  unsigned char* const* host_codes;   // n device pointers (host array)
+  unsigned char** d_codes;            // their device copy (workspace)
+  admmq_qmeta* meta;                  // device, n entries
+};
 static int run_quant(QPlan& pl, int n, int bits, int qscheme, int ncand, hipStream_t s, bool final_pass,
-                     bool exhaustive) {
+                     bool exhaustive, const PackOut* pack = nullptr) {
   int rc;
+  if (pack) {
+    if ((rc = h2d(pack->d_codes, pack->host_codes, n * sizeof(unsigned char*), s))) return rc;
+    if (hipMemsetAsync(pack->meta, 0, n * sizeof(admmq_qmeta), s) != hipSuccess) return check_hip("quantize_packed");
+  }
   if ((rc = h2d(pl.d_jobs, pl.jobs.data(), n * sizeof(QJob), s))) return rc;
   if ((rc = h2d(pl.d_pack, pl.pack_chunks.data(), pl.pack_chunks.size() * sizeof(Chunk), s))) return rc;
   if ((rc = h2d(pl.d_stat, pl.stat_chunks.data(), pl.stat_chunks.size() * sizeof(Chunk), s))) return rc;
@@ -418,7 +428,16 @@ static int run_quant(QPlan& pl, int n, int bits, int qscheme, int ncand, hipStre
       launch_mse_sse(nullptr, pl.d_jobs, pl.d_sse, (int)pl.sse_chunks.size(), ncand, bits, 0, s);
     }
   }
-  if (final_pass) launch_qfinal(pl.d_jobs, pl.d_pack, (int)pl.pack_chunks.size(), ncand, bits, qscheme, s);
+  if (final_pass && pack) {
+    static_assert(kHistElems == 4 * kElemChunk, "k_qfinal_pack's unit sizes");
+    if ((int)pl.hist_chunks.size() >= kPackMinUnits)   // enough 4096-element units to fill the chip
+      launch_qfinal_pack(pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), 4, pack->d_codes, pack->meta, ncand, bits,
+                         qscheme, s);
+    else
+      launch_qfinal_pack(pl.d_jobs, pl.d_pack, (int)pl.pack_chunks.size(), 1, pack->d_codes, pack->meta, ncand, bits,
+                         qscheme, s);
+  } else if (final_pass)
+    launch_qfinal(pl.d_jobs, pl.d_pack, (int)pl.pack_chunks.size(), ncand, bits, qscheme, s);
   return check_hip("quantize");
 }
 
@@ -958,6 +977,74 @@ int32_t admmq_quantize_batched(const admmq_qtensor* t, int32_t n, int32_t bits, 
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, g_exhaustive.load());
+}
+
+size_t admmq_packed_bytes(int64_t numel, int32_t bits) {
+  if (numel <= 0 || bits < 1 || bits > 8 || numel > (int64_t(1) << 56)) return 0;
+  return (size_t)((numel * bits + 7) / 8);
+}
+
+// the quantize plan, then the device copy of the code pointers
+static size_t packed_codes_offset(const QPlan& pl) { return align_up(pl.bytes, 256); }
+
+size_t admmq_quantize_packed_workspace_size(const admmq_qtensor* t, int32_t n, int32_t num_attempts) {
+  QPlan pl;
+  if (plan_quant(t, n, num_attempts, nullptr, pl) != ADMMQ_OK) return 0;
+  return align_up(packed_codes_offset(pl) + (size_t)n * sizeof(unsigned char*), 256);
+}
+
+int32_t admmq_quantize_packed(const admmq_qtensor* t, uint8_t* const* codes, admmq_qmeta* meta_dev, int32_t n,
+                              int32_t bits, int32_t qscheme, int32_t num_attempts, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  if (!valid_scheme(qscheme)) return fail(ADMMQ_ERR_SCHEME, "quantize_packed: unknown qscheme (the four tensor schemes only)");
+  if (bits < 1 || bits > 8) return fail(ADMMQ_ERR_ARG, "quantize_packed: bits must be 1..8");
+  if (qscheme == kMinMax && bits == 1)
+    return fail(ADMMQ_ERR_ARG, "quantize_packed: tensor_minmax with 1 bit has three output values; no 1-bit code");
+  if (!codes || !meta_dev) return fail(ADMMQ_ERR_ARG, "quantize_packed: codes and meta must not be NULL");
+  QPlan pl;
+  int rc = plan_quant(t, n, num_attempts, workspace, pl);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i) {
+    if (!t[i].x) return fail(ADMMQ_ERR_ARG, "quantize_packed: null tensor");
+    if (!codes[i] || (reinterpret_cast<uintptr_t>(codes[i]) & 15) != 0)
+      return fail(ADMMQ_ERR_ARG, "quantize_packed: every codes[i] must be a 16-byte aligned device pointer");
+  }
+  const size_t off = packed_codes_offset(pl);
+  if (!workspace || workspace_bytes < align_up(off + (size_t)n * sizeof(unsigned char*), 256))
+    return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
+  PackOut po{codes, reinterpret_cast<unsigned char**>(static_cast<char*>(workspace) + off), meta_dev};
+  return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, g_exhaustive.load(), &po);
+}
+
+int32_t admmq_dequantize_packed(const uint8_t* const* codes, const admmq_qmeta* meta_dev, float* const* y,
+                                const int64_t* numel, int32_t n, void* stream) {
+  if (n <= 0 || !codes || !meta_dev || !y || !numel) return fail(ADMMQ_ERR_ARG, "dequantize_packed: null argument");
+  for (int i = 0; i < n; ++i) {
+    if (!codes[i] || !y[i]) return fail(ADMMQ_ERR_ARG, "dequantize_packed: null tensor");
+    if ((reinterpret_cast<uintptr_t>(codes[i]) & 15) != 0)
+      return fail(ADMMQ_ERR_ARG, "dequantize_packed: every codes[i] must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(y[i]) & 3) != 0) return fail(ADMMQ_ERR_ARG, "dequantize_packed: y[i] must be float aligned");
+    if (numel[i] <= 0 || numel[i] >= (int64_t(1) << 40)) return fail(ADMMQ_ERR_ARG, "dequantize_packed: numel out of range");
+  }
+  for (int i0 = 0; i0 < n;) {   // up to kDqJobs tensors and 2^30 blocks per launch
+    DqBatch b;
+    std::memset(&b, 0, sizeof(b));
+    b.meta0 = i0;
+    long long nblk = 0;
+    int k = 0;
+    for (; k < kDqJobs && i0 + k < n; ++k) {
+      const long long nb = (numel[i0 + k] + kDqBlockElems - 1) / kDqBlockElems;
+      if (k > 0 && nblk + nb > (1LL << 30)) break;
+      b.codes[k] = codes[i0 + k]; b.y[k] = y[i0 + k]; b.numel[k] = numel[i0 + k];
+      b.blk0[k] = (int)nblk;
+      nblk += nb;
+    }
+    b.blk0[k] = (int)nblk;
+    b.njobs = k;
+    launch_dequant_pack(b, (int)nblk, meta_dev, static_cast<hipStream_t>(stream));
+    i0 += k;
+  }
+  return check_hip("dequantize_packed");
 }
 
 int32_t admmq_mse_sse_table(const float* x, int64_t rows, int64_t cols, int32_t bits, int32_t num_attempts,

@@ -354,8 +354,9 @@ __device__ __forceinline__ unsigned wave_suffix_u32(unsigned v) {
 // Resolve the quantization parameters of a job inside a block (all threads call).
 // MSE: the select record gives c* directly (|S| = 1), or the canonical SSE of the
 // list / of every candidate decides (first index on ties, like torch.argmin).
+// idx_out (optional): receives c* of an MSE job whose search ran; otherwise left as it is.
 __device__ __forceinline__ QParams block_qparams(int scheme, int bits, const MseView& v, int slot, int ncand,
-                                                 int has_kw, float kw_min, float kw_max) {
+                                                 int has_kw, float kw_min, float kw_max, int* idx_out = nullptr) {
   __shared__ int s_idx;
   const unsigned* stat = v.stat + 4 * slot;
   const unsigned ab = stat[0];
@@ -392,6 +393,7 @@ __device__ __forceinline__ QParams block_qparams(int scheme, int bits, const Mse
       if (threadIdx.x == 0) s_idx = idx;
     }
     __syncthreads();
+    if (idx_out) *idx_out = s_idx;
     return qparams_mse(bits, cand_t(mx, s_idx, ncand));
   }
   return qparams_stats(scheme, bits, dec_ord(stat[1]), dec_ord(stat[2]), has_nan ? 1 : 0, has_kw, kw_min, kw_max);

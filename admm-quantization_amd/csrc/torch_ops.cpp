@@ -6,6 +6,8 @@
 // include/admmq.h on the current HIP stream. Reference interfaces mirrored:
 //   admmq::admm_iteration_batched  <- source/admm.py:51-67 admm_iteration (batched over problems)
 //   admmq::quantize_batched        <- source/quantization.py:69-144 quantize_tensor
+//   admmq::quantize_packed / dequantize_packed: the packed integer codes of the tensor schemes
+//                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -208,6 +210,91 @@ std::vector<at::Tensor> quantize_batched_meta(at::TensorList x, int64_t bits, in
   return ys;
 }
 
+// --- quantize_packed / dequantize_packed ------------------------------------------------------
+// codes[i]: uint8 [ceil(numel * bits / 8)]; meta: int32 [n, 8], the words of admmq_qmeta.
+std::tuple<std::vector<at::Tensor>, at::Tensor> quantize_packed_cuda(at::TensorList x, int64_t bits, int64_t qscheme,
+                                                                     int64_t num_attempts, std::optional<double> tmin,
+                                                                     std::optional<double> tmax) {
+  static_assert(sizeof(admmq_qmeta) == 32, "meta is int32 [n, 8]");
+  TORCH_CHECK(!x.empty(), "admmq: quantize_packed needs at least one tensor");
+  TORCH_CHECK(bits >= 1 && bits <= 8, "admmq: quantize_packed: bits must be 1..8");
+  check_f32_device(x[0], "tensor");
+  const c10::DeviceGuard guard(x[0].device());
+  const bool has_kw = qscheme == ADMMQ_TENSOR_AFFINE && tmin.has_value() && tmax.has_value();
+  std::vector<at::Tensor> xs, cs;
+  std::vector<admmq_qtensor> items(x.size());
+  std::vector<uint8_t*> cptr(x.size());
+  for (size_t i = 0; i < x.size(); ++i) {
+    check_f32_device(x[i], "tensor");
+    check_same_device(x[i], x[0], "tensor");
+    TORCH_CHECK(x[i].numel() > 0, "admmq: quantize_packed: empty tensor");
+    xs.push_back(x[i].contiguous());
+    cs.push_back(at::empty({static_cast<int64_t>(admmq_packed_bytes(xs.back().numel(), static_cast<int32_t>(bits)))},
+                           xs.back().options().dtype(at::kByte)));
+    cptr[i] = cs.back().data_ptr<uint8_t>();
+    const int64_t cols = xs.back().dim() == 0 ? 1 : xs.back().size(-1);
+    admmq_qtensor& t = items[i];
+    t.x = xs.back().data_ptr<float>(); t.y = nullptr;
+    t.rows = xs.back().numel() / cols; t.cols = cols;
+    t.tmin = has_kw ? static_cast<float>(*tmin) : 0.f; t.tmax = has_kw ? static_cast<float>(*tmax) : 0.f;
+    t.has_minmax = has_kw ? 1 : 0; t.reserved = 0;
+  }
+  const int32_t n = static_cast<int32_t>(items.size());
+  at::Tensor meta = at::empty({n, 8}, xs[0].options().dtype(at::kInt));
+  const size_t nb = admmq_quantize_packed_workspace_size(items.data(), n, static_cast<int32_t>(num_attempts));
+  TORCH_CHECK(nb != 0, "admmq: quantize workspace planning failed: ", admmq_last_error());
+  at::Tensor ws = workspace(nb, xs[0]);
+  check_rc(admmq_quantize_packed(items.data(), cptr.data(), reinterpret_cast<admmq_qmeta*>(meta.data_ptr<int32_t>()), n,
+                                 static_cast<int32_t>(bits), static_cast<int32_t>(qscheme),
+                                 static_cast<int32_t>(num_attempts), ws.data_ptr(), ws.numel(), stream_of(xs[0])),
+           "quantize_packed");
+  return {cs, meta};
+}
+
+std::tuple<std::vector<at::Tensor>, at::Tensor> quantize_packed_meta(at::TensorList x, int64_t bits, int64_t qscheme,
+                                                                     int64_t num_attempts, std::optional<double> tmin,
+                                                                     std::optional<double> tmax) {
+  TORCH_CHECK(bits >= 1 && bits <= 8, "admmq: quantize_packed: bits must be 1..8");
+  std::vector<at::Tensor> cs;
+  for (const at::Tensor& t : x) cs.push_back(at::empty({(t.numel() * bits + 7) / 8}, t.options().dtype(at::kByte)));
+  return {cs, at::empty({static_cast<int64_t>(x.size()), 8}, x[0].options().dtype(at::kInt))};
+}
+
+std::vector<at::Tensor> dequantize_packed_cuda(at::TensorList codes, const at::Tensor& meta, at::IntArrayRef numel) {
+  const size_t n = codes.size();
+  TORCH_CHECK(n > 0, "admmq: dequantize_packed needs at least one tensor");
+  TORCH_CHECK(numel.size() == n, "admmq: dequantize_packed: codes and numel differ in length");
+  TORCH_CHECK(meta.is_cuda() && meta.scalar_type() == at::kInt && meta.dim() == 2 &&
+                  meta.size(0) == static_cast<int64_t>(n) && meta.size(1) == 8,
+              "admmq: dequantize_packed: meta must be a device int32 [n, 8] tensor");
+  const c10::DeviceGuard guard(meta.device());
+  const at::Tensor mc = meta.contiguous();
+  std::vector<at::Tensor> cc, ys;
+  std::vector<const uint8_t*> cptr(n);
+  std::vector<float*> yptr(n);
+  std::vector<int64_t> ne(numel.begin(), numel.end());
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(codes[i].is_cuda() && codes[i].scalar_type() == at::kByte, "admmq: codes must be uint8 tensors on the GPU");
+    check_same_device(codes[i], meta, "codes");
+    TORCH_CHECK(ne[i] > 0, "admmq: dequantize_packed: numel must be positive");
+    // (the byte count for any bits <= 8 is at most numel; the kernel reads ceil(numel * bits / 8) <= codes.numel())
+    cc.push_back(codes[i].contiguous());
+    cptr[i] = cc.back().data_ptr<uint8_t>();
+    ys.push_back(at::empty({ne[i]}, mc.options().dtype(at::kFloat)));
+    yptr[i] = ys.back().data_ptr<float>();
+  }
+  check_rc(admmq_dequantize_packed(cptr.data(), reinterpret_cast<const admmq_qmeta*>(mc.data_ptr<int32_t>()),
+                                   yptr.data(), ne.data(), static_cast<int32_t>(n), stream_of(mc)),
+           "dequantize_packed");
+  return ys;
+}
+
+std::vector<at::Tensor> dequantize_packed_meta(at::TensorList codes, const at::Tensor& meta, at::IntArrayRef numel) {
+  std::vector<at::Tensor> ys;
+  for (const int64_t ne : numel) ys.push_back(at::empty({ne}, meta.options().dtype(at::kFloat)));
+  return ys;
+}
+
 // --- quantize_channel (channel_symmetric / channel_affine with an explicit dim) ----------------
 at::Tensor quantize_channel_cuda(const at::Tensor& x, int64_t bits, int64_t qscheme, int64_t dim) {
   check_f32_device(x, "tensor");
@@ -346,6 +433,9 @@ TORCH_LIBRARY(admmq, m) {
         "-> (Tensor[] H_out, Tensor info, Tensor[] HT, Tensor[] X)");
   m.def("quantize_batched(Tensor[] x, int bits, int qscheme, int num_attempts=200, float? tmin=None, "
         "float? tmax=None) -> Tensor[]");
+  m.def("quantize_packed(Tensor[] x, int bits, int qscheme, int num_attempts=200, float? tmin=None, "
+        "float? tmax=None) -> (Tensor[] codes, Tensor meta)");
+  m.def("dequantize_packed(Tensor[] codes, Tensor meta, int[] numel) -> Tensor[]");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -355,6 +445,8 @@ TORCH_LIBRARY(admmq, m) {
 TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("admm_iteration_batched", &admm_batched_cuda);
   m.impl("quantize_batched", &quantize_batched_cuda);
+  m.impl("quantize_packed", &quantize_packed_cuda);
+  m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -363,6 +455,8 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
 TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("admm_iteration_batched", &admm_batched_meta);
   m.impl("quantize_batched", &quantize_batched_meta);
+  m.impl("quantize_packed", &quantize_packed_meta);
+  m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

@@ -145,6 +145,47 @@ size_t admmq_quantize_workspace_size(const admmq_qtensor* t, int32_t n, int32_t 
 int32_t admmq_quantize_batched(const admmq_qtensor* t, int32_t n, int32_t bits, int32_t qscheme, int32_t num_attempts,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Packed integer codes of the four tensor schemes (DESIGN.md "Packed codes"). Every element
+ * gets an unsigned code u in [0, 2^bits), bits 1..8, with q = 2^(bits-1), n = 2^bits - 1:
+ *   mse-minmax / symmetric  u = clamp(rint(x/scale), -q, q-1) + q       y = (float)(u - q) * scale
+ *   affine                  u = clamp(rint(x/scale) + zp, -q, q-1) + q  y = (float)((u - q) - zp) * scale
+ *   minmax (bits >= 2)      u = floor(((x - mn)/rng) * n + 0.5)         y = ((float)u * rng) / n + mn
+ * (float32 operations in this order, no fused multiply-add). Element i of the tensor's flat
+ * row-major order occupies bits [i*bits, (i+1)*bits) of a little-endian bit stream: byte
+ * (i*bits) >> 3 from bit (i*bits) & 7, least significant bit first; no row padding; the
+ * stream is admmq_packed_bytes(numel, bits) = ceil(numel*bits/8) bytes and the spare high
+ * bits of its last byte are 0. De-quantizing the codes gives admmq_quantize_batched's output
+ * (equal under IEEE comparison; an integer code has no -0). `bad` counts the elements for
+ * which it does not (every NaN result among them; such a code is stored as 0): a tensor
+ * whose bad > 0 has no valid packed form. */
+typedef struct admmq_qmeta { /* 32 bytes, written on the device */
+  int32_t scheme, bits;
+  float scale;        /* mse / symmetric / affine */
+  int32_t zero_point; /* affine, else 0 */
+  float mn, rng;      /* minmax, else 0 */
+  int32_t index;      /* mse: chosen candidate (first-index argmin), else -1 */
+  int32_t bad;
+} admmq_qmeta;
+
+size_t admmq_packed_bytes(int64_t numel, int32_t bits); /* 0 on bad arguments */
+
+/* t, codes: host arrays of n entries; codes[i] (device, 16-byte aligned, admmq_packed_bytes
+ * bytes) and meta_dev (device, n entries) receive the result. t[i].y may be NULL (codes
+ * only); when it is not, the same launch also writes admmq_quantize_batched's float32
+ * output there. ADMMQ_ERR_ARG for bits outside 1..8 and for tensor_minmax with bits == 1
+ * (its outputs take three values). The workspace is admmq_quantize_workspace_size's plus
+ * the table of code pointers. */
+size_t admmq_quantize_packed_workspace_size(const admmq_qtensor* t, int32_t n, int32_t num_attempts);
+int32_t admmq_quantize_packed(const admmq_qtensor* t, uint8_t* const* codes, admmq_qmeta* meta_dev, int32_t n,
+                              int32_t bits, int32_t qscheme, int32_t num_attempts, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* The inverse: y[i] (device, numel[i] floats) from codes[i] (device, 16-byte aligned,
+ * admmq_packed_bytes(numel[i], meta_dev[i].bits) bytes: nothing past them is read) and
+ * meta_dev[i]. codes, y and numel are host arrays. Needs no workspace: the job table travels
+ * in the kernel arguments, 32 tensors per launch. */
+int32_t admmq_dequantize_packed(const uint8_t* const* codes, const admmq_qmeta* meta_dev, float* const* y,
+                                const int64_t* numel, int32_t n, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast
