@@ -13,6 +13,11 @@ device they were produced on (the reference round-trips them through ``.pt`` fil
 ``load_factors`` reads the files ``admmq.factorize.main`` writes, with the
 ``scripts/calibrate.py:169-184`` naming (``weights_only=True``); ``packed=True`` reads the
 packed integer codes of ``--save-packed`` and de-quantizes them on the device.
+
+Packed layers: ``load_packed_factors`` returns the ``PackedTensor`` factors themselves, and
+the CP builders accept them in place of float tensors: the 1x1 convs / linears then become
+``PackedConv1x1`` / ``PackedLinear``, which keep the codes and run ``k_packed_gemm`` on them
+(inference only); no float32 copy of such a factor is ever made.
 """
 from __future__ import annotations
 
@@ -22,6 +27,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
+
+from .packed import PackedTensor, _meta_words, _weight_dims, load_packed, packed_bytes, packed_gemm
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -33,9 +40,148 @@ def _expect(module_w: torch.Tensor, t: torch.Tensor):
         raise AssertionError(f'Expected shape: {tuple(module_w.shape)}, but got {tuple(t.shape)}')
 
 
+def _expect_shape(expected, got):
+    if tuple(expected) != tuple(got):
+        raise AssertionError(f'Expected shape: {tuple(expected)}, but got {tuple(got)}')
+
+
+def _is_packed(factors) -> bool:
+    return bool(factors) and all(isinstance(f, PackedTensor) for f in factors)
+
+
+class _PackedWeight(nn.Module):
+    """A weight ``[out, in]`` kept as the packed codes of ``p`` (``transpose``: ``p`` holds its
+    transpose ``[in, out]``). ``codes`` is a uint8 buffer; the scale / zero-point / shape travel
+    in the extra state; ``bias`` is an optional parameter (``requires_grad=False``: the layer is
+    inference only). There is no ``weight`` attribute: ``dequantize()`` returns the float32
+    weight for callers that want the library GEMM instead."""
+    _layout = 1
+
+    def __init__(self, p: PackedTensor, bias: Optional[torch.Tensor] = None, transpose: bool = False):
+        super().__init__()
+        self.transpose = bool(transpose)
+        self.out_features, self.in_features = _weight_dims(p, self.transpose)
+        self.register_buffer("codes", p.codes.detach().clone().contiguous())
+        self._set_quant(p)
+        if bias is not None:
+            _expect_shape((self.out_features,), bias.shape)
+            self.bias = nn.Parameter(bias.detach().clone().to(self.codes.device).contiguous(), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    def _set_quant(self, p):
+        self._q = dict(shape=[int(s) for s in p.shape], bits=int(p.bits), qscheme=str(p.qscheme), scale=float(p.scale),
+                       zero_point=int(p.zero_point), mn=float(p.mn), rng=float(p.rng), index=int(p.index))
+        self._meta = _meta_words(self.packed())
+
+    def packed(self) -> PackedTensor:
+        """The layer's weight as a ``PackedTensor`` sharing the ``codes`` buffer."""
+        q = self._q
+        return PackedTensor(codes=self.codes, shape=tuple(q["shape"]), bits=q["bits"], qscheme=q["qscheme"],
+                            scale=q["scale"], zero_point=q["zero_point"], mn=q["mn"], rng=q["rng"], index=q["index"])
+
+    def dequantize(self) -> torch.Tensor:
+        """The float32 weight ``[out, in]`` (a new tensor; the layer does not keep it)."""
+        w = self.packed().dequantize()
+        return w.T.contiguous() if self.transpose else w
+
+    def get_extra_state(self):
+        return dict(self._q, transpose=self.transpose)
+
+    def set_extra_state(self, state):
+        q = {k: state[k] for k in ("shape", "bits", "qscheme", "scale", "zero_point", "mn", "rng", "index")}
+        if bool(state["transpose"]) != self.transpose or [int(s) for s in q["shape"]] != self._q["shape"] or \
+                packed_bytes(self.in_features * self.out_features, int(q["bits"])) != self.codes.numel():
+            raise ValueError(f"packed state of shape {tuple(q['shape'])}, {q['bits']} bits, transpose={state['transpose']} "
+                             f"does not fit this layer ({tuple(self._q['shape'])}, {self._q['bits']} bits, "
+                             f"transpose={self.transpose})")
+        self._set_quant(PackedTensor(codes=self.codes, shape=tuple(q["shape"]), bits=int(q["bits"]), qscheme=q["qscheme"],
+                                     scale=float(q["scale"]), zero_point=int(q["zero_point"]), mn=float(q["mn"]),
+                                     rng=float(q["rng"]), index=int(q["index"])))
+
+    def _gemm(self, x):
+        return packed_gemm(self.codes, self._meta, self.transpose, self.out_features, self.in_features, x, self._layout,
+                           self.bias)
+
+    def extra_repr(self):
+        return (f"{self.in_features}, {self.out_features}, bits={self._q['bits']}, qscheme={self._q['qscheme']}, "
+                f"transpose={self.transpose}, bias={self.bias is not None}")
+
+
+class PackedLinear(_PackedWeight):
+    """``nn.Linear`` on packed codes: ``x [..., in] -> [..., out]``."""
+    _layout = 1
+
+    def forward(self, x):
+        return self._gemm(x)
+
+
+class PackedConv1x1(_PackedWeight):
+    """A 1x1 ``nn.Conv2d`` on packed codes: ``x [n, in, H, W] -> [n, out, H', W']``. Zero
+    padding and stride act on ``x`` before the product (a 1x1 kernel commutes with both)."""
+    _layout = 0
+
+    def __init__(self, p: PackedTensor, bias: Optional[torch.Tensor] = None, transpose: bool = False, stride=1,
+                 padding=0):
+        super().__init__(p, bias, transpose)
+        self.stride = (stride, stride) if isinstance(stride, int) else tuple(stride)
+        self.padding = (padding, padding) if isinstance(padding, int) else tuple(padding)
+
+    def forward(self, x):
+        if self.padding != (0, 0):
+            x = nn.functional.pad(x, (self.padding[1], self.padding[1], self.padding[0], self.padding[0]))
+        if self.stride != (1, 1):
+            x = x[:, :, ::self.stride[0], ::self.stride[1]]
+        return self._gemm(x)
+
+
+def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups):
+    if groups != 1:
+        raise NotImplementedError("packed CP layers support groups=1 only")
+    A, B, C = factors
+    _expect_shape((rank, cin, 1, 1), (B.shape[1], B.shape[0], 1, 1))
+    _expect_shape((kernel_size[0] * kernel_size[1], rank), tuple(C.shape))
+    _expect_shape((cout, rank, 1, 1), (A.shape[0], A.shape[1], 1, 1))
+    dev = C.codes.device
+    conv2 = nn.Conv2d(rank, rank, kernel_size=kernel_size, groups=rank, padding=padding, stride=stride, bias=False,
+                      device=dev)
+    # k k R floats: nothing to save by keeping the depthwise stage packed; frozen like the
+    # packed stages (they refuse an input that requires grad)
+    conv2.weight = nn.Parameter(C.dequantize().reshape(*kernel_size, rank).permute(2, 0, 1)[:, None].contiguous(),
+                                requires_grad=False)
+    return nn.Sequential(OrderedDict([
+        ('conv1', PackedConv1x1(B, None, transpose=True)),
+        ('conv2', conv2),
+        ('conv3', PackedConv1x1(A, bias, transpose=False)),
+    ]))
+
+
+def _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride):
+    A, B = factors
+    _expect_shape((rank, cin, 1, 1), (B.shape[1], B.shape[0], 1, 1))
+    _expect_shape((cout, rank, 1, 1), (A.shape[0], A.shape[1], 1, 1))
+    return nn.Sequential(OrderedDict([
+        ('conv1', PackedConv1x1(B, None, transpose=True, stride=stride, padding=padding)),
+        ('conv2', PackedConv1x1(A, bias, transpose=False)),
+    ]))
+
+
+def _packed_cpfc_layer(rank, factors, bias, fin, fout):
+    B, A = factors
+    _expect_shape((rank, fin), (A.shape[1], A.shape[0]))
+    _expect_shape((fout, rank), tuple(B.shape))
+    return nn.Sequential(OrderedDict([
+        ('fc1', PackedLinear(A, None, transpose=True)),
+        ('fc2', PackedLinear(B, bias, transpose=False)),
+    ]))
+
+
 def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
                    cout: int, kernel_size: Tuple[int, int], padding, stride, groups: int = 1) -> nn.Sequential:
-    """1x1 (cin -> R) -> depthwise kernel_size (R) -> 1x1 (R -> cout); source/models.py:24-51."""
+    """1x1 (cin -> R) -> depthwise kernel_size (R) -> 1x1 (R -> cout); source/models.py:24-51.
+    ``PackedTensor`` factors: conv1 / conv3 become ``PackedConv1x1`` (B transposed, A)."""
+    if _is_packed(factors):
+        return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups)
     dev = factors[0].device if factors else None
     seq = nn.Sequential(OrderedDict([
         ('conv1', nn.Conv2d(cin, rank, kernel_size=(1, 1), groups=groups, bias=False, device=dev)),
@@ -63,7 +209,10 @@ def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: O
 
 def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
                         cout: int, padding, stride) -> nn.Sequential:
-    """1x1 (cin -> R, with the original padding/stride) -> 1x1 (R -> cout); source/models.py:54-77."""
+    """1x1 (cin -> R, with the original padding/stride) -> 1x1 (R -> cout); source/models.py:54-77.
+    ``PackedTensor`` factors: both stages become ``PackedConv1x1`` (B transposed, A)."""
+    if _is_packed(factors):
+        return _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride)
     dev = factors[0].device if factors else None
     seq = nn.Sequential(OrderedDict([
         ('conv1', nn.Conv2d(cin, rank, kernel_size=(1, 1), padding=padding, stride=stride, bias=False, device=dev)),
@@ -86,7 +235,10 @@ def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bi
 
 def build_cpfc_layer(rank: int, factors: Sequence[torch.Tensor], bias: Optional[torch.Tensor], fin: int,
                      fout: int) -> nn.Sequential:
-    """Linear fin -> R (A^T) -> Linear R -> fout (B); source/models.py:80-99 (factors = [B, A])."""
+    """Linear fin -> R (A^T) -> Linear R -> fout (B); source/models.py:80-99 (factors = [B, A]).
+    ``PackedTensor`` factors: both stages become ``PackedLinear`` (A transposed, B)."""
+    if _is_packed(factors):
+        return _packed_cpfc_layer(rank, factors, bias, fin, fout)
     B, A = factors
     seq = nn.Sequential(OrderedDict([
         ('fc1', nn.Linear(fin, rank, bias=False, device=A.device)),
@@ -143,6 +295,14 @@ def load_factors(prefix: str, ndim: int, device=None, packed: bool = False) -> L
             raise TypeError(f"{prefix}mode_{m}.pt: expected float32 factors, got {t.dtype}")
         out.append(t.to(device) if device is not None else t)
     return out
+
+
+def load_packed_factors(prefix: str, ndim: int, device=None) -> List[PackedTensor]:
+    """The ``PackedTensor`` factors of ``mode_0_packed.pt`` .. ``mode_{ndim-1}_packed.pt`` under
+    ``prefix`` (``admmq.factorize --save-packed``), codes on ``device`` (default ``cuda:0``): the
+    builders above turn them into packed layers without de-quantizing the large factors."""
+    dev = torch.device("cuda:0") if device is None else torch.device(device)
+    return [load_packed(prefix + f"mode_{m}_packed.pt", device=dev) for m in range(ndim)]
 
 
 def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor]) -> nn.Sequential:

@@ -7,6 +7,9 @@ what ``quantize_tensor`` returns (equal under ``torch.equal``; an integer code h
 ``-0.0``). The codes come from the kernel that chose the grid (``k_qfinal_pack``), not from
 a second guess at the float32 result.
 
+``packed_linear`` / ``packed_conv1x1`` multiply activations by a weight kept as such codes
+(``k_packed_gemm``: the codes are decoded inside the GEMM, the float32 weight never exists).
+
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
 """
@@ -20,7 +23,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes"]
+__all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
+           "packed_gemm", "packed_linear", "packed_conv1x1"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -46,10 +50,16 @@ def _validate(bits: int, qscheme: str) -> int:
 
 
 def _meta_words(p: "PackedTensor") -> torch.Tensor:
-    """The 8 int32 words of ``admmq_qmeta`` for ``p`` (bad = 0)."""
+    """The 8 int32 words of ``admmq_qmeta`` for ``p`` (bad = 0), on the CPU; kept on ``p`` while
+    its fields are unchanged (a packed layer asks for them at every forward)."""
+    key = (p.qscheme, p.bits, p.scale, p.zero_point, p.mn, p.rng, p.index)
+    if getattr(p, "_mw_key", None) == key:
+        return p._mw
     f = torch.tensor([p.scale, p.mn, p.rng], dtype=torch.float32).view(torch.int32)
-    return torch.tensor([_lib.SCHEMES[p.qscheme], p.bits, int(f[0]), p.zero_point, int(f[1]), int(f[2]), p.index, 0],
-                        dtype=torch.int32)
+    p._mw = torch.tensor([_lib.SCHEMES[p.qscheme], p.bits, int(f[0]), p.zero_point, int(f[1]), int(f[2]), p.index, 0],
+                         dtype=torch.int32)
+    p._mw_key = key
+    return p._mw
 
 
 @dataclass
@@ -193,6 +203,95 @@ def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
         rc = lib.admmq_dequantize_packed(cptr, _lib.ptr(meta), yptr, ne, len(codes), _lib.stream_handle(dev))
         _lib.check(rc, "dequantize_packed")
     return [y.view(p.shape) for y, p in zip(ys, packed)]
+
+
+def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int, x: torch.Tensor,
+                x_layout: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Y = W X (+ bias)`` with ``W`` the ``[M, K]`` de-quantization of ``codes`` (``transpose``: of the
+    ``[K, M]`` packed tensor's transpose). ``meta_words``: the 8 int32 words of the meta record on
+    the CPU. ``x_layout`` 0: ``x [n, K, ...] -> [n, M, ...]``; 1: ``x [..., K] -> [..., M]``.
+    Inference only: an ``x`` that requires grad is refused while grad mode is on."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda":
+        raise RuntimeError("admmq: packed_gemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
+                           "the MI355X path has no CPU implementation")
+    _lib.require_device(x)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
+                           "under torch.no_grad() or detach x")
+    M, K, x_layout = int(M), int(K), int(x_layout)
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_gemm (csrc/torch_ops.cpp) -> admmq_packed_gemm
+        return _lib.ops().packed_gemm(codes, meta_words, bool(transpose), M, K, x, x_layout, bias)
+    lib = _lib.load()
+    if x_layout == 0:
+        if x.dim() < 3 or x.shape[1] != K:
+            raise ValueError(f"packed_gemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
+        oshape = (x.shape[0], M) + tuple(x.shape[2:])
+        nb = int(x.shape[0])
+    elif x_layout == 1:
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError(f"packed_gemm: x must be [..., {K}], got {tuple(x.shape)}")
+        oshape = tuple(x.shape[:-1]) + (M,)
+        nb = 1
+    else:
+        raise ValueError("packed_gemm: x_layout must be 0 or 1")
+    xc = x.contiguous()
+    if xc.numel() == 0:
+        raise ValueError("packed_gemm: empty x")
+    N = xc.numel() // (nb * K)
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    bc = None
+    if bias is not None:
+        _lib.require_device(bias)
+        if tuple(bias.shape) != (M,):
+            raise ValueError(f"packed_gemm: bias must be [{M}], got {tuple(bias.shape)}")
+        bc = bias.contiguous()
+    y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+    nbytes = lib.admmq_packed_gemm_workspace_size(M, K, N, nb)
+    ws = _lib.workspace(nbytes, x.device)
+    rc = lib.admmq_packed_gemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc), x_layout, N,
+                               nb, _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_gemm")
+    return y
+
+
+def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
+    _validate(p.bits, p.qscheme)
+    if len(p.shape) != 2:
+        raise ValueError(f"a packed weight must be 2-D, got shape {tuple(p.shape)}")
+    if p.bad:
+        raise ValueError(f"packed tensor has {p.bad} element(s) without a valid code (bad > 0)")
+    if p.codes.dtype != torch.uint8 or p.codes.numel() != packed_bytes(p.numel, p.bits) or p.numel == 0:
+        raise ValueError(f"packed tensor of shape {tuple(p.shape)} with {p.bits} bits needs "
+                         f"{packed_bytes(p.numel, p.bits)} uint8 code bytes")
+    r, c = int(p.shape[0]), int(p.shape[1])
+    return (c, r) if transpose else (r, c)
+
+
+def packed_linear(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
+                  transpose: bool = False) -> torch.Tensor:
+    """``F.linear(x, W, bias)`` with ``W = p.dequantize()`` (``transpose``: its transpose) computed
+    from the codes: ``x [..., K] -> [..., M]``. Inference only."""
+    M, K = _weight_dims(p, transpose)
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias)
+
+
+def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None, transpose: bool = False,
+                   stride=1) -> torch.Tensor:
+    """``F.conv2d(x, W[:, :, None, None], bias, stride=stride)`` with ``W = p.dequantize()``
+    (``transpose``: its transpose) computed from the codes: ``x [n, K, H, W] -> [n, M, H', W']``.
+    The stride sub-samples ``x`` (a 1x1 kernel without padding commutes with it). Inference only."""
+    M, K = _weight_dims(p, transpose)
+    if isinstance(x, torch.Tensor) and x.dim() != 4:
+        raise ValueError(f"packed_conv1x1: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    sh, sw = (stride, stride) if isinstance(stride, int) else tuple(stride)
+    if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
+        x = x[:, :, ::sh, ::sw]
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias)
 
 
 def save_packed(path: str, p) -> None:

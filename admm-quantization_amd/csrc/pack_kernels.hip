@@ -6,15 +6,6 @@
 
 namespace admmq {
 
-// The table's de-quantization of code u: float32 operations in this order (-ffp-contract=off).
-__device__ __forceinline__ float dequant_code(unsigned u, int scheme, int bits, float scale, int zp, float mn,
-                                              float rng) {
-  const int q = 1 << (bits - 1);
-  if (scheme == kMinMax) return ((float)u * rng) / (float)((1 << bits) - 1) + mn;
-  if (scheme == kAffine) return (float)(((int)u - q) - zp) * scale;
-  return (float)((int)u - q) * scale;
-}
-
 // apply_quant's result y for x (the same quotient, rounding and clamp, operation for
 // operation) together with the code of the level it chose; 0 where no code can be formed.
 __device__ __forceinline__ float quant_code(float x, const QParams& p, unsigned& u, bool& formed) {
@@ -188,16 +179,6 @@ __global__ __launch_bounds__(256) void k_qfinal_pack(const QJob* __restrict__ jo
       }
     }
   }
-}
-
-// Dword w of a code stream of nbytes bytes; the stream's last, partial dword byte by byte
-// (nothing past the stream is read).
-__device__ __forceinline__ unsigned code_dword(const unsigned char* __restrict__ c, long long w, long long nbytes) {
-  if (4 * w + 4 <= nbytes) return *reinterpret_cast<const unsigned*>(c + 4 * w);
-  unsigned v = 0u;
-  for (int b = 0; b < 4; ++b)
-    if (4 * w + b < nbytes) v |= (unsigned)c[4 * w + b] << (8 * b);
-  return v;
 }
 
 // Block = kDqBlockElems flat elements of one tensor; a thread takes the float4 groups

@@ -1,0 +1,350 @@
+// GEMM on a weight kept as packed integer codes (include/admmq.h "Packed-weight GEMM",
+// DESIGN.md 2.22): Y = W X (+ bias) with W = D or D^T, D the table de-quantization of a
+// packed tensor's codes (dequant_code, quant_device.h), decoded tile by tile into LDS and
+// multiplied on the fp32 MFMA - the float32 weight never exists in memory.
+//
+// The batch and the positions form one column axis c in [0, C), C = nb N:
+//   x_layout 0 (NCHW 1x1 conv): c = b N + n, X[(b K + k) N + n], Y[(b M + m) N + n]
+//   x_layout 1 (linear, nb = 1): c = token,  X[c K + k],         Y[c M + m]
+// A workgroup (256 threads, 4 waves of 32 x 32) owns a 64 (m) x 64 (c) tile and steps
+// through K in 32s: the W block of a step is decoded from the bit stream (a thread takes a
+// run of 8 consecutive codes of the stream: along k for trans_w = 0, along m for 1; a run
+// starts at any bit, so it is cut out of three dwords) into a k-major LDS image, the X
+// block is copied beside it, and each wave issues 16 v_mfma_f32_32x32x2_f32. x_layout 1
+// swaps the MFMA operands so that the lanes of the result run along m, Y's contiguous axis.
+//
+// K is cut into pieces of kp = max(64, 32 ceil(K / 1024)) (a function of K alone; at most
+// 32 pieces). Every piece is summed in its own accumulator chain from zero, and an output is
+// ((p0 + p1) + p2) + ... (+ bias) in piece order. Two forms give those same bits: serial (one
+// workgroup runs all pieces of its tile and folds the accumulator at each piece end) and
+// parallel (one workgroup per piece writes its partial image to the workspace, and
+// k_packed_reduce adds the images in piece order). The planner takes the parallel form when
+// the serial one would start fewer than kPgParallelBelow workgroups (the weight-streaming
+// regime: few columns, the work is reading the code stream). No workgroup waits for
+// another, and nothing is combined with atomics.
+#include <algorithm>
+#include <type_traits>
+
+#include "../../include/admmq.h"
+#include "quant_device.h"
+
+namespace admmq {
+
+constexpr int kPgBM = 64, kPgBN = 64, kPgBK = 32;
+constexpr int kPgLD = 65;               // LDS row stride: the k-major fragment reads and both store patterns spread over the banks
+constexpr int kPgPieceMin = 64;         // K per piece at least
+constexpr int kPgPiecesMax = 32;        // pieces at most
+constexpr int kPgParallelBelow = 256;   // tiles below which the pieces run in parallel (one workgroup per CU at least)
+
+typedef float pg_f32x16 __attribute__((ext_vector_type(16)));
+typedef __attribute__((address_space(1))) const unsigned gcu32;   // (gcf32: admmq_internal.h)
+
+struct PgArgs {
+  const unsigned char* codes;
+  const float* x;
+  const float* bias;
+  float* y;
+  float* part;        // parallel form: [np][total] partial images in Y's layout
+  long long nbytes;   // bytes of the code stream
+  long long total;    // C * M
+  long long C;
+  int M, K, N;
+  int xl;
+  int kp, np, parallel;
+  int scheme, zp;
+  float scale, mn, rng;
+};
+
+// C/D map of v_mfma_f32_32x32x2_f32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#define PG_ROW(r) (((r) & 3) + 8 * ((r) >> 2) + 4 * h)
+
+// The per-step addresses are hoisted: a run's bit offset in its first dword is the same in
+// every step (a step advances the stream by 32 (x M) BITS bits: whole dwords), so the thread
+// keeps one dword index and adds a constant; X is read through one pointer plus 8 fixed
+// offsets. FULL steps (all 32 k inside the piece) load without k tests; columns past C read
+// a clamped (valid) address and are zeroed by a select, not a branch.
+template <int BITS, bool TRANS, bool XL>
+__global__ __launch_bounds__(256) void k_packed_gemm(const PgArgs a) {
+  __shared__ float sW[2][kPgBK * kPgLD];
+  __shared__ float sX[2][kPgBK * kPgLD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
+  const int M = a.M, K = a.K, N = a.N;
+  const long long C = a.C;
+  const int m0 = (int)blockIdx.y * kPgBM;
+  const long long c0 = (long long)blockIdx.x * kPgBN;
+  const int piece = (int)blockIdx.z;
+  const int kb = a.parallel ? piece * a.kp : 0;
+  const int ke = a.parallel ? min(K, kb + a.kp) : K;
+  const unsigned char* __restrict__ codes = a.codes;
+  const long long nbytes = a.nbytes;
+
+  // W: this thread's run of 8 stream-consecutive codes of a step's 64 x 32 block
+  // (neighbouring lanes take neighbouring runs of the stream: 8 runs of a k row, 4 runs of an m row)
+  const int wrow = TRANS ? 8 * (tid & 7) : (tid >> 2);   // m - m0 of the run's first code
+  const int wk = TRANS ? (tid >> 3) : 8 * (tid & 3);     // k - k0 of the run's first code
+  const int nvm = TRANS ? min(8, M - (m0 + wrow)) : (m0 + wrow < M ? 8 : 0);   // codes of a full step's run inside W (<= 0: none)
+  const long long bit0 = (TRANS ? (long long)(kb + wk) * M + (m0 + wrow) : (long long)(m0 + wrow) * K + (kb + wk)) * BITS;
+  const int wsh = (int)(bit0 & 31);    // the run's 8 BITS <= 64 bits start at bit wsh of dword wq: three dwords
+  long long wq = bit0 >> 5;
+  const long long wstep = TRANS ? (long long)M * BITS : BITS;   // dwords per K-step
+  // X: 8 elements of the step's 32 x 64 block; layout 0: one column, k = xk + 4 j;
+  // layout 1: one k, columns xc + 8 j
+  const int xc = XL ? (tid >> 5) : (tid & 63);
+  const int xk = XL ? (tid & 31) : (tid >> 6);
+  long long xo[8];      // element offsets of the 8 loads from xp
+  unsigned xok = 0u;    // bit j: load j's column is inside C
+  const float* __restrict__ xp;
+  if (XL) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long long c = c0 + xc + 8 * j;
+      if (c < C) xok |= 1u << j;
+      xo[j] = min(c, C - 1) * K;
+    }
+    xp = a.x + (kb + xk);
+  } else {
+    const long long c = min(c0 + xc, C - 1);
+    if (c0 + xc < C) xok = 0xFFu;
+    const long long b = c / N;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xo[j] = (long long)(4 * j) * N;
+    xp = a.x + (b * K * N + (c - b * N)) + (long long)(kb + xk) * N;
+  }
+  const long long xstep = XL ? kPgBK : (long long)kPgBK * N;
+
+  unsigned cw[3];
+  int nv = 0;
+  float rx[8];
+  // the loads of the next step in stream order (each call advances wq and xp by one step)
+  auto load = [&](int k0, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    cw[0] = 0u; cw[1] = 0u; cw[2] = 0u;
+    if (FULL) nv = nvm;
+    else if (TRANS) nv = k0 + wk < ke ? nvm : 0;
+    else nv = nvm > 0 ? min(8, ke - (k0 + wk)) : 0;
+    if (nv > 0) {
+      if (4 * wq + 12 <= nbytes) {   // all three inside the stream: plain loads, issued together
+        const gcu32* q = (const gcu32*)(codes + 4 * wq);
+        cw[0] = q[0]; cw[1] = q[1]; cw[2] = q[2];
+      } else {                       // the stream's end: nothing past its last byte is read
+        cw[0] = code_dword(codes, wq, nbytes);
+        cw[1] = code_dword(codes, wq + 1, nbytes);
+        cw[2] = code_dword(codes, wq + 2, nbytes);
+      }
+    }
+    wq += wstep;
+    const gcf32* xg = (const gcf32*)xp;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (FULL) {
+        const float v = xg[xo[j]];
+        rx[j] = ((xok >> j) & 1u) ? v : 0.f;
+      } else {
+        const int k = XL ? k0 + xk : k0 + xk + 4 * j;
+        rx[j] = (((xok >> j) & 1u) && k < ke) ? xg[xo[j]] : 0.f;
+      }
+    }
+    xp += xstep;
+  };
+  auto store = [&](int buf) {
+    constexpr unsigned mask = (1u << BITS) - 1u;
+    // codes 0..3 lie in bits [wsh, wsh + 4 BITS) of (cw1 : cw0); codes 4..7 from bit p2 = wsh + 4 BITS <= 63
+    const int p2 = wsh + 4 * BITS;
+    const bool up = p2 >= 32;
+    unsigned long long win[2];
+    win[0] = (((unsigned long long)cw[1] << 32) | cw[0]) >> wsh;
+    win[1] = (((unsigned long long)(up ? cw[2] : cw[1]) << 32) | (up ? cw[1] : cw[0])) >> (p2 & 31);
+    float d[8];
+    if (a.scheme == kMinMax) {   // (one uniform branch per step, not one per code)
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        d[j] = dequant_code((unsigned)(win[j >> 2] >> ((j & 3) * BITS)) & mask, kMinMax, BITS, a.scale, a.zp, a.mn, a.rng);
+    } else {                     // mse-minmax / symmetric: the affine form with zero_point 0 (an exact integer)
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        d[j] = dequant_code((unsigned)(win[j >> 2] >> ((j & 3) * BITS)) & mask, kAffine, BITS, a.scale, a.zp, a.mn, a.rng);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = j < nv ? d[j] : 0.f;   // past the run's row / the piece / the matrix: exactly 0
+      if (TRANS) sW[buf][wk * kPgLD + wrow + j] = v;
+      else sW[buf][(wk + j) * kPgLD + wrow] = v;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (XL) sX[buf][xk * kPgLD + xc + 8 * j] = rx[j];
+      else sX[buf][(xk + 4 * j) * kPgLD + xc] = rx[j];
+    }
+  };
+  auto load_step = [&](int k0) {
+    if (k0 + kPgBK <= ke) load(k0, std::true_type{});
+    else load(k0, std::false_type{});
+  };
+
+  pg_f32x16 acc, tot;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; tot[r] = 0.f; }
+  bool first = true;
+  int pend = kb + a.kp;   // the current piece's end
+  load_step(kb);
+  store(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kb; k0 < ke; k0 += kPgBK) {
+    const bool more = k0 + kPgBK < ke;
+    if (more) load_step(k0 + kPgBK);
+    const float* w = sW[buf] + 32 * wm + i;
+    const float* x = sX[buf] + 32 * wn + i;
+#pragma unroll
+    for (int q = 0; q < kPgBK / 2; ++q) {
+      if (XL) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[(2 * q + h) * kPgLD], w[(2 * q + h) * kPgLD], acc, 0, 0, 0);
+      else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[(2 * q + h) * kPgLD], x[(2 * q + h) * kPgLD], acc, 0, 0, 0);
+    }
+    if (!more || k0 + kPgBK == pend) {   // a piece ends: fold it into the running sum
+      pend += a.kp;
+      if (first) {
+        tot = acc;
+        first = false;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tot[r] = tot[r] + acc[r];
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  float* const dst = a.parallel ? a.part + (long long)piece * a.total : a.y;
+  const float* __restrict__ bias = a.parallel ? nullptr : a.bias;
+  if (XL) {   // lanes along m, rows along the columns: Y[c M + m]
+    const int m = m0 + 32 * wm + i;
+    if (m >= M) return;
+    const float bv = bias ? bias[m] : 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const long long c = c0 + 32 * wn + PG_ROW(r);
+      if (c < C) dst[c * M + m] = bias ? tot[r] + bv : tot[r];
+    }
+  } else {    // lanes along the columns: Y[(b M + m) N + n]
+    const long long c = c0 + 32 * wn + i;
+    if (c >= C) return;
+    const long long b = c / N;
+    const long long ybase = b * M * N + (c - b * N);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + 32 * wm + PG_ROW(r);
+      if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+    }
+  }
+}
+
+// Y[e] = ((part_0[e] + part_1[e]) + ...) + bias[m(e)]: the piece order of the serial form
+__global__ __launch_bounds__(256) void k_packed_reduce(const float* __restrict__ part, int np, long long total,
+                                                       const float* __restrict__ bias, float* __restrict__ y, int M,
+                                                       int N, int xl) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  float s = part[e];
+  for (int p = 1; p < np; ++p) s = s + part[(long long)p * total + e];
+  if (bias) s = s + bias[xl ? e % M : (e / N) % M];
+  y[e] = s;
+}
+
+struct PgPlan {
+  int kp, np, parallel;
+  long long tiles_m, tiles_c, C, total;
+  size_t ws;
+};
+
+// A function of the four sizes alone; false when they are out of range.
+static bool plan_packed_gemm(int64_t M, int64_t K, int64_t N, int64_t nb, PgPlan& pl) {
+  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return false;
+  if (M > (int64_t(1) << 22) || K > (int64_t(1) << 24) || N > (int64_t(1) << 30) || nb > (int64_t(1) << 30)) return false;
+  if (M * K >= (int64_t(1) << 40)) return false;
+  const int64_t C = nb * N;
+  if (C > (int64_t(1) << 30)) return false;
+  pl.C = C;
+  pl.total = C * M;   // < 2^52
+  pl.kp = (int)std::max<int64_t>(kPgPieceMin, 32 * ((K + 32 * kPgPiecesMax - 1) / (32 * kPgPiecesMax)));
+  pl.np = (int)((K + pl.kp - 1) / pl.kp);
+  pl.tiles_m = (M + kPgBM - 1) / kPgBM;
+  pl.tiles_c = (C + kPgBN - 1) / kPgBN;
+  pl.parallel = (pl.np > 1 && pl.tiles_m * pl.tiles_c < kPgParallelBelow) ? 1 : 0;
+  pl.ws = pl.parallel ? (size_t)pl.np * (size_t)pl.total * sizeof(float) : 0;
+  return true;
+}
+
+}  // namespace admmq
+
+using namespace admmq;
+
+extern "C" {
+
+size_t admmq_packed_gemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t nb) {
+  PgPlan pl;
+  if (!plan_packed_gemm(M, K, N, nb, pl)) return 0;
+  return pl.ws;
+}
+
+int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                          const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (!codes || !x || !y || !meta) return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes, meta, x and y must not be NULL");
+  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: M, K, N and nb must be positive");
+  if (meta->bits < 1 || meta->bits > 8) return set_error(ADMMQ_ERR_ARG, "packed_gemm: meta bits must be 1..8");
+  if (meta->scheme < kMse || meta->scheme > kAffine)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: unknown meta scheme (the four tensor schemes only)");
+  if (meta->scheme == kMinMax && meta->bits == 1)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: tensor_minmax has no 1 bit code");
+  if (meta->bad != 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: meta bad != 0: not a valid packed tensor");
+  if (trans_w != 0 && trans_w != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: trans_w must be 0 or 1");
+  if (x_layout != 0 && x_layout != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout must be 0 or 1");
+  if (x_layout == 1 && nb != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout 1 (linear) needs nb = 1");
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes must be 16-byte aligned");
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: x, y and bias must be float aligned");
+  PgPlan pl;
+  if (!plan_packed_gemm(M, K, N, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_gemm: sizes out of range");
+  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
+  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: workspace must be float aligned");
+  PgArgs a;
+  a.codes = codes; a.x = x; a.bias = bias; a.y = y;
+  a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
+  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
+  a.total = pl.total; a.C = pl.C;
+  a.M = (int)M; a.K = (int)K; a.N = (int)N;
+  a.xl = x_layout;
+  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
+  a.scheme = meta->scheme;
+  a.zp = meta->scheme == kAffine ? meta->zero_point : 0;   // (the other schemes' table has none)
+  a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
+#define ADMMQ_PG_CASE(B)                                                                              \
+  case B:                                                                                             \
+    if (trans_w && x_layout) hipLaunchKernelGGL((k_packed_gemm<B, true, true>), grid, dim3(256), 0, s, a);        \
+    else if (trans_w) hipLaunchKernelGGL((k_packed_gemm<B, true, false>), grid, dim3(256), 0, s, a);  \
+    else if (x_layout) hipLaunchKernelGGL((k_packed_gemm<B, false, true>), grid, dim3(256), 0, s, a); \
+    else hipLaunchKernelGGL((k_packed_gemm<B, false, false>), grid, dim3(256), 0, s, a);              \
+    break;
+  switch (meta->bits) {
+    ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
+    ADMMQ_PG_CASE(5) ADMMQ_PG_CASE(6) ADMMQ_PG_CASE(7) ADMMQ_PG_CASE(8)
+    default: break;   // (refused above)
+  }
+#undef ADMMQ_PG_CASE
+  if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
+                       pl.total, bias, y, a.M, a.N, a.xl);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
+
+}  // extern "C"

@@ -177,6 +177,26 @@ __device__ __forceinline__ float apply_quant_mse(float x, const QParams& p) {
   return nan_clamp(q, p.qlo, p.qhi) * p.scale;
 }
 
+// Packed codes (pack_kernels.hip, packed_gemm.hip; include/admmq.h "Packed integer codes").
+// The table's de-quantization of code u: float32 operations in this order (-ffp-contract=off).
+__device__ __forceinline__ float dequant_code(unsigned u, int scheme, int bits, float scale, int zp, float mn,
+                                              float rng) {
+  const int q = 1 << (bits - 1);
+  if (scheme == kMinMax) return ((float)u * rng) / (float)((1 << bits) - 1) + mn;
+  if (scheme == kAffine) return (float)(((int)u - q) - zp) * scale;
+  return (float)((int)u - q) * scale;
+}
+
+// Dword w of a code stream of nbytes bytes; the stream's last, partial dword byte by byte
+// (nothing past the stream is read).
+__device__ __forceinline__ unsigned code_dword(const unsigned char* __restrict__ c, long long w, long long nbytes) {
+  if (4 * w + 4 <= nbytes) return *reinterpret_cast<const unsigned*>(c + 4 * w);
+  unsigned v = 0u;
+  for (int b = 0; b < 4; ++b)
+    if (4 * w + b < nbytes) v |= (unsigned)c[4 * w + b] << (8 * b);
+  return v;
+}
+
 // First-index argmin of sse[0..n) by ONE wave (all 64 lanes must call).
 __device__ __forceinline__ int wave_argmin_u64(const unsigned long long* sse, int n) {
   const int lane = threadIdx.x & 63;

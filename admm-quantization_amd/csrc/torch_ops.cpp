@@ -8,6 +8,7 @@
 //   admmq::quantize_batched        <- source/quantization.py:69-144 quantize_tensor
 //   admmq::quantize_packed / dequantize_packed: the packed integer codes of the tensor schemes
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
+//   admmq::packed_gemm             a packed weight times float32 activations
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -17,6 +18,7 @@
 #include <torch/library.h>
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
+#include <ATen/core/grad_mode.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/util/Exception.h>
 
@@ -295,6 +297,75 @@ std::vector<at::Tensor> dequantize_packed_meta(at::TensorList codes, const at::T
   return ys;
 }
 
+// --- packed_gemm ----------------------------------------------------------------------------
+// Y = W X (+ bias) with W the [M, K] de-quantization of `codes` (trans_w: of its transpose),
+// decoded inside the kernel (admmq_packed_gemm). meta_words: the 8 int32 words of admmq_qmeta
+// on the CPU (the host picks the kernel from its bits). x_layout 0: x [nb, K, *spatial] ->
+// [nb, M, *spatial]; x_layout 1: x [..., K] -> [..., M]. Inference only: no autograd formula.
+std::vector<int64_t> packed_gemm_shape(const at::Tensor& x, int64_t M, int64_t K, int64_t x_layout) {
+  TORCH_CHECK(x_layout == 0 || x_layout == 1, "admmq: packed_gemm: x_layout must be 0 (NCHW) or 1 (linear)");
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_gemm: M and K must be positive");
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  if (x_layout == 0) {
+    TORCH_CHECK(x.dim() >= 3 && x.size(1) == K, "admmq: packed_gemm: x must be [n, ", K, ", ...] (NCHW), got ", x.sizes());
+    shape[1] = M;
+  } else {
+    TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "admmq: packed_gemm: x must be [..., ", K, "], got ", x.sizes());
+    shape.back() = M;
+  }
+  return shape;
+}
+
+at::Tensor packed_gemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
+  static_assert(sizeof(admmq_qmeta) == 32, "meta is int32 [8]");
+  check_f32_device(x, "x");
+  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
+              "admmq: packed_gemm is inference only (no backward through packed weights): call it under "
+              "torch.no_grad() or detach x");
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
+              "admmq: packed_gemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_same_device(codes, x, "codes");
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
+              "admmq: packed_gemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
+  admmq_qmeta meta;
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_gemm: bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_gemm: a ", M,
+              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
+              " code bytes, got ", codes.numel());
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  at::Tensor cc = codes.contiguous();
+  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_gemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
+  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
+  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_gemm: empty x");
+  at::Tensor y = at::empty(oshape, xc.options());
+  const size_t nbytes = admmq_packed_gemm_workspace_size(M, K, N, static_cast<int32_t>(nb));
+  at::Tensor ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_gemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<float>(),
+                             static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
+                             bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(), ws.data_ptr(),
+                             ws.numel(), stream_of(xc)),
+           "packed_gemm");
+  return y;
+}
+
+at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
+  return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
+}
+
 // --- quantize_channel (channel_symmetric / channel_affine with an explicit dim) ----------------
 at::Tensor quantize_channel_cuda(const at::Tensor& x, int64_t bits, int64_t qscheme, int64_t dim) {
   check_f32_device(x, "tensor");
@@ -436,6 +507,8 @@ TORCH_LIBRARY(admmq, m) {
   m.def("quantize_packed(Tensor[] x, int bits, int qscheme, int num_attempts=200, float? tmin=None, "
         "float? tmax=None) -> (Tensor[] codes, Tensor meta)");
   m.def("dequantize_packed(Tensor[] codes, Tensor meta, int[] numel) -> Tensor[]");
+  m.def("packed_gemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
+        "Tensor? bias=None) -> Tensor");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -447,6 +520,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("quantize_batched", &quantize_batched_cuda);
   m.impl("quantize_packed", &quantize_packed_cuda);
   m.impl("dequantize_packed", &dequantize_packed_cuda);
+  m.impl("packed_gemm", &packed_gemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -457,6 +531,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("quantize_batched", &quantize_batched_meta);
   m.impl("quantize_packed", &quantize_packed_meta);
   m.impl("dequantize_packed", &dequantize_packed_meta);
+  m.impl("packed_gemm", &packed_gemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

@@ -186,6 +186,34 @@ int32_t admmq_quantize_packed(const admmq_qtensor* t, uint8_t* const* codes, adm
 int32_t admmq_dequantize_packed(const uint8_t* const* codes, const admmq_qmeta* meta_dev, float* const* y,
                                 const int64_t* numel, int32_t n, void* stream);
 
+/* Packed-weight GEMM: a weight kept as packed codes times float32
+ * activations, decoded on the fly; the float32 weight is never written to memory.
+ *   Y_b[M, N] = W[M, K] . X_b[K, N] (+ bias[M]),  b = 0 .. nb-1
+ *   trans_w = 0: W = D, the packed tensor is [M, K];  trans_w = 1: W = D^T, it is [K, M]
+ * with D the table de-quantization of the codes (the formulas above), in the layout
+ * admmq_quantize_packed wrote: admmq_packed_bytes(M*K, meta->bits) bytes, nothing past them
+ * is read. `meta` is a HOST record (its bits select the kernel); `bad` must be 0, `index` is
+ * ignored.
+ *   x_layout 0 (NCHW 1x1 conv): X [nb, K, N] and Y [nb, M, N] contiguous, N = H*W
+ *   x_layout 1 (linear):        X [N, K] and Y [N, M] row-major, one row per token; nb = 1
+ * codes: device, 16-byte aligned. x, y, bias (may be NULL): device, float (4-byte) aligned -
+ * no wider alignment is needed or used. Accumulation is exact float32 FMA on the fp32 MFMA:
+ * K is cut into pieces of max(64, 32 ceil(K/1024)), each summed in increasing k from zero,
+ * and an output is ((p0 + p1) + p2) + ... (+ bias last): a function of the inputs and K only,
+ * the same bits for every nb and on every call. Limits: M <= 2^22, K <= 2^24, nb*N <= 2^30,
+ * M*K < 2^40. ADMMQ_ERR_ARG for NULL codes / meta / x / y, non-positive sizes or sizes past
+ * the limits, meta->bits outside 1..8, an unknown scheme, tensor_minmax with 1 bit,
+ * meta->bad != 0, x_layout 1 with nb != 1, misaligned pointers; ADMMQ_ERR_WORKSPACE for a
+ * short workspace - all before any launch.
+ * admmq_packed_gemm_workspace_size depends on its arguments only. It returns 0 both for
+ * arguments out of range and when no workspace is needed (many output tiles: `workspace`
+ * may then be NULL); a positive size (float aligned device memory) is needed when the K
+ * pieces of a tile run as separate workgroups (few output tiles). */
+size_t admmq_packed_gemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t nb);
+int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                          const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

@@ -85,6 +85,43 @@ int main(void) {
   fails += admmq_admm_workspace_size(&bad, 1, 0) != 0;
   fails += admmq_admm_prepare(&bad, 1, 200, NULL, 0, NULL) == ADMMQ_OK;
   fails += admmq_quantize_batched(NULL, 1, 4, 99, 200, NULL, 0, NULL) != ADMMQ_ERR_SCHEME;
+  /* packed-weight GEMM: the planner over ragged sizes (a function of its arguments), then
+   * every refusal of the entry point (made-up device addresses: nothing may be launched) */
+  for (int t = 0; t < 400; ++t) {
+    const int64_t M = rnd(1, 6000), K = rnd(1, 6000), N = rnd(1, t % 3 ? 70 : 4000);
+    const int32_t nb = rnd(1, 8);
+    fails += admmq_packed_gemm_workspace_size(M, K, N, nb) != admmq_packed_gemm_workspace_size(M, K, N, nb);
+  }
+  fails += admmq_packed_gemm_workspace_size(512, 1141, 4, 1) == 0;
+  fails += admmq_packed_gemm_workspace_size(0, 8, 8, 1) != 0;
+  fails += admmq_packed_gemm_workspace_size(8, -1, 8, 1) != 0;
+  fails += admmq_packed_gemm_workspace_size(8, 8, 8, 0) != 0;
+  fails += admmq_packed_gemm_workspace_size((int64_t)1 << 40, 8, 8, 1) != 0;
+  {
+    const uint8_t* c = (const uint8_t*)0x1000;
+    const float* x = (const float*)0x10000;
+    float* y = (float*)0x20000;
+    void* ws = (void*)0x100000;
+    admmq_qmeta qm = {ADMMQ_TENSOR_MSEMINMAX_SYMMETRIC, 4, 0.125f, 0, 0.f, 0.f, -1, 0}, q2;
+    fails += admmq_packed_gemm(NULL, &qm, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, NULL, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 8, 8, NULL, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 8, 8, x, 0, 4, 1, NULL, NULL, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 0, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 8, 8, x, 0, -4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 8, 8, x, 1, 4, 2, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c + 4, &qm, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.bits = 9;
+    fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.scheme = 7;
+    fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX; q2.bits = 1;
+    fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.bad = 3;
+    fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+    fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, ws, 16, NULL) != ADMMQ_ERR_WORKSPACE;
+    fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, NULL, 0, NULL) != ADMMQ_ERR_WORKSPACE;
+  }
   printf("last error: %s\n", admmq_last_error());
   printf("%s (%d failures)\n", fails ? "FAIL" : "OK", fails);
   return fails ? 1 : 0;
