@@ -148,6 +148,7 @@ def load() -> ctypes.CDLL:
         "admmq_debug_set_legacy_stage1": (I32, [I32]),
         "admmq_debug_admm_plan_bytes": (S, [P, I32, I32, P]),
         "admmq_debug_admm_plan_digest": (I32, [P, I32, I32, I32, P, P]),
+        "admmq_debug_admm_run_schedule": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
         "admmq_debug_check_thresholds": (I32, [ctypes.c_uint32, I32]),
         "admmq_debug_set_fused_finalize": (I32, [I32]),
         "admmq_debug_set_search_units_per_block": (I32, [I32]),
@@ -251,36 +252,51 @@ def fault_repairs(reset: bool = False) -> int:
     return n
 
 
-class exhaustive_search:
+class _switch:
+    """A process switch held for a ``with`` block: ``_setter`` is called with ``_encode()``
+    on entry and with ``_restore`` on exit. ``_checked`` says whether the setter's status is
+    raised through ``check`` (on entry, on exit) or ignored."""
+
+    _setter = ""
+    _restore = 0
+    _checked = (False, False)
+
+    def _encode(self) -> int:
+        return 1 if self.enable else 0
+
+    def _set(self, value: int, checked: bool):
+        rc = getattr(load(), self._setter)(value)
+        if checked:
+            check(rc, type(self).__name__)
+
+    def __enter__(self):
+        self._set(self._encode(), self._checked[0])
+        return self
+
+    def __exit__(self, *exc):
+        self._set(self._restore, self._checked[1])
+        return False
+
+
+class exhaustive_search(_switch):
     """Context manager: evaluate every MSE candidate (the reference's 200 full passes)
     instead of the default two-stage exact search. Results are bit-identical; used
     for A/B timing and as a cross-check in the parity tests."""
 
+    _setter = "admmq_set_exhaustive_search"
+
     def __init__(self, enable: bool = True):
         self.enable = enable
 
-    def __enter__(self):
-        load().admmq_set_exhaustive_search(1 if self.enable else 0)
-        return self
 
-    def __exit__(self, *exc):
-        load().admmq_set_exhaustive_search(0)
-        return False
-
-
-class sel_widen:
+class sel_widen(_switch):
     """Context manager (diagnostics): keep every candidate in the two-stage search's
     selected set, so its multi-candidate paths - the canonical SSEs, and in the fused
     finalize the record published before the ready word, and the thin loop's stage 2 - run
     on every call. The answer is exact either way, so the bits are the same."""
 
-    def __enter__(self):
-        check(load().admmq_debug_set_sel_widen(1), "sel_widen")
-        return self
-
-    def __exit__(self, *exc):
-        check(load().admmq_debug_set_sel_widen(0), "sel_widen")
-        return False
+    _setter, _checked = "admmq_debug_set_sel_widen", (True, True)
+    enable = True
 
 
 class solve_mode:
@@ -305,124 +321,96 @@ class solve_mode:
         return False
 
 
-class fin_nv3:
+class fin_nv3(_switch):
     """Context manager: let the search take three float4 groups per thread where that keeps
     the finalize in the search launch (default), or at most two (planned at prepare, so the
     manager must enclose the whole call). Same integers. Restores the default on exit."""
 
+    _setter, _restore = "admmq_debug_set_fin_nv3", 1
+
     def __init__(self, enable: bool):
         self.enable = enable
 
-    def __enter__(self):
-        load().admmq_debug_set_fin_nv3(1 if self.enable else 0)
-        return self
 
-    def __exit__(self, *exc):
-        load().admmq_debug_set_fin_nv3(1)
-        return False
-
-
-class fused_finalize:
+class fused_finalize(_switch):
     """Context manager: run the big jobs' finalize step inside the search launch
     (default, where all of its blocks are resident) or as its own launch. Same
     integers; used as a cross-check in the parity tests. Restores the default on exit."""
 
+    _setter, _restore = "admmq_debug_set_fused_finalize", 1
+
     def __init__(self, enable: bool):
         self.enable = enable
 
-    def __enter__(self):
-        load().admmq_debug_set_fused_finalize(1 if self.enable else 0)
-        return self
 
-    def __exit__(self, *exc):
-        load().admmq_debug_set_fused_finalize(1)
-        return False
-
-
-class fin_wait_polls:
+class fin_wait_polls(_switch):
     """Context manager (diagnostics): polls of the fused finalize's bounded wait for its
     job's selection (1 forces the timeout / internal-fault path). Restores the default."""
+
+    _setter, _checked = "admmq_debug_set_fin_wait_polls", (True, False)
 
     def __init__(self, polls: int):
         self.polls = polls
 
-    def __enter__(self):
-        check(load().admmq_debug_set_fin_wait_polls(int(self.polls)), "fin_wait_polls")
-        return self
-
-    def __exit__(self, *exc):
-        load().admmq_debug_set_fin_wait_polls(0)
-        return False
+    def _encode(self):
+        return int(self.polls)
 
 
-class fin_capacity:
+class fin_capacity(_switch):
     """Context manager (diagnostics): resident-block budget of the fused finalize (0: the
     device's). A small budget forces its several-units-per-block form."""
+
+    _setter, _checked = "admmq_debug_set_fin_capacity", (True, False)
 
     def __init__(self, blocks: int):
         self.blocks = blocks
 
-    def __enter__(self):
-        check(load().admmq_debug_set_fin_capacity(int(self.blocks)), "fin_capacity")
-        return self
-
-    def __exit__(self, *exc):
-        load().admmq_debug_set_fin_capacity(0)
-        return False
+    def _encode(self):
+        return int(self.blocks)
 
 
-class thin_loop:
+class thin_loop(_switch):
     """Context manager: the persistent loop of the thin factors (k_thin_loop: every
     iteration of a call whose factors all have I <= 16 in one launch; default on) or the
     per-iteration launches; ``"wide"``: on, with 64-column workgroups wherever allowed
     (ld <= 512; normally only when 32-column teams would not fit on the CUs). Restores the
     default on exit."""
 
+    _setter, _restore, _checked = "admmq_debug_set_thin_loop", 1, (True, False)
+
     def __init__(self, enable):
         self.enable = enable
 
-    def __enter__(self):
-        code = 2 if self.enable == "wide" else (1 if self.enable else 0)
-        check(load().admmq_debug_set_thin_loop(code), "thin_loop")
-        return self
-
-    def __exit__(self, *exc):
-        load().admmq_debug_set_thin_loop(1)
-        return False
+    def _encode(self):
+        return 2 if self.enable == "wide" else (1 if self.enable else 0)
 
 
-class search_units_per_block:
+class search_units_per_block(_switch):
     """Context manager: stage-1 units per block of the search launch that runs without the
     fused finalize (0 = the planner's choice). Same integers for any value; used as a
     cross-check in the parity tests. Restores the planner's choice on exit."""
 
+    _setter, _checked = "admmq_debug_set_search_units_per_block", (True, False)
+
     def __init__(self, reps: int):
         self.reps = reps
 
-    def __enter__(self):
-        check(load().admmq_debug_set_search_units_per_block(int(self.reps)), "search_units_per_block")
-        return self
-
-    def __exit__(self, *exc):
-        load().admmq_debug_set_search_units_per_block(0)
-        return False
+    def _encode(self):
+        return int(self.reps)
 
 
-class stage1_form:
+class stage1_form(_switch):
     """Context manager: run stage 1 of the two-stage search in its per-level form
     (``"legacy"``, k_mse_hist) or its merged-threshold form (``"merged"``,
     k_mse_prep2 + k_mse_hist2). Both produce the same integers; used as a
     cross-check in the parity tests. Restores the merged default on exit."""
+
+    _setter = "admmq_debug_set_legacy_stage1"
 
     def __init__(self, form: str):
         if form not in ("legacy", "merged"):
             raise ValueError(form)
         self.form = form
 
-    def __enter__(self):
-        load().admmq_debug_set_legacy_stage1(1 if self.form == "legacy" else 0)
-        return self
-
-    def __exit__(self, *exc):
-        load().admmq_debug_set_legacy_stage1(0)
-        return False
+    def _encode(self):
+        return 1 if self.form == "legacy" else 0

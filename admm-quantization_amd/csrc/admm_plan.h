@@ -2,6 +2,12 @@
 // tile lists, the thin units and teams, the search units and the device tables of one
 // prepare / run call. Host code only; api.hip snapshots the switches, plans, uploads and
 // launches.
+// The run's form is decided here too: search_form (exhaustive / per-level / merged stage 1
+// and its host tables, shared with the standalone quantizer) and schedule_run (which
+// launches a run call makes, as a RunSchedule that admmq_admm_run_ex only follows). Both are
+// pure functions of their arguments: tests/test_plan_digest.py pins the plan and
+// tests/test_run_schedule.py the schedule (admmq_debug_admm_run_schedule against
+// tests/golden/run_schedules.json), without a device.
 #pragma once
 #include <vector>
 
@@ -126,6 +132,64 @@ unsigned long long plan_fingerprint(const AdmmPlan& pl, const void* ws);
 // Diagnostics (admmq_debug_admm_plan_digest): FNV-1a digests of a plan carved against
 // `ws`, one per section, so that a mismatch between two planners says where the plans differ.
 void plan_digest(const AdmmPlan& pl, const void* ws, uint64_t out[8]);
+
+// The form of the MSE candidate search for (num_attempts, bits), shared by the ADMM run and
+// the standalone quantizer: exhaustive (every candidate's canonical SSE) or two-stage, and
+// for the two-stage search the merged-threshold stage 1 with its host tables (rank0 / groups
+// as merged_tables writes them, uploaded only when `merged`) or the per-level stage 1.
+struct SearchForm {
+  bool exhaustive = false;
+  bool merged = false;
+  std::vector<unsigned short> rank0, groups;
+  int ngroups = 0;
+};
+// merged is false unless qscheme == kMse; force_exhaustive: the process switch
+// (admmq_set_exhaustive_search) or a caller that wants every candidate's SSE.
+SearchForm search_form(int ncand, int bits, int qscheme, bool force_exhaustive, bool legacy_stage1);
+
+// The process switches a run reads beyond the plan's (api.hip snapshots them once per
+// entry-point call; after the snapshot the call reads no atomics).
+struct RunSwitches {
+  bool exhaustive = false;       // admmq_set_exhaustive_search
+  bool legacy_stage1 = false;    // per-level stage 1 instead of merged thresholds
+  int thin_loop = 1;             // persistent thin loop: 0 off (the plan's PlanSwitches::thin_loop)
+  int fin_cap_override = 0;      // resident-block budget of the fused finalize (0: the device's)
+  unsigned fin_wait_polls = kFinWaitPollsDefault;   // polls of the fused paths' bounded waits
+};
+
+// The launches of one admmq_admm_run_ex call: what is zeroed before the loop, whether the
+// persistent thin loop is tried, and the launches of each of the `iters` iterations in
+// stream order (GEMM group, thin solve, search, small jobs, finalize). Host-only and pure:
+// tests/test_run_schedule.py pins it through admmq_debug_admm_run_schedule.
+enum SearchKind {
+  kSearchNone,       // not kMse, or no stage-1 unit outside the small-job kernel
+  kSearchHist3,      // merged stage 1, selection and stage 2 in k_mse_hist3
+  kSearchHist3Fin,   // ... with the big jobs' finalize fused (one whole-row unit per resident block)
+  kSearchHist,       // per-level stage 1 (k_mse_hist)
+  kSearchAll         // exhaustive: k_mse_select_all + k_mse_sse
+};
+struct RunSchedule {
+  int iters = 0;                 // per-iteration rounds: max_iter - 1
+  bool try_thin_loop = false;    // upload the teams, zero their sync words, try k_thin_loop for all rounds
+  bool zero_kctr = false;        // K-split arrival counters
+  bool zero_ready = false;       // fused-finalize ready words
+  bool gemm = false;             // the GEMM launch group runs ...
+  bool gemm_diag = false;        // ... with a diagnostic fp32 kernel (f32p / f32t) in it: event packets
+  bool thin_solve = false;
+  SearchKind search = kSearchNone;
+  bool search_multi = false;     // hist3 reads d_hist_multi (several units per block), else d_hist
+  int nh = 0;                    // blocks of the hist3 launch, units of the per-level one
+  bool fuse_small = false;       // the small jobs' search and finalize in k_mse_small_admm
+  int nf = 0;                    // units of the separate finalize launch (0: none)
+  bool fin_wanted = false;       // the fused finalize is possible but for the device's capacity
+};
+// Whether schedule_run will read `fin_capacity` (hist3_fin_capacity's answer for the device):
+// the caller makes that runtime query only then.
+bool fin_capacity_wanted(const AdmmPlan& pl, const SearchForm& sf, int qscheme, int ncand, bool fused_allowed);
+// fused_allowed: the call may take the paths that report a broken residency assumption
+// through info (the fused finalize, the thin loop).
+RunSchedule schedule_run(const AdmmPlan& pl, const SearchForm& sf, const RunSwitches& sw, int qscheme, int bits,
+                         int ncand, int max_iter, bool fused_allowed, int fin_capacity);
 
 // Pieces per 64 x 64 tile of an (I, R) factor, and how many of a launch's split tiles run
 // their pieces in parallel (diagnostic entry points use both)

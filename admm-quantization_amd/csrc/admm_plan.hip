@@ -857,4 +857,121 @@ void plan_digest(const AdmmPlan& pl, const void* ws, uint64_t out[8]) {
   off(pl.d_ready); off(pl.d_kctr); off(pl.d_rank0); off(pl.d_groups);
   out[7] = h;
 }
+
+// ---------------------------------------------------------------------------
+// The search form and the run's launch schedule
+
+// The two-stage search needs the per-block threshold table in LDS; otherwise exhaustive.
+static bool two_stage_ok(int ncand, int bits) {
+  return ncand <= kMaxStage1 && bits <= kMaxStage1Bits && hist_lds_bytes(ncand, bits) <= 64 * 1024;
+}
+
+// Exact merged order of the level thresholds for (n, qmax) (k_mse_hist3): thr[k][c] is
+// within a few ulps of (2k-1) ((n-1) + 5c) times a constant, so the integer keys give
+// the order; rank0[e] for e = (k-1) n + c, and the groups of equal keys as
+// {first rank, size, element indices...} padded to 6 entries. false: a tie group larger
+// than 4 (the per-level stage 1 is used instead).
+// rank0 is returned padded to kMaxMerged entries and followed by the coarse cell index
+// lower bound lo[g], g = 0..kCells (see h3_setup): the number of thresholds whose cell
+// (floor of threshold * kCells / largest threshold) is below g for EVERY mx. A
+// threshold's cell is floor(z (1 + d)) with z = kCells key / key_max and |d| a few ulps
+// (the float thresholds and the cell scale each within ~10 ulps of the key proportion),
+// so counting the keys with z (1 + 1e-4) < g can only undercount.
+static bool merged_tables(int n, int qmax, std::vector<unsigned short>& rank0, std::vector<unsigned short>& groups) {
+  const int M = qmax * n;
+  std::vector<std::pair<long long, int>> key(M);
+  for (int k = 1; k <= qmax; ++k)
+    for (int c = 0; c < n; ++c) key[(k - 1) * n + c] = {(long long)(2 * k - 1) * ((n - 1) + 5LL * c), (k - 1) * n + c};
+  std::sort(key.begin(), key.end());
+  rank0.assign(kMaxMerged + kCells + 2, 0);
+  groups.clear();
+  for (int r = 0; r < M;) {
+    int r1 = r + 1;
+    while (r1 < M && key[r1].first == key[r].first) ++r1;
+    for (int j = r; j < r1; ++j) rank0[key[j].second] = (unsigned short)j;
+    if (r1 - r > 1) {
+      if (r1 - r > 4) return false;
+      unsigned short g[6] = {(unsigned short)r, (unsigned short)(r1 - r), 0, 0, 0, 0};
+      for (int j = r; j < r1; ++j) g[2 + j - r] = (unsigned short)key[j].second;
+      groups.insert(groups.end(), g, g + 6);
+    }
+    r = r1;
+  }
+  const double kmax = (double)key[M - 1].first;
+  int cnt = 0;
+  for (int g = 0; g <= kCells; ++g) {
+    while (cnt < M && (double)kCells * (double)key[cnt].first / kmax * (1.0 + 1e-4) < (double)g) ++cnt;
+    rank0[kMaxMerged + g] = (unsigned short)cnt;
+  }
+  return true;
+}
+
+SearchForm search_form(int ncand, int bits, int qscheme, bool force_exhaustive, bool legacy_stage1) {
+  SearchForm sf;
+  sf.exhaustive = force_exhaustive || !two_stage_ok(ncand, bits);
+  sf.merged = !sf.exhaustive && merged_ok(ncand, bits) && !legacy_stage1 && qscheme == kMse &&
+              merged_tables(ncand, 1 << (bits - 1), sf.rank0, sf.groups);
+  if (!sf.merged) { sf.rank0.clear(); sf.groups.clear(); }   // (a refused tie group leaves them half written)
+  sf.ngroups = (int)sf.groups.size() / 6;
+  return sf;
+}
+
+// the small jobs' search and finalize in one block each (k_mse_small_admm)
+static bool small_jobs_fused(const AdmmPlan& pl, const SearchForm& sf, int qscheme, int ncand) {
+  return qscheme == kMse && !sf.exhaustive && sf.merged && !pl.small.empty() && pl.small_groups > 0 && ncand <= 1024;
+}
+// stage-1 units of the big jobs: the blocks of a search launch with the finalize fused
+static int fin_blocks(const AdmmPlan& pl, bool fuse_small) {
+  return fuse_small ? pl.nhist_big : (int)pl.hist_chunks.size();
+}
+
+bool fin_capacity_wanted(const AdmmPlan& pl, const SearchForm& sf, int qscheme, int ncand, bool fused_allowed) {
+  return fused_allowed && qscheme == kMse && !sf.exhaustive && sf.merged && pl.rows_aligned &&
+         fin_blocks(pl, small_jobs_fused(pl, sf, qscheme, ncand)) > 0;
+}
+
+RunSchedule schedule_run(const AdmmPlan& pl, const SearchForm& sf, const RunSwitches& sw, int qscheme, int bits,
+                         int ncand, int max_iter, bool fused_allowed, int fin_capacity) {
+  RunSchedule rs;
+  rs.iters = std::max(max_iter - 1, 0);
+  rs.zero_kctr = pl.nkctr > 0;
+  rs.fuse_small = small_jobs_fused(pl, sf, qscheme, ncand);
+  // the big jobs' finalize inside the search launch when all its blocks fit at once
+  // (with a margin of one resident block per CU: see hist3_fin_capacity): one whole-row
+  // unit per block, all blocks resident; a launch with more units than that takes the
+  // separate finalize launch (round 3 measured blocks taking several units each with the
+  // finalize fused: no faster at C4, 324 vs 318 ms per sweep, and that path held the fused
+  // kernel at 40 spilled VGPRs)
+  rs.fin_wanted = fin_capacity_wanted(pl, sf, qscheme, ncand, fused_allowed);
+  const int fin_cap = !rs.fin_wanted ? 0 : (sw.fin_cap_override > 0 ? std::min(sw.fin_cap_override, fin_capacity) : fin_capacity);
+  const int nfin_blocks = fin_blocks(pl, rs.fuse_small);
+  const bool fuse_fin = rs.fin_wanted && fin_cap > 0 && nfin_blocks <= fin_cap;
+  rs.zero_ready = fuse_fin;
+  // every problem thin: all iterations in one persistent launch (k_thin_loop) when the
+  // fused paths are allowed (the op's fault retry turns them off) and it fits the device
+  rs.try_thin_loop = pl.tl_ok && sw.thin_loop != 0 && fused_allowed && qscheme == kMse && !sf.exhaustive &&
+                     max_iter > 1 && ncand >= 2 && ncand <= kTLMaxCand && bits >= 2 && bits <= 5;
+  rs.gemm = pl.ntiles_wide + pl.ntiles_small + pl.ntiles_big + pl.nslots + pl.ntiles_f32t > 0;
+  rs.gemm_diag = pl.nslots + pl.ntiles_f32t > 0;
+  rs.thin_solve = !pl.thin.empty();
+  if (qscheme == kMse) {
+    if (sf.exhaustive) {
+      rs.search = kSearchAll;
+    } else if (!sf.merged) {
+      rs.search = kSearchHist;
+      rs.nh = (int)pl.hist_chunks.size();
+    } else {
+      // two-stage: stage 1, the selection and (when |S| > 1) stage 2 all in the hist launch;
+      // fused finalize: one whole-row unit per block; otherwise possibly several units per block
+      rs.nh = fuse_fin ? nfin_blocks : (rs.fuse_small ? pl.nhm_big : (int)pl.hist_multi.size());
+      if (rs.nh > 0) {
+        rs.search = fuse_fin ? kSearchHist3Fin : kSearchHist3;
+        rs.search_multi = !fuse_fin;
+      }
+    }
+  }
+  // fused: every job's finalize ran in the search launch (big jobs) or the small-job kernel
+  rs.nf = fuse_fin ? 0 : (rs.fuse_small ? pl.nfin_big : (int)pl.fin_chunks.size());
+  return rs;
+}
 }  // namespace admmq

@@ -1,5 +1,11 @@
 // C-ABI of libadmmq: workspace planning and stream-ordered launch sequences.
 // See include/admmq.h for the contract and the reference interfaces replaced.
+// What is left here: the error text, the pinned upload pool, the profiling marks, the process
+// switches with their setters and per-call snapshots (plan_switches, run_switches), the
+// workspace records, the standalone quantizer's plan and launches (QPlan, run_quant) and the
+// entry points, which validate, plan, upload and launch. What a call carves, which form its
+// search takes and which launches a run makes are decided in admm_plan.hip (plan_admm,
+// search_form, schedule_run): admmq_admm_run_ex only follows the schedule.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -182,6 +188,18 @@ static PlanSwitches plan_switches() {
   sw.hist_reps = g_hist_reps.load();
   return sw;
 }
+// The run's inputs among the switches, read once per entry-point call. thin_loop: the
+// value the call's plan was made with (one view of the switch for the plan and the run;
+// the standalone quantizer does not read it).
+static RunSwitches run_switches(int thin_loop = 1) {
+  RunSwitches sw;
+  sw.exhaustive = g_exhaustive.load();
+  sw.legacy_stage1 = g_legacy_stage1.load();
+  sw.thin_loop = thin_loop;
+  sw.fin_cap_override = g_fin_cap_override.load();
+  sw.fin_wait_polls = g_fin_wait_polls.load();
+  return sw;
+}
 
 // CUs of the current device (looked up once per device)
 static int device_cus() {
@@ -222,51 +240,6 @@ static int recorded_ws_mode(const void* ws) {
   return recorded_ws(ws, r) ? r.mode : -1;
 }
 
-// The two-stage search needs the per-block threshold table in LDS; otherwise exhaustive.
-static bool two_stage_ok(int ncand, int bits) {
-  return !g_exhaustive && ncand <= kMaxStage1 && bits <= kMaxStage1Bits && hist_lds_bytes(ncand, bits) <= 64 * 1024;
-}
-
-// Exact merged order of the level thresholds for (n, qmax) (k_mse_hist3): thr[k][c] is
-// within a few ulps of (2k-1) ((n-1) + 5c) times a constant, so the integer keys give
-// the order; rank0[e] for e = (k-1) n + c, and the groups of equal keys as
-// {first rank, size, element indices...} padded to 6 entries. false: a tie group larger
-// than 4 (the per-level stage 1 is used instead).
-// rank0 is returned padded to kMaxMerged entries and followed by the coarse cell index
-// lower bound lo[g], g = 0..kCells (see h3_setup): the number of thresholds whose cell
-// (floor of threshold * kCells / largest threshold) is below g for EVERY mx. A
-// threshold's cell is floor(z (1 + d)) with z = kCells key / key_max and |d| a few ulps
-// (the float thresholds and the cell scale each within ~10 ulps of the key proportion),
-// so counting the keys with z (1 + 1e-4) < g can only undercount.
-static bool merged_tables(int n, int qmax, std::vector<unsigned short>& rank0, std::vector<unsigned short>& groups) {
-  const int M = qmax * n;
-  std::vector<std::pair<long long, int>> key(M);
-  for (int k = 1; k <= qmax; ++k)
-    for (int c = 0; c < n; ++c) key[(k - 1) * n + c] = {(long long)(2 * k - 1) * ((n - 1) + 5LL * c), (k - 1) * n + c};
-  std::sort(key.begin(), key.end());
-  rank0.assign(kMaxMerged + kCells + 2, 0);
-  groups.clear();
-  for (int r = 0; r < M;) {
-    int r1 = r + 1;
-    while (r1 < M && key[r1].first == key[r].first) ++r1;
-    for (int j = r; j < r1; ++j) rank0[key[j].second] = (unsigned short)j;
-    if (r1 - r > 1) {
-      if (r1 - r > 4) return false;
-      unsigned short g[6] = {(unsigned short)r, (unsigned short)(r1 - r), 0, 0, 0, 0};
-      for (int j = r; j < r1; ++j) g[2 + j - r] = (unsigned short)key[j].second;
-      groups.insert(groups.end(), g, g + 6);
-    }
-    r = r1;
-  }
-  const double kmax = (double)key[M - 1].first;
-  int cnt = 0;
-  for (int g = 0; g <= kCells; ++g) {
-    while (cnt < M && (double)kCells * (double)key[cnt].first / kmax * (1.0 + 1e-4) < (double)g) ++cnt;
-    rank0[kMaxMerged + g] = (unsigned short)cnt;
-  }
-  return true;
-}
-
 static inline void prof_mark(hipStream_t s) {
   if (!g_prof.on || !g_prof.sampled || g_prof.next >= g_prof.ev.size()) return;
   (void)hipEventRecord(g_prof.ev[g_prof.next++], s);
@@ -299,6 +272,15 @@ static int upload_admm(const AdmmPlan& pl, hipStream_t s) {
   if (!pl.thin.empty() && (rc = h2d(pl.d_thin, pl.thin.data(), pl.thin.size() * sizeof(ThinLoopUnit), s))) return rc;
   if (!pl.small.empty() && (rc = h2d(pl.d_small, pl.small.data(), pl.small.size() * sizeof(int), s))) return rc;
   return check_hip("upload");
+}
+
+// The merged stage-1 tables of a search form (nothing unless merged; groups only when there are any)
+static int upload_search_tables(const SearchForm& sf, unsigned short* d_rank0, unsigned short* d_groups, hipStream_t s) {
+  int rc;
+  if (!sf.merged) return ADMMQ_OK;
+  if ((rc = h2d(d_rank0, sf.rank0.data(), sf.rank0.size() * 2, s))) return rc;
+  if (!sf.groups.empty() && (rc = h2d(d_groups, sf.groups.data(), sf.groups.size() * 2, s))) return rc;
+  return ADMMQ_OK;
 }
 
 __global__ void k_export_info(const ProbDesc* __restrict__ d, int n, int32_t* info) {
@@ -390,7 +372,7 @@ __global__ void k_copy_sse(const QJob* jobs, int ncand, unsigned long long* out)
   for (int c = threadIdx.x; c < ncand; c += blockDim.x) out[c] = jobs[0].mv.sse[c];
 }
 
-// exhaustive: evaluate every candidate's canonical SSE (debug table / forced mode)
+// sw.exhaustive: evaluate every candidate's canonical SSE (debug table / forced mode)
 // pack (optional): the final pass emits packed codes (k_qfinal_pack) instead of k_qfinal
 struct PackOut {
   unsigned char* const* host_codes;   // n device pointers (host array)
@@ -398,7 +380,7 @@ struct PackOut {
   admmq_qmeta* meta;                  // device, n entries
 };
 static int run_quant(QPlan& pl, int n, int bits, int qscheme, int ncand, hipStream_t s, bool final_pass,
-                     bool exhaustive, const PackOut* pack = nullptr) {
+                     const RunSwitches& sw, const PackOut* pack = nullptr) {
   int rc;
   if (pack) {
     if ((rc = h2d(pack->d_codes, pack->host_codes, n * sizeof(unsigned char*), s))) return rc;
@@ -412,16 +394,12 @@ static int run_quant(QPlan& pl, int n, int bits, int qscheme, int ncand, hipStre
   hipLaunchKernelGGL(k_qinit, dim3(n), dim3(256), 0, s, pl.d_jobs, n, ncand);
   launch_qpack(pl.d_jobs, n, pl.d_stat, (int)pl.stat_chunks.size(), s);
   if (qscheme == kMse) {
-    const bool all = exhaustive || !two_stage_ok(ncand, bits);
-    std::vector<unsigned short> rank0, groups;
-    const bool merged = !all && merged_ok(ncand, bits) && !g_legacy_stage1 &&
-                        merged_tables(ncand, 1 << (bits - 1), rank0, groups);
-    if (merged) {
-      if ((rc = h2d(pl.d_rank0, rank0.data(), rank0.size() * 2, s))) return rc;
-      if (!groups.empty() && (rc = h2d(pl.d_groups, groups.data(), groups.size() * 2, s))) return rc;
+    const SearchForm sf = search_form(ncand, bits, qscheme, sw.exhaustive, sw.legacy_stage1);
+    if ((rc = upload_search_tables(sf, pl.d_rank0, pl.d_groups, s))) return rc;
+    if (sf.merged) {
       launch_mse_hist3(nullptr, pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), ncand, bits, 0, pl.d_rank0,
-                       pl.d_groups, (int)groups.size() / 6, 1, false, 0, 0u, s);
-    } else if (!all) {
+                       pl.d_groups, sf.ngroups, 1, false, 0, 0u, s);
+    } else if (!sf.exhaustive) {
       launch_mse_hist(nullptr, pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), ncand, bits, 0, 1, s);
     } else {   // exhaustive: every candidate's canonical SSE over all chunks
       launch_mse_select_all(nullptr, pl.d_jobs, n, ncand, 0, s);
@@ -743,6 +721,64 @@ int32_t admmq_admm_prepare(const admmq_problem* probs, int32_t nprob, int32_t nu
   return admmq_admm_prepare_ex(probs, nprob, num_attempts, &o, workspace, workspace_bytes, stream);
 }
 
+// The per-call arguments the launches of an iteration share
+struct RunArgs {
+  int nprob, bits, qscheme, ncand;
+  float eps;
+  unsigned polls;
+};
+
+// One iteration's launches as the schedule lists them, one event pair per launch (classes:
+// include/admmq.h, admmq_profile_end)
+static void run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const SearchForm& sf, const RunArgs& a, int it,
+                          hipStream_t s) {
+  const int slot = it & 1;
+  if (rs.gemm) {
+    hipEvent_t g0 = nullptr, g1 = nullptr;
+    // the diagnostic fp32 kernels: event packets
+    if (rs.gemm_diag) { prof_class(ADMMQ_PROF_GEMM); prof_mark(s); } else { prof_pair(ADMMQ_PROF_GEMM, &g0, &g1); }
+    if (pl.ntiles_wide + pl.ntiles_small + pl.ntiles_big > 0)
+      launch_gemm(pl.d_desc, pl.d_tiles, pl.ntiles_wide, pl.ntiles_small, pl.ntiles_big, pl.split, slot, it, a.eps,
+                  a.ncand, s, g0, g1, pl.ksplit_par);
+    if (pl.nslots > 0)
+      launch_gemm_f32p(pl.d_desc, pl.d_tiles + pl.ntiles_wide, pl.d_list_off, pl.nslots, slot, it, a.eps, a.ncand, s);
+    if (pl.ntiles_f32t > 0)
+      launch_gemm_f32t(pl.d_desc, pl.d_tiles + pl.ntiles_wide, pl.ntiles_f32t, slot, it, a.eps, a.ncand, s);
+    if (rs.gemm_diag) prof_mark(s);
+  }
+  if (rs.thin_solve) {
+    prof_class(ADMMQ_PROF_GEMM_THIN); prof_mark(s);
+    launch_thin_solve(pl.d_desc, pl.d_thin, (int)pl.thin.size(), pl.thin_nr, pl.thin_maxld, slot, it, a.eps, a.ncand, s);
+    prof_mark(s);
+  }
+  if (rs.search == kSearchHist3 || rs.search == kSearchHist3Fin) {
+    hipEvent_t h0, h1;
+    prof_pair(ADMMQ_PROF_SEARCH, &h0, &h1);
+    launch_mse_hist3(pl.d_desc, nullptr, rs.search_multi ? pl.d_hist_multi : pl.d_hist, rs.nh, a.ncand, a.bits, slot,
+                     pl.d_rank0, pl.d_groups, sf.ngroups, pl.hist_nv, rs.search == kSearchHist3Fin, it, a.polls, s, h0, h1);
+  } else if (rs.search != kSearchNone) {
+    prof_class(ADMMQ_PROF_SEARCH); prof_mark(s);
+    if (rs.search == kSearchHist) {
+      launch_mse_hist(pl.d_desc, nullptr, pl.d_hist, rs.nh, a.ncand, a.bits, slot, pl.hist_nv, s);
+    } else {
+      launch_mse_select_all(pl.d_desc, nullptr, a.nprob, a.ncand, slot, s);
+      launch_mse_sse(pl.d_desc, nullptr, pl.d_sse, (int)pl.sse_chunks.size(), a.ncand, a.bits, slot, s);
+    }
+    prof_mark(s);
+  }
+  if (rs.fuse_small) {
+    prof_class(ADMMQ_PROF_SMALL); prof_mark(s);
+    launch_mse_small_admm(pl.d_desc, pl.d_small, (int)pl.small.size(), pl.small_groups, a.ncand, a.bits, slot, it,
+                          pl.d_rank0, pl.d_groups, sf.ngroups, s);
+    prof_mark(s);
+  }
+  if (rs.nf > 0) {
+    prof_class(ADMMQ_PROF_FINALIZE); prof_mark(s);
+    launch_finalize_admm(pl.d_desc, pl.d_fin, rs.nf, pl.fin_groups, a.ncand, a.bits, a.qscheme, slot, it, s);
+    prof_mark(s);
+  }
+}
+
 int32_t admmq_admm_run_ex(const admmq_problem* probs, int32_t nprob, int32_t max_iter, float eps, int32_t bits,
                           int32_t qscheme, int32_t num_attempts, const admmq_admm_options* opt, void* workspace,
                           size_t workspace_bytes, int32_t* info, void* stream) {
@@ -755,124 +791,46 @@ int32_t admmq_admm_run_ex(const admmq_problem* probs, int32_t nprob, int32_t max
     return fail(ADMMQ_ERR_ARG, "admm_run: the workspace has not been prepared (admmq_admm_prepare)");
   const int rec = wr.mode;
   if (rec != opt->solve_mode) return fail(ADMMQ_ERR_ARG, "admm_run: solve_mode differs from the one its prepare used");
+  const PlanSwitches psw = plan_switches();
+  const RunSwitches sw = run_switches(psw.thin_loop);
   AdmmPlan pl;
-  rc = plan_admm(probs, nprob, num_attempts, workspace, plan_switches(), rec, device_cus(), pl);
+  rc = plan_admm(probs, nprob, num_attempts, workspace, psw, rec, device_cus(), pl);
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   if (plan_fingerprint(pl, workspace) != wr.fp)
     return fail(ADMMQ_ERR_ARG, "admm_run: the problems or layout switches differ from the workspace's prepare");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // descriptors carry this call's output pointers (H_out may differ from prepare's)
-  if ((rc = upload_admm(pl, s))) return rc;
-  if (pl.nkctr > 0 && hipMemsetAsync(pl.d_kctr, 0, pl.nkctr * sizeof(unsigned), s) != hipSuccess)
-    return check_hip("K-split counter reset");
-  const int nsse = (int)pl.sse_chunks.size(), nfin = (int)pl.fin_chunks.size();
-  const int nhist = (int)pl.hist_chunks.size();
-  const bool exhaustive = !two_stage_ok(num_attempts, bits);
-  std::vector<unsigned short> rank0, groups;
-  const bool merged = !exhaustive && merged_ok(num_attempts, bits) && !g_legacy_stage1 && qscheme == kMse &&
-                      merged_tables(num_attempts, 1 << (bits - 1), rank0, groups);
-  const int ngroups = (int)groups.size() / 6;
-  if (merged) {
-    if ((rc = h2d(pl.d_rank0, rank0.data(), rank0.size() * 2, s))) return rc;
-    if (ngroups && (rc = h2d(pl.d_groups, groups.data(), groups.size() * 2, s))) return rc;
-  }
-  const bool fuse_small = qscheme == kMse && !exhaustive && merged && !pl.small.empty() &&
-                          pl.small_groups > 0 && num_attempts <= 1024;
-  // the big jobs' finalize inside the search launch when all its blocks fit at once
-  // (with a margin of one resident block per CU: see hist3_fin_capacity)
-  const int nh_big = fuse_small ? pl.nhist_big : nhist;
+  // which launches the call makes (admm_plan.hip): host code only, but for the resident-block
+  // query of the fused finalize, made only where the schedule reads its answer
+  const SearchForm sf = search_form(num_attempts, bits, qscheme, sw.exhaustive, sw.legacy_stage1);
   // the fused paths report a broken residency assumption only through info: without it
   // they never run (include/admmq.h)
   const bool fused_allowed = opt->fused_finalize != 0 && info != nullptr;
-  const bool fin_ok = fused_allowed && qscheme == kMse && !exhaustive && merged && pl.rows_aligned && nh_big > 0;
-  const int cap_over = g_fin_cap_override.load();
-  const int fin_cap = fin_ok ? (cap_over > 0 ? std::min(cap_over, hist3_fin_capacity(num_attempts, bits, pl.hist_nv))
-                                             : hist3_fin_capacity(num_attempts, bits, pl.hist_nv))
-                             : 0;
-  // one whole-row unit per block, all blocks resident; a launch with more units than that
-  // takes the separate finalize launch (round 3 measured blocks taking several units each
-  // with the finalize fused: no faster at C4, 324 vs 318 ms per sweep, and that path held
-  // the fused kernel at 40 spilled VGPRs)
-  const int nfin_blocks = nh_big;
-  const bool fuse_fin = fin_ok && fin_cap > 0 && nfin_blocks <= fin_cap;
-  const unsigned polls = g_fin_wait_polls.load();
-  if (fuse_fin && hipMemsetAsync(pl.d_ready, 0, 2 * (size_t)nprob * sizeof(unsigned long long), s) != hipSuccess)
+  const int fin_capacity = fin_capacity_wanted(pl, sf, qscheme, num_attempts, fused_allowed)
+                               ? hist3_fin_capacity(num_attempts, bits, pl.hist_nv) : 0;
+  const RunSchedule rs = schedule_run(pl, sf, sw, qscheme, bits, num_attempts, max_iter, fused_allowed, fin_capacity);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // descriptors carry this call's output pointers (H_out may differ from prepare's)
+  if ((rc = upload_admm(pl, s))) return rc;
+  if (rs.zero_kctr && hipMemsetAsync(pl.d_kctr, 0, pl.nkctr * sizeof(unsigned), s) != hipSuccess)
+    return check_hip("K-split counter reset");
+  if ((rc = upload_search_tables(sf, pl.d_rank0, pl.d_groups, s))) return rc;
+  if (rs.zero_ready && hipMemsetAsync(pl.d_ready, 0, 2 * (size_t)nprob * sizeof(unsigned long long), s) != hipSuccess)
     return check_hip("ready reset");
-  // every problem thin: all iterations in one persistent launch (k_thin_loop) when the
-  // fused paths are allowed (the op's fault retry turns them off) and it fits the device
+  const RunArgs a{nprob, bits, qscheme, num_attempts, eps, sw.fin_wait_polls};
   bool loop_done = false;
-  if (pl.tl_ok && g_thin_loop.load() != 0 && fused_allowed && qscheme == kMse && !exhaustive && max_iter > 1 &&
-      num_attempts >= 2 && num_attempts <= kTLMaxCand && bits >= 2 && bits <= 5) {
+  if (rs.try_thin_loop) {
     if ((rc = h2d(pl.d_tl_units, pl.tl_units.data(), pl.tl_units.size() * sizeof(ThinLoopUnit), s))) return rc;
     if (hipMemsetAsync(pl.d_tl_sync, 0, (size_t)nprob * sizeof(ThinSync), s) != hipSuccess)
       return check_hip("thin loop reset");
     g_prof.sampled = true;
     prof_class(ADMMQ_PROF_THIN_LOOP); prof_mark(s);
     loop_done = launch_thin_loop(pl.d_desc, pl.d_tl_units, (int)pl.tl_units.size(), pl.d_tl_sync, pl.thin_nr, pl.thin_maxld,
-                                 max_iter - 1, eps, num_attempts, bits, polls, device_cus(), s) == 0;
+                                 rs.iters, eps, num_attempts, bits, a.polls, device_cus(), s) == 0;
     prof_mark(s);
   }
-  for (int it = 0; !loop_done && it + 1 < max_iter; ++it) {
-    const int slot = it & 1;
+  for (int it = 0; !loop_done && it < rs.iters; ++it) {
     g_prof.sampled = it % g_prof.every == 0;
-    // one event pair per launch (classes: include/admmq.h, admmq_profile_end)
-    if (pl.ntiles_wide + pl.ntiles_small + pl.ntiles_big + pl.nslots + pl.ntiles_f32t > 0) {
-      const bool diag = pl.nslots + pl.ntiles_f32t > 0;   // the diagnostic fp32 kernels: event packets
-      hipEvent_t g0 = nullptr, g1 = nullptr;
-      if (diag) { prof_class(ADMMQ_PROF_GEMM); prof_mark(s); } else { prof_pair(ADMMQ_PROF_GEMM, &g0, &g1); }
-      if (pl.ntiles_wide + pl.ntiles_small + pl.ntiles_big > 0)
-        launch_gemm(pl.d_desc, pl.d_tiles, pl.ntiles_wide, pl.ntiles_small, pl.ntiles_big, pl.split, slot, it, eps,
-                    num_attempts, s, g0, g1, pl.ksplit_par);
-      if (pl.nslots > 0)
-        launch_gemm_f32p(pl.d_desc, pl.d_tiles + pl.ntiles_wide, pl.d_list_off, pl.nslots, slot, it, eps, num_attempts,
-                         s);
-      if (pl.ntiles_f32t > 0)
-        launch_gemm_f32t(pl.d_desc, pl.d_tiles + pl.ntiles_wide, pl.ntiles_f32t, slot, it, eps, num_attempts, s);
-      if (diag) prof_mark(s);
-    }
-    if (!pl.thin.empty()) {
-      prof_class(ADMMQ_PROF_GEMM_THIN); prof_mark(s);
-      launch_thin_solve(pl.d_desc, pl.d_thin, (int)pl.thin.size(), pl.thin_nr, pl.thin_maxld, slot, it, eps,
-                        num_attempts, s);
-      prof_mark(s);
-    }
-    if (qscheme == kMse) {
-      // two-stage: stage 1, the selection and (when |S| > 1) stage 2 all in the hist launch
-      if (!exhaustive && merged) {
-        // fused finalize: one whole-row unit per block; otherwise possibly several units per block
-        const int nh = fuse_fin ? nfin_blocks : (fuse_small ? pl.nhm_big : (int)pl.hist_multi.size());
-        if (nh > 0) {
-          hipEvent_t h0, h1;
-          prof_pair(ADMMQ_PROF_SEARCH, &h0, &h1);
-          launch_mse_hist3(pl.d_desc, nullptr,
-                           fuse_fin ? pl.d_hist : pl.d_hist_multi, nh, num_attempts,
-                           bits, slot, pl.d_rank0, pl.d_groups, ngroups, pl.hist_nv, fuse_fin, it, polls, s, h0, h1);
-        }
-        if (fuse_small) {   // the small jobs' search and finalize in one block each
-          prof_class(ADMMQ_PROF_SMALL); prof_mark(s);
-          launch_mse_small_admm(pl.d_desc, pl.d_small, (int)pl.small.size(), pl.small_groups, num_attempts, bits,
-                                slot, it, pl.d_rank0, pl.d_groups, ngroups, s);
-          prof_mark(s);
-        }
-      } else {
-        prof_class(ADMMQ_PROF_SEARCH); prof_mark(s);
-        if (!exhaustive) {
-          launch_mse_hist(pl.d_desc, nullptr, pl.d_hist, nhist, num_attempts, bits, slot, pl.hist_nv, s);
-        } else {
-          launch_mse_select_all(pl.d_desc, nullptr, nprob, num_attempts, slot, s);
-          launch_mse_sse(pl.d_desc, nullptr, pl.d_sse, nsse, num_attempts, bits, slot, s);
-        }
-        prof_mark(s);
-      }
-    }
-    // fused: every job's finalize ran in the search launch (big jobs) or the small-job kernel
-    const int nf = fuse_fin ? 0 : (fuse_small ? pl.nfin_big : nfin);
-    if (nf > 0) {
-      prof_class(ADMMQ_PROF_FINALIZE); prof_mark(s);
-      launch_finalize_admm(pl.d_desc, pl.d_fin, nf, pl.fin_groups, num_attempts, bits, qscheme, slot, it, s);
-      prof_mark(s);
-    }
+    run_iteration(pl, rs, sf, a, it, s);
   }
   g_prof.sampled = true;
   if (max_iter > 1) launch_unpack(pl.d_desc, nprob, pl.maxI, pl.maxR, s);
@@ -888,6 +846,44 @@ int32_t admmq_admm_run(const admmq_problem* probs, int32_t nprob, int32_t max_it
   if (rec >= 0) o.solve_mode = rec;
   return admmq_admm_run_ex(probs, nprob, max_iter, eps, bits, qscheme, num_attempts, &o, workspace, workspace_bytes,
                            info, stream);
+}
+
+// diagnostics (not in include/admmq.h): the launch schedule admmq_admm_run_ex would follow
+// for these problems under the current switches, planned against a fake workspace address
+// (never dereferenced). fused_finalize: the option; has_info: whether the call passes an
+// info array; fin_capacity: the resident blocks of the fused search kernel, so that the
+// answer does not depend on the machine (negative: ask the current device, and only where the
+// run would). out, one field of SearchForm / RunSchedule (admm_plan.h) per slot:
+//   0 iters            1 try_thin_loop    2 zero_kctr     3 zero_ready
+//   4 gemm (0 none, 1 the launch group, 2 with a diagnostic fp32 kernel in it)
+//   5 thin_solve       6 search (SearchKind)
+//   7 search list (0 d_hist, 1 d_hist_multi)              8 nh
+//   9 fuse_small      10 nf              11 exhaustive   12 merged
+//  13 ngroups         14 fin_wanted      15 the plan's finalize units
+int32_t admmq_debug_admm_run_schedule(const admmq_problem* probs, int32_t nprob, int32_t num_attempts, int32_t bits,
+                                      int32_t qscheme, int32_t max_iter, int32_t solve_mode, int32_t fused_finalize,
+                                      int32_t has_info, int32_t fin_capacity, int32_t out[16]) {
+  if (!out) return fail(ADMMQ_ERR_ARG, "run schedule: out must not be NULL");
+  if (solve_mode != kSolveF32 && solve_mode != kSolveSplit) return fail(ADMMQ_ERR_ARG, "solve mode must be 0 (fp32) or 1 (split)");
+  if (!valid_scheme(qscheme)) return fail(ADMMQ_ERR_SCHEME, "unknown qscheme");
+  if (!valid_bits(bits)) return fail(ADMMQ_ERR_ARG, "bits out of range");
+  const PlanSwitches psw = plan_switches();
+  const RunSwitches sw = run_switches(psw.thin_loop);
+  AdmmPlan pl;
+  const int rc = plan_admm(probs, nprob, num_attempts, reinterpret_cast<void*>(uintptr_t(1) << 20), psw, solve_mode,
+                           device_cus(), pl);
+  if (rc) return rc;
+  const SearchForm sf = search_form(num_attempts, bits, qscheme, sw.exhaustive, sw.legacy_stage1);
+  const bool fused_allowed = fused_finalize != 0 && has_info != 0;
+  if (fin_capacity < 0)
+    fin_capacity = fin_capacity_wanted(pl, sf, qscheme, num_attempts, fused_allowed)
+                       ? hist3_fin_capacity(num_attempts, bits, pl.hist_nv) : 0;
+  const RunSchedule rs = schedule_run(pl, sf, sw, qscheme, bits, num_attempts, max_iter, fused_allowed, fin_capacity);
+  const int32_t slots[16] = {rs.iters, rs.try_thin_loop, rs.zero_kctr, rs.zero_ready, rs.gemm ? (rs.gemm_diag ? 2 : 1) : 0,
+                             rs.thin_solve, rs.search, rs.search_multi, rs.nh, rs.fuse_small, rs.nf, sf.exhaustive,
+                             sf.merged, sf.ngroups, rs.fin_wanted, (int32_t)pl.fin_chunks.size()};
+  std::copy(slots, slots + 16, out);
+  return ADMMQ_OK;
 }
 
 // diagnostics (not in include/admmq.h): per-block timelines of the last launches (make TRACE=1)
@@ -976,7 +972,7 @@ int32_t admmq_quantize_batched(const admmq_qtensor* t, int32_t n, int32_t bits, 
   int rc = plan_quant(t, n, num_attempts, workspace, pl);
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
-  return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, g_exhaustive.load());
+  return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, run_switches());
 }
 
 size_t admmq_packed_bytes(int64_t numel, int32_t bits) {
@@ -1013,7 +1009,7 @@ int32_t admmq_quantize_packed(const admmq_qtensor* t, uint8_t* const* codes, adm
   if (!workspace || workspace_bytes < align_up(off + (size_t)n * sizeof(unsigned char*), 256))
     return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   PackOut po{codes, reinterpret_cast<unsigned char**>(static_cast<char*>(workspace) + off), meta_dev};
-  return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, g_exhaustive.load(), &po);
+  return run_quant(pl, n, bits, qscheme, num_attempts, static_cast<hipStream_t>(stream), true, run_switches(), &po);
 }
 
 int32_t admmq_dequantize_packed(const uint8_t* const* codes, const admmq_qmeta* meta_dev, float* const* y,
@@ -1058,7 +1054,9 @@ int32_t admmq_mse_sse_table(const float* x, int64_t rows, int64_t cols, int32_t 
   if (rc) return rc;
   if (!workspace || workspace_bytes < pl.bytes) return fail(ADMMQ_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if ((rc = run_quant(pl, 1, bits, kMse, num_attempts, s, false, true))) return rc;
+  RunSwitches sw = run_switches();
+  sw.exhaustive = true;   // the table holds every candidate's SSE
+  if ((rc = run_quant(pl, 1, bits, kMse, num_attempts, s, false, sw))) return rc;
   hipLaunchKernelGGL(k_copy_sse, dim3(1), dim3(256), 0, s, pl.d_jobs, num_attempts,
                      reinterpret_cast<unsigned long long*>(sse_out));
   return check_hip("mse_sse_table");

@@ -367,3 +367,68 @@ def test_ksplit_factors(torch_dev):
         _lib.check(lib.admmq_debug_set_ksplit(1), "ksplit")
         _lib.check(lib.admmq_debug_set_ksplit_form(1), "ksplit_form")
     print(f"K-split factors: worst H_T rel {worst:.2e}")
+
+
+# class indices of admmq_profile_end (include/admmq.h ADMMQ_PROF_*)
+_PROF = {"gemm": 0, "gemm_thin": 1, "search": 2, "small": 3, "finalize": 4, "prepare": 5, "thin_loop": 6}
+
+
+@pytest.mark.parametrize("batch", [[(9, 134), (9, 40)], [(64, 134), (9, 134)]], ids=["all_thin", "mixed"])
+def test_run_schedule_matches_launches(torch_dev, batch):
+    """The launch schedule (admm_plan.hip schedule_run, as admmq_debug_admm_run_schedule reports
+    it, asking the device for the fused finalize's capacity) against what ran: for 4 inner
+    iterations of an all-thin and a mixed batch under the defaults, thin_loop(False),
+    fused_finalize(False), exhaustive_search() and tensor_minmax, every launch class but the
+    prepare phase counts what the schedule says - the per-iteration launches max_iter - 1
+    times, or none of them after a thin loop that ran (these teams fit any device) - and the
+    three other forms of the MSE search give the default's H and U bit for bit."""
+    import contextlib
+    import ctypes
+    import gen_run_schedules as gen
+    torch, dev = torch_dev
+    from admmq import admm_iteration_batched, _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(11)
+    probs = []
+    for (I, R) in batch:
+        B = rng.standard_normal((R, 2 * R)).astype(np.float32) / np.float32(np.sqrt(2 * R))
+        probs.append((rng.standard_normal((I, R)).astype(np.float32), rng.standard_normal((I, R)).astype(np.float32),
+                      (B @ B.T + 0.5 * np.eye(R)).astype(np.float32)))
+    iters = 4
+    forms = {"default": (contextlib.nullcontext, MSE, 1), "thin_loop=0": (lambda: _lib.thin_loop(False), MSE, 1),
+             "fused_finalize=0": (lambda: _lib.fused_finalize(False), MSE, 0),
+             "exhaustive": (_lib.exhaustive_search, MSE, 1), "minmax": (contextlib.nullcontext, "tensor_minmax", 1)}
+    outs, kinds = {}, {}
+    for name, (manager, scheme, fused) in forms.items():
+        ps = [(_t(torch, dev, H), torch.zeros(H.shape, device=dev), _t(torch, dev, F), _t(torch, dev, G))
+              for (H, F, G) in probs]
+        ms, cnt = (ctypes.c_double * 8)(), (ctypes.c_int64 * 8)()
+        with manager():
+            s = gen.schedule(lib, batch, qscheme=_lib.SCHEMES[scheme], bits=4, max_iter=iters, fused_finalize=fused,
+                             has_info=1, fin_capacity=-1, num_attempts=200)
+            _lib.check(lib.admmq_profile_begin(256, 1), "profile_begin")
+            try:
+                Hs, info = admm_iteration_batched(ps, iters, 0.0, 4, scheme, return_info=True)
+                torch.cuda.synchronize()
+            finally:
+                _lib.check(lib.admmq_profile_end(ms, cnt), "profile_end")
+        info = info.cpu().numpy()
+        assert (info[:, 2:] == 0).all(), (name, info)   # no SPD error, no internal fault, no re-run
+        per_iter = 0 if s["try_thin_loop"] else s["iters"]
+        want = {"gemm": per_iter * (s["gemm"] != gen.GEMM_NONE), "gemm_thin": per_iter * s["thin_solve"],
+                "search": per_iter * (s["search"] != gen.SEARCH_NONE), "small": per_iter * s["fuse_small"],
+                "finalize": per_iter * (s["nf"] > 0), "thin_loop": s["try_thin_loop"]}
+        got = {c: int(cnt[_PROF[c]]) for c in want}
+        print(f"{name}: schedule {s}\n  launches {got}")
+        assert s["iters"] == iters - 1 and got == want, (name, got, want)
+        assert int(cnt[7]) == 0 and int(cnt[_PROF["prepare"]]) == 1, name
+        kinds[name] = (s["try_thin_loop"], s["search"])
+        outs[name] = [h.cpu() for h in Hs] + [p[1].cpu() for p in ps]
+    # the forms differ: the default takes a fused path (the thin loop, or the finalize in the
+    # search launch) that fused_finalize(False) must not
+    assert kinds["default"] in ((1, gen.SEARCH_NONE), (0, gen.SEARCH_HIST3_FIN)), kinds
+    assert kinds["fused_finalize=0"] in ((0, gen.SEARCH_NONE), (0, gen.SEARCH_HIST3)), kinds
+    assert kinds["exhaustive"] == (0, gen.SEARCH_ALL) and kinds["minmax"] == (0, gen.SEARCH_NONE), kinds
+    for name in ("thin_loop=0", "fused_finalize=0", "exhaustive"):
+        for a, b in zip(outs["default"], outs[name]):
+            assert torch.equal(a, b), name

@@ -3,7 +3,8 @@
  * against build/asan/libadmmq_asan.so, whose host code is instrumented (-Xarch_host
  * -fsanitize=address,undefined; device code untouched). Runs without a GPU: it drives the
  * host-only planners (workspace-size queries: problem layout, tile lists and their CU
- * ordering, stage-1 chunking, the finalize / small-job plans) over the bench configs
+ * ordering, stage-1 chunking, the finalize / small-job plans; the search form and the
+ * run's launch schedule through admmq_debug_admm_run_schedule) over the bench configs
  * C3 / C4 / C5 and seeded random batches, and the argument-validation error paths. Any
  * heap / stack overflow or UB in that code aborts with a sanitizer report.
  * usage: build/asan/asan_host_check   (exit 0 = clean) */
@@ -19,12 +20,38 @@ static int rnd(int lo, int hi) { /* xorshift64, inclusive range */
   return lo + (int)(rng % (uint64_t)(hi - lo + 1));
 }
 
+/* diagnostics entry point (csrc/api.hip, not in admmq.h): the run's launch schedule */
+int32_t admmq_debug_admm_run_schedule(const admmq_problem* probs, int32_t nprob, int32_t num_attempts, int32_t bits,
+                                      int32_t qscheme, int32_t max_iter, int32_t solve_mode, int32_t fused_finalize,
+                                      int32_t has_info, int32_t fin_capacity, int32_t out[16]);
+
 static size_t ws_of(const int (*ir)[2], int n) {
   admmq_problem* p = calloc((size_t)n, sizeof(admmq_problem));
   for (int i = 0; i < n; ++i) { p[i].I = ir[i][0]; p[i].R = ir[i][1]; }
   size_t b = admmq_admm_workspace_size(p, n, 200);
   free(p);
   return b;
+}
+
+/* the search form and the launch schedule of the batch (host code only: the capacity of
+ * the fused finalize is an argument), over the bit widths and candidate counts that take
+ * the merged, per-level and exhaustive forms (24 combinations; a caller with many batches
+ * takes every step-th from `first`); failures counted */
+static int schedules_of(const int (*ir)[2], int n, int first, int step) {
+  static const int bits[4] = {1, 4, 6, 8}, ncand[3] = {1, 200, 1100}, cap[3] = {0, 16, 512};
+  admmq_problem* p = calloc((size_t)n, sizeof(admmq_problem));
+  for (int i = 0; i < n; ++i) { p[i].I = ir[i][0]; p[i].R = ir[i][1]; }
+  int bad = 0;
+  for (int k = first; k < 24; k += step) {
+    int32_t out[16] = {0};
+    const int mse = k < 12;
+    bad += admmq_debug_admm_run_schedule(p, n, ncand[k % 3], bits[k % 4], mse ? ADMMQ_TENSOR_MSEMINMAX_SYMMETRIC
+                                                                             : ADMMQ_TENSOR_MINMAX,
+                                         1 + k % 4, 0, k % 5 != 0, k % 7 != 0, cap[(k / 2) % 3], out) != ADMMQ_OK;
+    bad += out[0] != k % 4 || out[10] < 0 || out[10] > out[15] || (!mse && out[6] != 0);
+  }
+  free(p);
+  return bad;
 }
 
 int main(void) {
@@ -40,6 +67,7 @@ int main(void) {
     size_t b = ws_of((const int(*)[2])ir, 16);
     printf("C3 mode %d: workspace %zu B\n", m, b);
     fails += b == 0;
+    fails += schedules_of((const int(*)[2])ir, 16, 0, 1);
   }
   /* C5: one Llama-7B decoder layer, both modes (the wide-tile plan) */
   static const int ll[7][3] = {{4096, 4096, 1024}, {4096, 4096, 1024}, {4096, 4096, 1024}, {4096, 4096, 1024},
@@ -50,6 +78,7 @@ int main(void) {
     size_t b = ws_of((const int(*)[2])ir, 7);
     printf("C5 mode %d: workspace %zu B\n", m, b);
     fails += b == 0;
+    fails += schedules_of((const int(*)[2])ir, 7, 0, 1);
   }
   /* seeded random batches: thin (I <= 16), 32-row, 64x64 and wide mixes, ragged R */
   size_t tot = 0;
@@ -62,6 +91,7 @@ int main(void) {
     }
     size_t b = ws_of((const int(*)[2])ir, n);
     fails += b == 0;
+    fails += schedules_of((const int(*)[2])ir, n, t % 4, 4);
     tot += b;
   }
   printf("400 random batches: total workspace %zu B\n", tot);
