@@ -17,7 +17,8 @@ packed integer codes of ``--save-packed`` and de-quantizes them on the device.
 Packed layers: ``load_packed_factors`` returns the ``PackedTensor`` factors themselves, and
 the CP builders accept them in place of float tensors: the 1x1 convs / linears then become
 ``PackedConv1x1`` / ``PackedLinear``, which keep the codes and run ``k_packed_gemm`` on them
-(inference only); no float32 copy of such a factor is ever made.
+(inference only); no float32 copy of such a factor is ever made. ``fused=True`` replaces a
+3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``).
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-from .packed import PackedTensor, _meta_words, _weight_dims, load_packed, packed_bytes, packed_gemm
+from .packed import PackedTensor, _meta_words, _pair, _weight_dims, load_packed, packed_bytes, packed_dwgemm, packed_gemm
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -135,7 +136,45 @@ class PackedConv1x1(_PackedWeight):
         return self._gemm(x)
 
 
-def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups):
+class PackedDepthwiseConv1x1(_PackedWeight):
+    """The depthwise ``k x k`` stage and the last 1x1 stage of a 3-way CP layer in one kernel
+    (``k_packed_dwgemm``): ``x [n, R, H, W] -> [n, out, Ho, Wo]``. The weight ``A [out, R]`` stays
+    packed; ``taps`` is a float32 buffer ``[kh kw, R]`` (the de-quantized ``C`` factor as it is:
+    ``k k R`` values). The rank-``R`` tensor between the two stages is never written. Kernel
+    size, stride and padding travel in the extra state beside the weight's quantization."""
+    _layout = 0
+
+    def __init__(self, p: PackedTensor, taps: torch.Tensor, bias: Optional[torch.Tensor] = None, kernel_size=(3, 3),
+                 stride=1, padding=0):
+        super().__init__(p, bias, transpose=False)
+        self.kernel_size, self.stride, self.padding = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), \
+            _pair(padding, "padding")
+        _expect_shape((self.kernel_size[0] * self.kernel_size[1], self.in_features), taps.shape)
+        if taps.dtype != torch.float32:
+            raise TypeError(f"taps must be float32, got {taps.dtype}")
+        self.register_buffer("taps", taps.detach().clone().to(self.codes.device).contiguous())
+
+    def get_extra_state(self):
+        return dict(super().get_extra_state(), kernel_size=list(self.kernel_size), stride=list(self.stride),
+                    padding=list(self.padding))
+
+    def set_extra_state(self, state):
+        if tuple(state["kernel_size"]) != self.kernel_size:
+            raise ValueError(f"packed state with kernel size {tuple(state['kernel_size'])} does not fit this layer "
+                             f"({self.kernel_size})")
+        super().set_extra_state(state)
+        self.stride, self.padding = _pair(state["stride"], "stride"), _pair(state["padding"], "padding")
+
+    def forward(self, x):
+        return packed_dwgemm(self.codes, self._meta, self.out_features, self.in_features, x, self.taps, self.kernel_size,
+                             self.stride, self.padding, self.bias)
+
+    def extra_repr(self):
+        return (f"{super().extra_repr()}, kernel_size={self.kernel_size}, stride={self.stride}, "
+                f"padding={self.padding}")
+
+
+def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups, fused=False):
     if groups != 1:
         raise NotImplementedError("packed CP layers support groups=1 only")
     A, B, C = factors
@@ -143,6 +182,11 @@ def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, strid
     _expect_shape((kernel_size[0] * kernel_size[1], rank), tuple(C.shape))
     _expect_shape((cout, rank, 1, 1), (A.shape[0], A.shape[1], 1, 1))
     dev = C.codes.device
+    if fused:
+        return nn.Sequential(OrderedDict([
+            ('conv1', PackedConv1x1(B, None, transpose=True)),
+            ('conv23', PackedDepthwiseConv1x1(A, C.dequantize(), bias, kernel_size, stride, padding)),
+        ]))
     conv2 = nn.Conv2d(rank, rank, kernel_size=kernel_size, groups=rank, padding=padding, stride=stride, bias=False,
                       device=dev)
     # k k R floats: nothing to save by keeping the depthwise stage packed; frozen like the
@@ -177,11 +221,16 @@ def _packed_cpfc_layer(rank, factors, bias, fin, fout):
 
 
 def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
-                   cout: int, kernel_size: Tuple[int, int], padding, stride, groups: int = 1) -> nn.Sequential:
+                   cout: int, kernel_size: Tuple[int, int], padding, stride, groups: int = 1,
+                   fused: bool = False) -> nn.Sequential:
     """1x1 (cin -> R) -> depthwise kernel_size (R) -> 1x1 (R -> cout); source/models.py:24-51.
-    ``PackedTensor`` factors: conv1 / conv3 become ``PackedConv1x1`` (B transposed, A)."""
+    ``PackedTensor`` factors: conv1 / conv3 become ``PackedConv1x1`` (B transposed, A).
+    ``fused`` (``PackedTensor`` factors only): the layout is ``conv1`` -> ``conv23``, a
+    ``PackedDepthwiseConv1x1`` that runs the depthwise and the last 1x1 stage as one kernel."""
     if _is_packed(factors):
-        return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups)
+        return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups, fused)
+    if fused:
+        raise ValueError("build_cp_layer: fused=True needs PackedTensor factors (the fused stage runs from packed codes)")
     dev = factors[0].device if factors else None
     seq = nn.Sequential(OrderedDict([
         ('conv1', nn.Conv2d(cin, rank, kernel_size=(1, 1), groups=groups, bias=False, device=dev)),
@@ -305,11 +354,14 @@ def load_packed_factors(prefix: str, ndim: int, device=None) -> List[PackedTenso
     return [load_packed(prefix + f"mode_{m}_packed.pt", device=dev) for m in range(ndim)]
 
 
-def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor]) -> nn.Sequential:
-    """The replacement scripts/calibrate.py:157-184 builds for ``conv`` from its factors."""
+def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor], fused: bool = False) -> nn.Sequential:
+    """The replacement scripts/calibrate.py:157-184 builds for ``conv`` from its factors.
+    ``fused``: ``build_cp_layer(..., fused=True)`` for a ``k x k`` conv (``PackedTensor`` factors only)."""
     bias = conv.bias.detach() if conv.bias is not None else None
     if tuple(conv.kernel_size) != (1, 1):
         return build_cp_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.kernel_size,
-                              conv.padding, conv.stride, conv.groups)
+                              conv.padding, conv.stride, conv.groups, fused)
+    if fused:
+        raise ValueError("factorized_conv: fused=True applies to k x k convs (a 1x1 conv has no depthwise stage)")
     return build_cp2conv_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.padding,
                                conv.stride)

@@ -9,6 +9,8 @@ a second guess at the float32 result.
 
 ``packed_linear`` / ``packed_conv1x1`` multiply activations by a weight kept as such codes
 (``k_packed_gemm``: the codes are decoded inside the GEMM, the float32 weight never exists).
+``packed_depthwise_conv1x1`` runs a depthwise ``k x k`` convolution and the 1x1 convolution by
+such a weight as one kernel (``k_packed_dwgemm``: the tensor between them is never written).
 
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
@@ -24,7 +26,7 @@ import torch
 from . import _lib
 
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
-           "packed_gemm", "packed_linear", "packed_conv1x1"]
+           "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -218,6 +220,8 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
     if x.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
                            "under torch.no_grad() or detach x")
+    if torch.compiler.is_compiling():   # (see _opaque_packed_gemm below)
+        return _opaque_packed_gemm(codes, meta_words, transpose, M, K, x, x_layout, bias)
     M, K, x_layout = int(M), int(K), int(x_layout)
     if bias is not None:
         bias = bias.detach()
@@ -259,6 +263,12 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
     return y
 
 
+# Under torch.compile a packed call stays opaque: the meta record is a host tensor (the host picks
+# the kernel from its bits) beside GPU tensors, a mix the tracer's fake-tensor device propagation
+# refuses. The call is a graph break and runs as it does in eager mode; eager calls do not pass here.
+_opaque_packed_gemm = torch.compiler.disable(packed_gemm)
+
+
 def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
     _validate(p.bits, p.qscheme)
     if len(p.shape) != 2:
@@ -292,6 +302,86 @@ def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tens
     if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
         x = x[:, :, ::sh, ::sw]
     return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias)
+
+
+def _pair(v, name: str) -> Tuple[int, int]:
+    if isinstance(v, int):
+        return v, v
+    v = tuple(int(a) for a in v)
+    if len(v) != 2:
+        raise ValueError(f"{name} must be an int or a pair, got {v}")
+    return v
+
+
+def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, x: torch.Tensor, taps: torch.Tensor,
+                  kernel_size, stride=1, padding=0, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Depthwise ``kernel_size`` convolution of ``x [n, K, H, W]`` by ``taps [kh kw, K]`` followed by
+    the 1x1 convolution by the ``[M, K]`` de-quantization of ``codes`` (+ ``bias``), in one kernel
+    (``k_packed_dwgemm``): ``-> [n, M, Ho, Wo]``; the ``K``-channel intermediate is never written.
+    Inference only: an ``x`` that requires grad is refused while grad mode is on."""
+    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda" or \
+            taps.device.type != "cuda":
+        raise RuntimeError("admmq: packed_dwgemm needs its codes, taps and activations on a ROCm GPU (device 'cuda'); "
+                           "the MI355X path has no CPU implementation")
+    _lib.require_device(x)
+    _lib.require_device(taps)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: packed_dwgemm is inference only (no backward through packed weights): call it "
+                           "under torch.no_grad() or detach x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_dwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias)
+    M, K = int(M), int(K)
+    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
+    taps = taps.detach()
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_dwgemm (csrc/torch_ops.cpp) -> admmq_packed_dwgemm
+        return _lib.ops().packed_dwgemm(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias)
+    lib = _lib.load()
+    if x.dim() != 4 or x.shape[1] != K:
+        raise ValueError(f"packed_dwgemm: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    if tuple(taps.shape) != (kh * kw, K):
+        raise ValueError(f"packed_dwgemm: taps must be [{kh * kw}, {K}], got {tuple(taps.shape)}")
+    xc, tc = x.contiguous(), taps.contiguous()
+    if xc.numel() == 0:
+        raise ValueError("packed_dwgemm: empty x")
+    nb, H, W = int(xc.shape[0]), int(xc.shape[2]), int(xc.shape[3])
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    bc = None
+    if bias is not None:
+        _lib.require_device(bias)
+        if tuple(bias.shape) != (M,):
+            raise ValueError(f"packed_dwgemm: bias must be [{M}], got {tuple(bias.shape)}")
+        bc = bias.contiguous()
+    # (a geometry outside the limits leaves Ho / Wo meaningless: the call below refuses it before any launch)
+    Ho = max((H + 2 * ph - kh) // max(sh, 1) + 1, 1)
+    Wo = max((W + 2 * pw - kw) // max(sw, 1) + 1, 1)
+    y = torch.empty((nb, M, Ho, Wo), dtype=torch.float32, device=x.device)
+    nbytes = lib.admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb)
+    ws = _lib.workspace(nbytes, x.device)
+    rc = lib.admmq_packed_dwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), nb, H, W, _lib.ptr(tc), kh, kw,
+                                 sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(),
+                                 _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_dwgemm")
+    return y
+
+
+_opaque_packed_dwgemm = torch.compiler.disable(packed_dwgemm)
+
+
+def packed_depthwise_conv1x1(x: torch.Tensor, taps: torch.Tensor, p: "PackedTensor",
+                             bias: Optional[torch.Tensor] = None, kernel_size=(3, 3), stride=1,
+                             padding=0) -> torch.Tensor:
+    """The last two stages of a 3-way CP layer in one call: ``F.conv2d(z, W[:, :, None, None], bias)`` with
+    ``W = p.dequantize()`` (``[M, K]``) and ``z`` the depthwise ``kernel_size`` convolution of ``x [n, K, H, W]``
+    (``stride``, zero ``padding``) whose kernel of channel ``k`` is ``taps[:, k]`` (``taps [kh kw, K]``: the
+    de-quantized ``C`` factor as it is). ``z`` is formed inside the GEMM's staging and never written; the
+    result has the bits of ``packed_conv1x1`` on a ``z`` summed tap by tap in float32. Inference only."""
+    M, K = _weight_dims(p, False)
+    return packed_dwgemm(p.codes, _meta_words(p), M, K, x, taps, kernel_size, stride, padding, bias)
 
 
 def save_packed(path: str, p) -> None:

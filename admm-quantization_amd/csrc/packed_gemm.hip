@@ -254,6 +254,230 @@ __global__ __launch_bounds__(256) void k_packed_reduce(const float* __restrict__
   y[e] = s;
 }
 
+// Fused depthwise kh x kw + 1x1 stage of a packed CP layer (include/admmq.h "Fused depthwise
+// + 1x1"): k_packed_gemm<BITS, false, false> with the X loader replaced by a
+// stencil. The activation operand Z[k, (b, oh, ow)] = sum_tap taps[tap][k] t[b, k, ih, iw] is
+// formed while the X tile is staged and never exists in memory; the W decode, the K pieces,
+// the fold, the two regimes and the epilogue are those of k_packed_gemm (a kernel of its own,
+// so that the existing instantiations' code does not change).
+struct PgDwArgs {
+  PgArgs g;            // x = t [nb, K, H, W]; N = Ho Wo; C = nb N
+  const float* taps;   // [kh kw][K]
+  long long H, W, HW;
+  int Wo;
+  int kh, kw, sh, sw, ph, pw;
+};
+
+// A thread's column (b, oh, ow) is fixed over the K steps: its first input position, the
+// rows / columns of the window that lie inside the image (two bit masks) and the channel
+// plane it starts in are derived once; a step then advances one pointer by 32 H W. A thread's
+// k within a step is xk + 4 j with xk uniform over the wave, so the tap weights are uniform
+// reads. The tap sum of an element is z = z + w v in tap order from +0.0, product and sum
+// rounded separately; a tap outside the image is skipped (a select), a k past the piece's or
+// K's end reads nothing and yields exactly 0, a column past C reads the clamped column and is
+// zeroed. The sums are formed in the load phase, two taps (16 loads) at a time (kh kw 8 raw
+// values do not fit the register file for the larger windows): the next step's stencil is
+// issued and summed before the current step's 16 MFMAs, the decode and the LDS stores come
+// after them.
+template <int BITS>
+__global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
+  __shared__ float sW[2][kPgBK * kPgLD];
+  __shared__ float sX[2][kPgBK * kPgLD];
+  const PgArgs& a = d.g;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
+  const int M = a.M, K = a.K, N = a.N;
+  const long long C = a.C;
+  const int m0 = (int)blockIdx.y * kPgBM;
+  const long long c0 = (long long)blockIdx.x * kPgBN;
+  const int piece = (int)blockIdx.z;
+  const int kb = a.parallel ? piece * a.kp : 0;
+  const int ke = a.parallel ? min(K, kb + a.kp) : K;
+  const unsigned char* __restrict__ codes = a.codes;
+  const long long nbytes = a.nbytes;
+
+  // W: as k_packed_gemm with trans_w = 0
+  const int wrow = tid >> 2;
+  const int wk = 8 * (tid & 3);
+  const int nvm = m0 + wrow < M ? 8 : 0;
+  const long long bit0 = ((long long)(m0 + wrow) * K + (kb + wk)) * BITS;
+  const int wsh = (int)(bit0 & 31);
+  long long wq = bit0 >> 5;
+  // Z: one column, k = xk + 4 j
+  const int xc = tid & 63;
+  const int xk = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool cok = c0 + xc < C;
+  const int kh = d.kh, kw = d.kw;
+  const long long W = d.W, HW = d.HW;
+  long long tbase;            // element offset of the window's first position in a channel plane (may be negative)
+  unsigned rmask = 0u, cmask = 0u;   // bit a / b: window row a / column b lies inside the image
+  const float* __restrict__ tp;
+  {
+    const long long c = min(c0 + xc, C - 1);
+    const long long b = c / N;
+    const int n = (int)(c - b * N);
+    const int oh = n / d.Wo, ow = n - oh * d.Wo;
+    const long long ih0 = (long long)oh * d.sh - d.ph, iw0 = (long long)ow * d.sw - d.pw;
+    for (int ta = 0; ta < kh; ++ta)
+      if (ih0 + ta >= 0 && ih0 + ta < d.H) rmask |= 1u << ta;
+    for (int tb = 0; tb < kw; ++tb)
+      if (iw0 + tb >= 0 && iw0 + tb < W) cmask |= 1u << tb;
+    tbase = ih0 * W + iw0;
+    tp = a.x + (b * K + (kb + xk)) * HW;
+  }
+  const float* __restrict__ wp = d.taps + (kb + xk);
+  const long long tstep = (long long)kPgBK * HW;
+
+  unsigned cw[3];
+  int nv = 0;
+  float rx[8];
+  auto load = [&](int k0, auto full) {
+    constexpr bool FULL = decltype(full)::value;
+    cw[0] = 0u; cw[1] = 0u; cw[2] = 0u;
+    if (FULL) nv = nvm;
+    else nv = nvm > 0 ? min(8, ke - (k0 + wk)) : 0;
+    if (nv > 0) {
+      if (4 * wq + 12 <= nbytes) {
+        const gcu32* q = (const gcu32*)(codes + 4 * wq);
+        cw[0] = q[0]; cw[1] = q[1]; cw[2] = q[2];
+      } else {
+        cw[0] = code_dword(codes, wq, nbytes);
+        cw[1] = code_dword(codes, wq + 1, nbytes);
+        cw[2] = code_dword(codes, wq + 2, nbytes);
+      }
+    }
+    wq += BITS;
+    const gcf32* tg = (const gcf32*)tp;
+    const gcf32* wg = (const gcf32*)wp;
+    float z[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = 0.f;
+    // two taps at a time: their 16 loads are issued together, then taken whatever the masks
+    // say (the empty asm: the loads stay together and ahead of the selects, instead of one load
+    // and one wait inside a branch per element), then summed in tap order; an odd count's last
+    // pair repeats the last tap with its second half switched off
+    const int ntap = kh * kw;
+    int ta = 0, tb = 0;
+    for (int tap = 0; tap < ntap; tap += 2) {
+      const bool two = tap + 1 < ntap;
+      int ta1 = ta, tb1 = tb;
+      if (two && ++tb1 == kw) { tb1 = 0; ++ta1; }
+      const bool ok0 = ((rmask >> ta) & (cmask >> tb) & 1u) != 0u;
+      const bool ok1 = two && ((rmask >> ta1) & (cmask >> tb1) & 1u) != 0u;
+      const long long off0 = ok0 ? tbase + ta * W + tb : 0;   // outside: the plane's first element, not used
+      const long long off1 = ok1 ? tbase + ta1 * W + tb1 : 0;
+      const gcf32* wt0 = wg + (long long)tap * K;
+      const gcf32* wt1 = wg + (long long)(two ? tap + 1 : tap) * K;
+      float w0[8], w1[8], v0[8], v1[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (FULL) {
+          w0[j] = wt0[4 * j];
+          w1[j] = wt1[4 * j];
+          v0[j] = tg[off0 + (long long)(4 * j) * HW];
+          v1[j] = tg[off1 + (long long)(4 * j) * HW];
+        } else {
+          const bool in = k0 + xk + 4 * j < ke;   // (uniform over the wave)
+          w0[j] = in ? wt0[4 * j] : 0.f;
+          w1[j] = in ? wt1[4 * j] : 0.f;
+          v0[j] = in ? tg[off0 + (long long)(4 * j) * HW] : 0.f;
+          v1[j] = in ? tg[off1 + (long long)(4 * j) * HW] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) asm("" : "+v"(v0[j]), "+v"(v1[j]));
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float s = z[j] + w0[j] * v0[j];
+        z[j] = ok0 ? s : z[j];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float s = z[j] + w1[j] * v1[j];
+        z[j] = ok1 ? s : z[j];
+      }
+      ta = ta1; tb = tb1;
+      if (++tb == kw) { tb = 0; ++ta; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) rx[j] = cok ? z[j] : 0.f;
+    tp += tstep;
+    wp += kPgBK;
+  };
+  auto store = [&](int buf) {
+    constexpr unsigned mask = (1u << BITS) - 1u;
+    const int p2 = wsh + 4 * BITS;
+    const bool up = p2 >= 32;
+    unsigned long long win[2];
+    win[0] = (((unsigned long long)cw[1] << 32) | cw[0]) >> wsh;
+    win[1] = (((unsigned long long)(up ? cw[2] : cw[1]) << 32) | (up ? cw[1] : cw[0])) >> (p2 & 31);
+    float dq[8];
+    if (a.scheme == kMinMax) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        dq[j] = dequant_code((unsigned)(win[j >> 2] >> ((j & 3) * BITS)) & mask, kMinMax, BITS, a.scale, a.zp, a.mn, a.rng);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        dq[j] = dequant_code((unsigned)(win[j >> 2] >> ((j & 3) * BITS)) & mask, kAffine, BITS, a.scale, a.zp, a.mn, a.rng);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sW[buf][(wk + j) * kPgLD + wrow] = j < nv ? dq[j] : 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sX[buf][(xk + 4 * j) * kPgLD + xc] = rx[j];
+  };
+  auto load_step = [&](int k0) {
+    if (k0 + kPgBK <= ke) load(k0, std::true_type{});
+    else load(k0, std::false_type{});
+  };
+
+  pg_f32x16 acc, tot;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { acc[r] = 0.f; tot[r] = 0.f; }
+  bool first = true;
+  int pend = kb + a.kp;
+  load_step(kb);
+  store(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kb; k0 < ke; k0 += kPgBK) {
+    const bool more = k0 + kPgBK < ke;
+    if (more) load_step(k0 + kPgBK);
+    const float* w = sW[buf] + 32 * wm + i;
+    const float* x = sX[buf] + 32 * wn + i;
+#pragma unroll
+    for (int q = 0; q < kPgBK / 2; ++q)
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[(2 * q + h) * kPgLD], x[(2 * q + h) * kPgLD], acc, 0, 0, 0);
+    if (!more || k0 + kPgBK == pend) {
+      pend += a.kp;
+      if (first) {
+        tot = acc;
+        first = false;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tot[r] = tot[r] + acc[r];
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  float* const dst = a.parallel ? a.part + (long long)piece * a.total : a.y;
+  const float* __restrict__ bias = a.parallel ? nullptr : a.bias;
+  const long long c = c0 + 32 * wn + i;
+  if (c >= C) return;
+  const long long b = c / N;
+  const long long ybase = b * M * N + (c - b * N);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = m0 + 32 * wm + PG_ROW(r);
+    if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+  }
+}
+
 struct PgPlan {
   int kp, np, parallel;
   long long tiles_m, tiles_c, C, total;
@@ -342,6 +566,84 @@ int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t
   if (pl.parallel)
     hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
                        pl.total, bias, y, a.M, a.N, a.xl);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
+
+size_t admmq_packed_dwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb) {
+  PgPlan pl;
+  if (Ho <= 0 || Wo <= 0 || Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30)) return 0;
+  if (!plan_packed_gemm(M, K, Ho * Wo, nb, pl)) return 0;
+  return pl.ws;
+}
+
+int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                            int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
+                            int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (!codes || !t || !taps || !y || !meta)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes, meta, t, taps and y must not be NULL");
+  if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: M, K, H, W and nb must be positive");
+  if (meta->bits < 1 || meta->bits > 8) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: meta bits must be 1..8");
+  if (meta->scheme < kMse || meta->scheme > kAffine)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: unknown meta scheme (the four tensor schemes only)");
+  if (meta->scheme == kMinMax && meta->bits == 1)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: tensor_minmax has no 1 bit code");
+  if (meta->bad != 0) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: meta bad != 0: not a valid packed tensor");
+  if (kh < 1 || kh > 7 || kw < 1 || kw > 7) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: kernel size must be 1..7 x 1..7");
+  if (sh < 1 || sw < 1) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: stride must be at least 1");
+  if (ph < 0 || ph >= kh || pw < 0 || pw >= kw)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: padding must be in [0, kernel size)");
+  if (H > (int64_t(1) << 40) || W > (int64_t(1) << 40) || H > (int64_t(1) << 40) / W)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range");
+  if (H + 2 * ph < kh || W + 2 * pw < kw)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: the window does not fit the padded image (Ho, Wo >= 1)");
+  const int64_t Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes must be 16-byte aligned");
+  if (((reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(y) |
+        reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: t, taps, y and bias must be float aligned");
+  PgPlan pl;
+  if (Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30) || !plan_packed_gemm(M, K, Ho * Wo, nb, pl))
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range");
+  const int64_t tmax = (int64_t(1) << 40) - 1;   // nb K H W <= tmax, without overflow
+  if (K > tmax / (H * W) || nb > tmax / (H * W * K))
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range (nb K H W must be below 2^40)");
+  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
+  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: workspace must be float aligned");
+  PgDwArgs d;
+  PgArgs& a = d.g;
+  a.codes = codes; a.x = t; a.bias = bias; a.y = y;
+  a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
+  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
+  a.total = pl.total; a.C = pl.C;
+  a.M = (int)M; a.K = (int)K; a.N = (int)(Ho * Wo);
+  a.xl = 0;
+  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
+  a.scheme = meta->scheme;
+  a.zp = meta->scheme == kAffine ? meta->zero_point : 0;
+  a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
+  d.taps = taps;
+  d.H = H; d.W = W; d.HW = H * W;
+  d.Wo = (int)Wo;
+  d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
+#define ADMMQ_PG_CASE(B) \
+  case B: hipLaunchKernelGGL((k_packed_dwgemm<B>), grid, dim3(256), 0, s, d); break;
+  switch (meta->bits) {
+    ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
+    ADMMQ_PG_CASE(5) ADMMQ_PG_CASE(6) ADMMQ_PG_CASE(7) ADMMQ_PG_CASE(8)
+    default: break;   // (refused above)
+  }
+#undef ADMMQ_PG_CASE
+  if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
+                       pl.total, bias, y, a.M, a.N, 0);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
   return ADMMQ_OK;

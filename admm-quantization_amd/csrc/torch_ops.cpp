@@ -9,6 +9,7 @@
 //   admmq::quantize_packed / dequantize_packed: the packed integer codes of the tensor schemes
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::packed_gemm             a packed weight times float32 activations
+//   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -366,6 +367,79 @@ at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_word
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
 }
 
+// --- packed_dwgemm --------------------------------------------------------------------------
+// The depthwise kh x kw stage (taps [kh kw, K]) and the 1x1 stage by the packed [M, K] weight
+// in one kernel (admmq_packed_dwgemm): x [nb, K, H, W] -> [nb, M, Ho, Wo]. Inference only.
+std::vector<int64_t> packed_dwgemm_shape(const at::Tensor& x, const at::Tensor& taps, int64_t M, int64_t K, int64_t kh,
+                                         int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_dwgemm: M and K must be positive");
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == K, "admmq: packed_dwgemm: x must be [n, ", K, ", H, W], got ", x.sizes());
+  TORCH_CHECK(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "admmq: packed_dwgemm: kernel size must be 1..7 x 1..7");
+  TORCH_CHECK(sh >= 1 && sw >= 1, "admmq: packed_dwgemm: stride must be at least 1");
+  TORCH_CHECK(ph >= 0 && ph < kh && pw >= 0 && pw < kw, "admmq: packed_dwgemm: padding must be in [0, kernel size)");
+  TORCH_CHECK(taps.dim() == 2 && taps.size(0) == kh * kw && taps.size(1) == K, "admmq: packed_dwgemm: taps must be [",
+              kh * kw, ", ", K, "], got ", taps.sizes());
+  const int64_t H = x.size(2), W = x.size(3);
+  TORCH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "admmq: packed_dwgemm: the ", kh, " x ", kw,
+              " window does not fit the padded image of x ", x.sizes());
+  return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
+}
+
+at::Tensor packed_dwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                              const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                              int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias) {
+  check_f32_device(x, "x");
+  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
+              "admmq: packed_dwgemm is inference only (no backward through packed weights): call it under "
+              "torch.no_grad() or detach x");
+  check_f32_device(taps, "taps");
+  check_same_device(taps, x, "taps");
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
+              "admmq: packed_dwgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_same_device(codes, x, "codes");
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
+              "admmq: packed_dwgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  const std::vector<int64_t> oshape = packed_dwgemm_shape(x, taps, M, K, kh, kw, sh, sw, ph, pw);
+  TORCH_CHECK(std::max(sh, sw) <= INT32_MAX && x.size(0) <= INT32_MAX, "admmq: packed_dwgemm: sizes out of range");
+  admmq_qmeta meta;
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_dwgemm: bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_dwgemm: a ", M,
+              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
+              " code bytes, got ", codes.numel());
+  TORCH_CHECK(x.numel() > 0, "admmq: packed_dwgemm: empty x");
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor tc = taps.detach().contiguous();
+  at::Tensor cc = codes.contiguous();
+  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_dwgemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int32_t nb = static_cast<int32_t>(xc.size(0));
+  at::Tensor y = at::empty(oshape, xc.options());
+  const size_t nbytes = admmq_packed_dwgemm_workspace_size(M, K, oshape[2], oshape[3], nb);
+  at::Tensor ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_dwgemm(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<float>(), nb, xc.size(2), xc.size(3),
+                               tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
+                               static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
+                               static_cast<int32_t>(pw), bc.defined() ? bc.data_ptr<float>() : nullptr,
+                               y.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(xc)),
+           "packed_dwgemm");
+  return y;
+}
+
+at::Tensor packed_dwgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                              const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                              int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias) {
+  return at::empty(packed_dwgemm_shape(x, taps, M, K, kh, kw, sh, sw, ph, pw), x.options().dtype(at::kFloat));
+}
+
 // --- quantize_channel (channel_symmetric / channel_affine with an explicit dim) ----------------
 at::Tensor quantize_channel_cuda(const at::Tensor& x, int64_t bits, int64_t qscheme, int64_t dim) {
   check_f32_device(x, "tensor");
@@ -509,6 +583,8 @@ TORCH_LIBRARY(admmq, m) {
   m.def("dequantize_packed(Tensor[] codes, Tensor meta, int[] numel) -> Tensor[]");
   m.def("packed_gemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
         "Tensor? bias=None) -> Tensor");
+  m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
+        "int sw, int ph, int pw, Tensor? bias=None) -> Tensor");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -521,6 +597,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("quantize_packed", &quantize_packed_cuda);
   m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("packed_gemm", &packed_gemm_cuda);
+  m.impl("packed_dwgemm", &packed_dwgemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -532,6 +609,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("quantize_packed", &quantize_packed_meta);
   m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("packed_gemm", &packed_gemm_meta);
+  m.impl("packed_dwgemm", &packed_dwgemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

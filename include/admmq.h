@@ -214,6 +214,37 @@ int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t
                           const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Fused depthwise + 1x1 stage of a packed CP layer: the depthwise kh x kw
+ * convolution (the C factor) and the 1x1 convolution by a packed weight (the A factor) in one
+ * kernel; the rank-K intermediate between them is never written to memory.
+ *   t     [nb, K, H, W] float32, contiguous (the first 1x1 stage's output)
+ *   taps  [kh*kw, K]    float32, row-major (the de-quantized C factor as it is)
+ *   codes, meta         the packed weight D [M, K] (not transposed), as for admmq_packed_gemm
+ *   y     [nb, M, Ho, Wo],  Ho = (H + 2 ph - kh) / sh + 1,  Wo = (W + 2 pw - kw) / sw + 1 (floor)
+ * 1. z starts at +0.0f; for tap = a*kw + b in increasing order
+ *      z = z + taps[tap][k] * t[b_img, k, oh*sh - ph + a, ow*sw - pw + b]
+ *    with the product and the sum rounded separately; a tap whose position lies outside the
+ *    image contributes nothing (for finite inputs: zero padding).
+ * 2. Y[b, m, oh, ow] = sum_k D[m, k] z[b, k, oh, ow] (+ bias[m]) with exactly
+ *    admmq_packed_gemm's arithmetic and order for (M, K, N = Ho*Wo, nb), trans_w = 0,
+ *    x_layout = 0: the same K pieces, fold order (bias last) and regimes. The result has the
+ *    bits of admmq_packed_gemm on a Z formed by step 1, for every nb and on every call.
+ * Limits: 1 <= kh, kw <= 7; sh, sw >= 1; 0 <= ph < kh, 0 <= pw < kw; Ho, Wo >= 1;
+ * admmq_packed_gemm's limits on M, K, nb*Ho*Wo and M*K; nb*K*H*W < 2^40. codes: device,
+ * 16-byte aligned; t, taps, y, bias (may be NULL): device, float aligned. ADMMQ_ERR_ARG for
+ * NULL codes / meta / t / taps / y, non-positive sizes, a bad meta record (as for
+ * admmq_packed_gemm), a kernel size, stride or padding outside the limits, a window that does
+ * not fit the padded image, misaligned pointers, sizes past the limits; ADMMQ_ERR_WORKSPACE
+ * for a short workspace - all before any launch, each with its own admmq_last_error text.
+ * admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb) equals
+ * admmq_packed_gemm_workspace_size(M, K, Ho*Wo, nb) (0 for arguments out of range): the
+ * partial images of the parallel regime only; there is no buffer for Z. */
+size_t admmq_packed_dwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb);
+int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                            int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
+                            int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

@@ -151,6 +151,51 @@ int main(void) {
     fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
     fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, ws, 16, NULL) != ADMMQ_ERR_WORKSPACE;
     fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, NULL, 0, NULL) != ADMMQ_ERR_WORKSPACE;
+    /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
+     * and every refusal before any launch */
+    const float* tp = (const float*)0x18000;
+    for (int t = 0; t < 400; ++t) {
+      const int64_t M = rnd(1, 6000), K = rnd(1, 6000), Ho = rnd(1, t % 3 ? 9 : 70), Wo = rnd(1, t % 3 ? 9 : 70);
+      const int32_t nb = rnd(1, 8);
+      fails += admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb) != admmq_packed_gemm_workspace_size(M, K, Ho * Wo, nb);
+    }
+    fails += admmq_packed_dwgemm_workspace_size(512, 1141, 2, 2, 1) == 0;
+    fails += admmq_packed_dwgemm_workspace_size(8, 8, 0, 4, 1) != 0;
+    fails += admmq_packed_dwgemm_workspace_size(8, 8, 4, -4, 1) != 0;
+    fails += admmq_packed_dwgemm_workspace_size(8, 8, (int64_t)1 << 62, (int64_t)1 << 62, 1) != 0;
+    fails += admmq_packed_dwgemm_workspace_size(8, 8, (int64_t)1 << 20, (int64_t)1 << 20, 1) != 0;
+#define DW(cc, mm, M, K, tt, nb, H, W, pp, kh, kw, sh, sw, ph, pw, yy, wsb) \
+  admmq_packed_dwgemm(cc, mm, M, K, tt, nb, H, W, pp, kh, kw, sh, sw, ph, pw, NULL, yy, ws, wsb, NULL)
+    fails += DW(NULL, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, NULL, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, NULL, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, NULL, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 0, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 0, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 0, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, tp, 0, 3, 1, 1, 0, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 9, 9, tp, 3, 8, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 0, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 3, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, -1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, 2, 6, tp, 5, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c + 4, &qm, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, (const float*)0x10002, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, (int64_t)1 << 41, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, (int64_t)1 << 20, x, 1, 1024, 1024, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 1024, x, 1024, 1024, 1024, tp, 3, 3, 64, 64, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 8, 8, x, 1, INT64_MAX, INT64_MAX, tp, 3, 3, INT32_MAX, INT32_MAX, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.bits = 0;
+    fails += DW(c, &q2, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.scheme = -2;
+    fails += DW(c, &q2, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX; q2.bits = 1;
+    fails += DW(c, &q2, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    q2 = qm; q2.bad = 1;
+    fails += DW(c, &q2, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
+    fails += DW(c, &qm, 512, 1141, x, 1, 2, 2, tp, 3, 3, 1, 1, 1, 1, y, 16) != ADMMQ_ERR_WORKSPACE;
+#undef DW
   }
   printf("last error: %s\n", admmq_last_error());
   printf("%s (%d failures)\n", fails ? "FAIL" : "OK", fails);
