@@ -148,6 +148,8 @@ def load() -> ctypes.CDLL:
         "admmq_set_solve_mode": (I32, [I32]),
         "admmq_get_solve_mode": (I32, []),
         "admmq_debug_set_legacy_stage1": (I32, [I32]),
+        "admmq_debug_set_launch_head": (I32, [I32]),
+        "admmq_debug_get_launch_head_default": (I32, []),
         "admmq_debug_admm_plan_bytes": (S, [P, I32, I32, P]),
         "admmq_debug_admm_plan_digest": (I32, [P, I32, I32, I32, P, P]),
         "admmq_debug_admm_run_schedule": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),

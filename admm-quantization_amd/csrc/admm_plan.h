@@ -54,6 +54,7 @@ struct PlanSwitches {
   int fin_nv3 = 1;        // three float4 groups per search thread where that keeps the finalize fused
   int thin_loop = 1;      // persistent thin loop: 2 = 64-column workgroups wherever allowed
   int hist_reps = 0;      // forced stage-1 units per block of the non-fused search (0: planned)
+  int launch_head = kLaunchHeadDefault;   // kHead* bits (admmq_internal.h): bit 0 fills the tiles' stop-test pointers
 };
 
 // CUs of the chip the device-independent choices are made for (the MI355X's 256): whatever

@@ -483,9 +483,9 @@ static void plan_small_tiles(AdmmPlan& pl) {
   }
 }
 
-// The operands' addresses and strides of every tile (admmq_internal.h GemmTile), and this
-// call's partial images and counters of the parallel K-split pieces
-static void fill_tile_pointers(AdmmPlan& pl) {
+// The operands' addresses and strides of every tile (admmq_internal.h GemmTile), the stop
+// test's inputs (launch-head bit 0), and this call's partial images and counters of the parallel K-split pieces
+static void fill_tile_pointers(AdmmPlan& pl, const PlanSwitches& sw) {
   if (!pl.d_kctr) return;   // a size query carves from a null base: there are no addresses to fill
   std::vector<size_t> ctrbase(pl.desc.size(), 0);   // first counter of each split problem
   size_t n = 0;
@@ -498,6 +498,7 @@ static void fill_tile_pointers(AdmmPlan& pl) {
   for (GemmTile& t : pl.tiles) {
     const ProbDesc& d = pl.desc[t.prob];
     t.U = d.U; t.ld = d.ld; t.ldm = d.ldm;
+    if (sw.launch_head & kHeadGemmStop) { t.flags = d.flags; t.res = d.res; }   // else null: read through the descriptor
     if (d.split) {   // the fp16 planes keep the fp32 rows' strides (in floats)
       t.P = reinterpret_cast<const float*>(d.P2); t.M = reinterpret_cast<const float*>(d.M2);
       t.eP = d.eP; t.eM = d.eM;
@@ -526,7 +527,7 @@ static void plan_gemm_tiles(AdmmPlan& pl, const PlanSwitches& sw, int ncu) {
     plan_small_tiles(pl);
     pl.ntiles_small = (int)pl.tiles.size() - pl.ntiles_wide - pl.ntiles_big;
   }
-  fill_tile_pointers(pl);
+  fill_tile_pointers(pl, sw);
 }
 
 // thin factors: one solve workgroup per 32 columns (thin_loop.hip), longest rows first;

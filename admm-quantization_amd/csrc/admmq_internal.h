@@ -134,14 +134,29 @@ struct DqBatch {
 // arrival counter: gemm_kernels.hip ksplit_combine) or serial (one workgroup runs the whole
 // tile and folds its accumulator into the running sum at each of the ser - 1 piece starts).
 struct GemmTile {
-  int prob, tm, tn, first, nk, bm;   // bm: tile rows of the persistent fp32 kernel (k_gemm_f32p), else 0
+  int prob, tm, tn, nk;
+  int ld, ldm;
+  signed char first;                 // 1: the problem's first tile (zeroes the search accumulators, sets the stop flag)
+  unsigned char bm;                  // tile rows of the persistent fp32 kernel (k_gemm_f32p), else 0
+  short k0;                          // K-split, parallel form: first K-step, pieces, this piece (np = 1: whole tile);
+  signed char np, pc, ser, pad_;     // serial form: pieces folded in this workgroup (1: none)
   const float* P; const float* M; const float* U;
   const int* eP; const int* eM;
-  int ld, ldm;
-  int k0, np, pc, ser;               // K-split: parallel form: first K-step, pieces, this piece (np = 1: whole tile);
-                                     // serial form: pieces folded in this workgroup (1: none)
   float* part; unsigned* ctr;        // K-split: the tile's partial images [np][16 KB] and arrival counter
+  // The stop test's inputs (the problem's flags and residual sums), so that the kernel can
+  // load them beside the first stages instead of behind a read of the problem descriptor;
+  // null: the kernel reads them through the descriptor (launch-head bit 0 off). The small
+  // fields above are narrow so that the record keeps its 104 bytes (the workspace carve).
+  const int* flags; const double* res;
 };
+static_assert(sizeof(GemmTile) == 104, "GemmTile: the workspace carve depends on its size");
+// Launch-head forms (admmq_debug_set_launch_head; same bits either way):
+// which of a launch's first dependent loads are taken off the chain kernel start -> work
+// unit -> descriptor -> data. (Bit 1, the search launch's jobs by value in its kernel
+// arguments, was measured slower and removed; bit 2 is not built: DESIGN.md §8.2.)
+constexpr int kHeadGemmStop = 1;     // solve GEMM: the stop test's inputs from the tile record, decided at the first K-step's wait
+constexpr int kLaunchHeadAll = kHeadGemmStop;
+constexpr int kLaunchHeadDefault = kLaunchHeadAll;
 constexpr int kKsplitMax = 4;        // pieces per tile at most
 constexpr int kKsplitMinSteps = 6;   // K-steps per piece at least
 // Thin-factor solve workgroup (thin_loop.hip): columns [col0, col0 + cw) of problem `job`,
@@ -262,6 +277,7 @@ size_t hist3_lds_bytes(int ncand, int bits);
 int copy_hist_trace(unsigned long long* host, int n);
 int copy_gemm_trace(unsigned long long* host, int n);
 int copy_gemm_trace2(unsigned long long* host, int n);
+int copy_gemm_trace3(unsigned long long* host, int n);
 int copy_gemm_simd(unsigned* host, int n);
 int copy_setup_trace(unsigned long long* host, int n);
 int copy_fin_trace(unsigned long long* host, int n);

@@ -169,6 +169,8 @@ static std::atomic<int> g_ksplit_par{1};
 // Balance (admm_plan.hip ksplit_balance): on / off, and the price of a parallel piece in K-steps
 static std::atomic<int> g_ksplit_bal{1};
 static std::atomic<int> g_ksplit_cost{1};
+// Launch-head forms (admmq_internal.h kHead* bits; same bits either way)
+static std::atomic<int> g_launch_head{kLaunchHeadDefault};
 
 // The planner's inputs among the switches, read once per entry-point call
 static PlanSwitches plan_switches() {
@@ -186,6 +188,7 @@ static PlanSwitches plan_switches() {
   sw.fin_nv3 = g_fin_nv3.load();
   sw.thin_loop = g_thin_loop.load();
   sw.hist_reps = g_hist_reps.load();
+  sw.launch_head = g_launch_head.load();
   return sw;
 }
 // The run's inputs among the switches, read once per entry-point call. thin_loop: the
@@ -612,6 +615,16 @@ int32_t admmq_debug_set_f32_persistent(int32_t kernel, int32_t rule) {
   return ADMMQ_OK;
 }
 
+// diagnostics (not in include/admmq.h): which launch heads take their first loads off the
+// descriptor chain (kHead* bits, admmq_internal.h; default kLaunchHeadDefault, 0 = the
+// descriptor-chain heads; same bits either way)
+int32_t admmq_debug_set_launch_head(int32_t mask) {
+  if (mask < 0 || (mask & ~kLaunchHeadAll)) return fail(ADMMQ_ERR_ARG, "launch head mask out of range");
+  g_launch_head = mask;
+  return ADMMQ_OK;
+}
+int32_t admmq_debug_get_launch_head_default(void) { return kLaunchHeadDefault; }
+
 // diagnostics (not in include/admmq.h): 1 = per-level stage 1, 0 = merged thresholds
 int32_t admmq_debug_set_legacy_stage1(int32_t enable) {
   g_legacy_stage1 = enable != 0;
@@ -890,6 +903,7 @@ int32_t admmq_debug_admm_run_schedule(const admmq_problem* probs, int32_t nprob,
 int32_t admmq_debug_hist_trace(unsigned long long* host, int32_t n) { return copy_hist_trace(host, n); }
 int32_t admmq_debug_gemm_trace(unsigned long long* host, int32_t n) { return copy_gemm_trace(host, n); }
 int32_t admmq_debug_gemm_trace2(unsigned long long* host, int32_t n) { return copy_gemm_trace2(host, n); }
+int32_t admmq_debug_gemm_trace3(unsigned long long* host, int32_t n) { return copy_gemm_trace3(host, n); }
 int32_t admmq_debug_gemm_simd(unsigned* host, int32_t n) { return copy_gemm_simd(host, n); }
 int32_t admmq_debug_setup_trace(unsigned long long* host, int32_t n) { return copy_setup_trace(host, n); }
 int32_t admmq_debug_fin_trace(unsigned long long* host, int32_t n) { return copy_fin_trace(host, n); }

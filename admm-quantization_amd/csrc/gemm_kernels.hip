@@ -34,6 +34,7 @@
 // Epilogue: store HT (split: scaled back by ldexp), and fold max|X|, min X, max X of
 // X = HT - U over the valid region into the problem's per-iteration stat slot.
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
@@ -63,6 +64,76 @@ __device__ __forceinline__ bool converged_before(const ProbDesc& p, int slot_pre
   const double rr = t[0] / t[1];
   const double ss = t[2] / t[3];
   return (rr < (double)eps) && (ss < (double)eps);
+}
+
+// A tile record by scalar loads (constant address space: the table is uploaded before the
+// run and only read by the launches). The record's narrow fields are unpacked from their
+// two dwords, made opaque so that the compiler does not narrow them back into vector byte
+// loads with a wait of their own.
+__device__ __forceinline__ GemmTile load_tile(const GemmTile* __restrict__ tiles, int idx) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef __attribute__((address_space(4))) const int cint;
+  static_assert(offsetof(GemmTile, first) == 24 && offsetof(GemmTile, k0) == 26 && offsetof(GemmTile, np) == 28 &&
+                    offsetof(GemmTile, ser) == 30, "GemmTile's packed fields");
+  struct Words { int w[sizeof(GemmTile) / 4]; } raw;
+  cint* src = (cint*)(tiles + idx);
+#pragma unroll
+  for (int k = 0; k < (int)(sizeof(GemmTile) / 4); ++k) raw.w[k] = src[k];
+  int w0 = raw.w[6], w1 = raw.w[7];
+  asm("" : "+s"(w0), "+s"(w1));
+  GemmTile t = __builtin_bit_cast(GemmTile, raw);
+  t.first = (signed char)(w0 & 0xFF); t.bm = (unsigned char)((w0 >> 8) & 0xFF); t.k0 = (short)(w0 >> 16);
+  t.np = (signed char)(w1 & 0xFF); t.pc = (signed char)((w1 >> 8) & 0xFF); t.ser = (signed char)((w1 >> 16) & 0xFF);
+  return t;
+#else
+  return tiles[idx];
+#endif
+}
+// The same test with its inputs taken from the tile record (GemmTile::flags / res,
+// launch-head bit 0) and loaded ahead of the decision: stop_load goes out beside the first
+// stages (wave-uniform addresses: scalar loads, outside the ring's vmcnt accounting), and
+// stop_test - the sums, divisions and comparisons of converged_before in the same order -
+// runs once the first stage has landed, by when these have too. Returns 0 go on, 1 the
+// problem had stopped before, 2 it stops now (the first tile then sets the sticky flag).
+struct StopIn { int flag; double r[4 * kResRep]; };
+__device__ __forceinline__ void stop_load(const GemmTile& tl, int slot_prev, int iter, StopIn& si) {
+  // through the constant address space: wave-uniform addresses, so these are scalar loads
+  // whatever the compiler knows about the pointers (a flat load would also count in lgkmcnt
+  // and vmcnt). The residual sums were written by the previous launch; the flag changes
+  // under this launch only 0 -> 1, by a tile whose own test gives what this one's gives.
+  typedef __attribute__((address_space(4))) const int cint;
+  typedef __attribute__((address_space(4))) const double cdouble;
+  si.flag = *(cint*)tl.flags;
+  if (iter != 0) {
+    cdouble* r = (cdouble*)tl.res + 4 * kResRep * slot_prev;
+#pragma unroll
+    for (int q = 0; q < 4 * kResRep; ++q) si.r[q] = r[q];
+  }
+  asm volatile("" ::: "memory");   // issued here, not sunk to the test
+}
+// ... and kept unread until the stages are out: an empty asm "rewrites" the loaded values
+// after the stage issue, so the compiler cannot start on the sums (and wait for the loads)
+// before it
+__device__ __forceinline__ void stop_hold(StopIn& si, int iter) {
+  asm volatile("" : "+s"(si.flag));
+  if (iter != 0) {
+#pragma unroll
+    for (int q = 0; q < 4 * kResRep; q += 8)
+      asm volatile("" : "+s"(si.r[q]), "+s"(si.r[q + 1]), "+s"(si.r[q + 2]), "+s"(si.r[q + 3]), "+s"(si.r[q + 4]),
+                        "+s"(si.r[q + 5]), "+s"(si.r[q + 6]), "+s"(si.r[q + 7]));
+  }
+}
+__device__ __forceinline__ int stop_test(const StopIn& si, int iter, float eps) {
+  if (si.flag != 0) return 1;
+  if (iter == 0) return 0;
+  double t[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < kResRep; ++q)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] += si.r[4 * q + k];
+  const double rr = t[0] / t[1];
+  const double ss = t[2] / t[3];
+  return ((rr < (double)eps) && (ss < (double)eps)) ? 2 : 0;
 }
 
 // 16 B per lane global -> LDS (global_load_lds_dwordx4): LDS bytes [lds + 16 lane, +16).
@@ -171,6 +242,13 @@ int copy_gemm_trace2(unsigned long long* host, int n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_trace2), (size_t)n * 2 * sizeof(unsigned long long)) == hipSuccess
              ? n : -1;
 }
+// ... and per workgroup the end of its head: the first K-step's stage has landed and the stop
+// test is decided (k_gemm_f32b; the head is this minus the start)
+__device__ unsigned long long g_gemm_trace3[kGemmTraceMax];
+int copy_gemm_trace3(unsigned long long* host, int n) {
+  n = n < kGemmTraceMax ? n : kGemmTraceMax;
+  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_trace3), (size_t)n * sizeof(unsigned long long)) == hipSuccess ? n : -1;
+}
 // ... and per workgroup the set of SIMDs its waves ran on (bit per SIMD id, k_gemm_f32b)
 __device__ unsigned g_gemm_simd[kGemmTraceMax];
 int copy_gemm_simd(unsigned* host, int n) {
@@ -229,7 +307,7 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
 
   const unsigned long long T0 = ADMMQ_NOW();
   const unsigned long long C0 = ADMMQ_TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
-  const GemmTile tl = tiles[blockIdx.x];
+  const GemmTile tl = load_tile(tiles, blockIdx.x);
   if (tl.nk <= 0) return;   // grid padding (order_tiles_for_cus)
   const ProbDesc& p = probs[tl.prob];
   const int ld = tl.ld, ldm = tl.ldm;
@@ -282,14 +360,28 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
 #define ADMMQ_ISSUE(s, kt)                                                                                      \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                                                              \
     blds16(8 * (wave * GPW + j) < BM ? rsA : rsB, stp[s] + (wave * GPW + j) * 256, voff[j], (kt) * (BK * 4))
-  // the first NS-1 stages go out before the stop test, whose inputs (flag, residual
-  // sums) are one dependent read further away; a stopped problem drains them unused
+  // the first NS-1 stages go out before the stop test; a stopped problem drains them unused
+  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
+  // of the stages, one dependent level after the tile record like the stages themselves,
+  // and the test waits for the first stage first (the first K-step's own wait)
+  const bool early = tl.flags != nullptr;
+  StopIn si;
+  if (early) stop_load(tl, slot ^ 1, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip = p.flags[0] != 0;
-  if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-    if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = true;
+  bool skip;
+  if (early) {
+    wait_vmcnt<GPW * (NS - 2)>();
+    stop_hold(si, iter);
+    const int st = stop_test(si, iter, eps);
+    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+    skip = st != 0;
+  } else {
+    skip = p.flags[0] != 0;
+    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
+      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+      skip = true;
+    }
   }
   if (skip) {
     wait_vmcnt<0>();   // the speculative stage loads land before the wave ends
@@ -538,12 +630,27 @@ __device__ __forceinline__ void f32_tile(const ProbDesc* __restrict__ probs, con
 #define ADMMQ_ISSUE(s, kt)                                                 \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                         \
     glds16(src[j] + (kt) * BK, stp[s] + (wave * GPW + j) * 256)
+  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
+  // of the stages, one dependent level after the tile record like the stages themselves,
+  // and the test waits for the first stage first (the first K-step's own wait)
+  const bool early = tl.flags != nullptr;
+  StopIn si;
+  if (early) stop_load(tl, slot ^ 1, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip = p.flags[0] != 0;
-  if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-    if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = true;
+  bool skip;
+  if (early) {
+    wait_vmcnt<GPW * (NS - 2)>();
+    stop_hold(si, iter);
+    const int st = stop_test(si, iter, eps);
+    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+    skip = st != 0;
+  } else {
+    skip = p.flags[0] != 0;
+    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
+      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+      skip = true;
+    }
   }
   if (skip) {
     wait_vmcnt<0>();   // the speculative stage loads land before the stages are reused
@@ -669,7 +776,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
   __shared__ unsigned red[3][4];
   const int t1 = list_off[blockIdx.x + 1];
   for (int t = list_off[blockIdx.x]; t < t1; ++t) {
-    const GemmTile tl = tiles[t];
+    const GemmTile tl = load_tile(tiles, t);
     if (tl.bm == 128) f32_tile<128, NS>(probs, tl, slot, iter, eps, ncand, stp, red);
     else if (tl.bm == 64) f32_tile<64, NS>(probs, tl, slot, iter, eps, ncand, stp, red);
     else f32_tile<32, NS>(probs, tl, slot, iter, eps, ncand, stp, red);
@@ -693,7 +800,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
   __shared__ __attribute__((aligned(16))) float st3[NS > 3 ? STAGE : 4];
   float* const stp[4] = {st0, st1, st2, st3};
   __shared__ unsigned red[3][4];
-  const GemmTile tl = tiles[blockIdx.x];
+  const GemmTile tl = load_tile(tiles, blockIdx.x);
   if (tl.nk <= 0) return;   // grid padding (order_tiles_for_cus)
   if (tl.bm == 128) f32_tile<128, NS>(probs, tl, slot, iter, eps, ncand, stp, red);
   else if (tl.bm == 64) f32_tile<64, NS>(probs, tl, slot, iter, eps, ncand, stp, red);
@@ -740,7 +847,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
   const int aoff = (32 * wm + i) * 32, boff = (BM + 32 * wn + i) * 32;
   const unsigned long long T0 = ADMMQ_NOW();
   const unsigned long long C0 = ADMMQ_TRACE ? __builtin_amdgcn_s_memtime() : 0ull;
-  const GemmTile tl = tiles[blockIdx.x];
+  const GemmTile tl = load_tile(tiles, blockIdx.x);
   if (tl.nk <= 0) return;   // grid padding (order_tiles_for_cus)
   if (ADMMQ_TRACE && blockIdx.x < kGemmTraceMax) {   // (uniform over the workgroup)
     if (tid == 0) g_gemm_simd[blockIdx.x] = 0u;
@@ -778,16 +885,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
 #define ADMMQ_ISSUE(s, kt)                                                                            \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                                                    \
     blds16(rs, stp[s] + (wave * GPW + j) * 256, voff[j], (kt) * (BK * 4))
+  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
+  // of the stages, one dependent level after the tile record like the stages themselves,
+  // and the test waits for the first stage first (the first K-step's own wait)
+  const bool early = tl.flags != nullptr;
+  StopIn si;
+  if (early) stop_load(tl, slot ^ 1, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip = p.flags[0] != 0;
-  if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-    if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = true;
+  bool skip;
+  if (early) {
+    wait_vmcnt<GPW * (NS - 2)>();
+    stop_hold(si, iter);
+    const int st = stop_test(si, iter, eps);
+    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+    skip = st != 0;
+  } else {
+    skip = p.flags[0] != 0;
+    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
+      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
+      skip = true;
+    }
   }
   if (skip) {
-    wait_vmcnt<0>();
+    wait_vmcnt<0>();   // the speculative stage loads land before the wave ends
     return;
+  }
+  unsigned long long TH = 0ull;
+  if (ADMMQ_TRACE) {   // the head's end: the wait the first K-step is about to make, made here
+    wait_vmcnt<GPW * (NS - 2)>();
+    TH = ADMMQ_NOW();
   }
   if (tl.first) {   // this iteration's quantizer-search accumulators start at zero
     unsigned long long* sse = p.mv.sse + (size_t)slot * ncand;
@@ -865,6 +992,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
     if (ADMMQ_TRACE && tid == 0 && blockIdx.x < kGemmTraceMax) {
       g_gemm_trace2[blockIdx.x][0] = TK;
       g_gemm_trace2[blockIdx.x][1] = ADMMQ_NOW();
+      g_gemm_trace3[blockIdx.x] = TH;
       if (!go) {   // a piece that did not complete its tile: {start, end, info | 1 << 63}
         g_gemm_trace[blockIdx.x][0] = T0;
         g_gemm_trace[blockIdx.x][3] = __builtin_amdgcn_s_memtime() - C0;
@@ -879,6 +1007,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
   } else if (ADMMQ_TRACE && tid == 0 && blockIdx.x < kGemmTraceMax) {
     g_gemm_trace2[blockIdx.x][0] = TK;
     g_gemm_trace2[blockIdx.x][1] = TK;
+    g_gemm_trace3[blockIdx.x] = TH;
   }
   if constexpr (!PRE) load_u();
   unsigned amax = 0u, mn = 0xFFFFFFFFu, mxo = 0u;

@@ -22,6 +22,7 @@ ap.add_argument("--mode", type=int, default=0)
 ap.add_argument("--iters", type=int, default=4)
 ap.add_argument("--shapes", default="", help="I:R,I:R,... instead of the resnet18 factors of --mode")
 ap.add_argument("--ksplit-form", type=int, default=1)
+ap.add_argument("--launch-head", type=int, default=-1, help="admmq_debug_set_launch_head mask (-1: the library's default)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)
@@ -36,6 +37,8 @@ for I, R in shapes:
     U = torch.zeros(I, R, device=dev)
     probs.append((H, U, F, G))
 _lib.check(_lib.load().admmq_debug_set_ksplit_form(a.ksplit_form), "ksplit_form")
+if a.launch_head >= 0:
+    _lib.check(_lib.load().admmq_debug_set_launch_head(a.launch_head), "launch_head")
 admm_iteration_batched(probs, a.iters, 0.0, 4, "tensor_mseminmax_symmetric", check_spd=False)
 torch.cuda.synchronize()
 lib = _lib.load()
@@ -143,6 +146,32 @@ if lib.admmq_debug_gemm_trace2(buf2, n) > 0:
           [round(tails[int(q * (len(tails) - 1))], 2) for q in (0, 0.1, 0.5, 0.9, 1.0)])
     print("CU last K-loop end (us) percentiles 0/10/50/90/100:",
           [round(lastk[int(q * (len(lastk) - 1))], 1) for q in (0, 0.1, 0.5, 0.9, 1.0)])
+
+# head: kernel start to the first K-step ready (its stage landed, the stop test decided;
+# k_gemm_f32b TRACE builds), per tile, per tile of the launch's first round (the tiles that
+# start within 1 us of the launch: later ones start on a busy CU) and per CU (its first tile)
+fn3 = getattr(lib, "admmq_debug_gemm_trace3", None)
+if fn3 is not None:
+    fn3.restype = ctypes.c_int32
+    buf3 = (ctypes.c_ulonglong * 8192)()
+    if fn3(buf3, 8192) > 0:
+        def pct(v):
+            v = sorted(v)
+            return [round(v[int(q * (len(v) - 1))], 2) for q in (0, 0.1, 0.5, 0.9, 1.0)]
+        heads = [(buf3[r[0]] - r[1]) / 100 for r in recs if buf3[r[0]] >= r[1]]
+        first = [(buf3[r[0]] - r[1]) / 100 for r in recs if buf3[r[0]] >= r[1] and (r[1] - t0) < 100]
+        cu_head = []
+        for k, v in cus.items():
+            x = min(v, key=lambda r: r[1])
+            if buf3[x[0]] >= x[1]:
+                cu_head.append((buf3[x[0]] - t0) / 100)
+        if heads:
+            print("tile head, start -> first K-step ready (us) percentiles 0/10/50/90/100:", pct(heads), "n", len(heads))
+        if first:
+            print("  ... tiles of the first round:", pct(first), "n", len(first), " mean", round(statistics.mean(first), 3))
+        if cu_head:
+            print("CU head, launch start -> its first tile's first K-step ready (us):", pct(cu_head),
+                  " mean", round(statistics.mean(cu_head), 3))
 
 # SIMDs each workgroup's four waves ran on (k_gemm_f32b TRACE builds): a CU's 1..3 resident
 # tiles put their waves on distinct SIMDs, or do some share one?

@@ -19,6 +19,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--mode", type=int, default=0)
 ap.add_argument("--iters", type=int, default=4)
 ap.add_argument("--shapes", default="", help="I:R,I:R,... instead of the resnet18 factors of --mode")
+ap.add_argument("--launch-head", type=int, default=-1, help="admmq_debug_set_launch_head mask (-1: the library's default)")
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 g = torch.Generator().manual_seed(0)
@@ -32,6 +33,8 @@ for I, R in shapes:
     H = torch.randn(I, R, generator=g).to(dev) * 0.1
     U = torch.zeros(I, R, device=dev)
     probs.append((H, U, F, G))
+if a.launch_head >= 0:
+    _lib.check(_lib.load().admmq_debug_set_launch_head(a.launch_head), "launch_head")
 admm_iteration_batched(probs, a.iters, 0.0, 4, "tensor_mseminmax_symmetric", check_spd=False)
 torch.cuda.synchronize()
 lib = _lib.load()
