@@ -16,7 +16,7 @@ Compute runs in libadmmq.so (hand-written HIP for gfx950) through a C ABI
 (include/admmq.h); there is no CPU fallback.
 """
 from .admm import admm_iteration, admm_iteration_batched, init_factors, init_factors_many, squared_relative_diff  # noqa: F401
-from .quantization import quantize_tensor, quantize_tensor_mse, min_max_quantize, quantize_batched  # noqa: F401
+from .quantization import quantize_tensor, quantize_tensor_mse, min_max_quantize, fixed_quantize, quantize_batched  # noqa: F401
 from .packed import PackedTensor, quantize_packed, dequantize_packed, save_packed, load_packed  # noqa: F401
 from .packed import packed_linear, packed_conv1x1, packed_depthwise_conv1x1  # noqa: F401
 from .utils import unfold  # noqa: F401

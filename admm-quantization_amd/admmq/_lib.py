@@ -59,6 +59,11 @@ class QMeta(ctypes.Structure):
                 ("index", ctypes.c_int32), ("bad", ctypes.c_int32)]
 
 
+class ActQ(ctypes.Structure):
+    """admmq_actq (include/admmq.h): a fixed-range activation quantizer, 16 bytes; ``on`` = 0: none."""
+    _fields_ = [("bits", ctypes.c_int32), ("on", ctypes.c_int32), ("mn", ctypes.c_float), ("rng", ctypes.c_float)]
+
+
 class CpLayer(ctypes.Structure):
     _fields_ = [("W", ctypes.c_void_p), ("factors", ctypes.c_void_p * 3), ("G", ctypes.c_void_p),
                 ("F", ctypes.c_void_p), ("dims", ctypes.c_int32 * 3), ("ndim", ctypes.c_int32),
@@ -139,6 +144,10 @@ def load() -> ctypes.CDLL:
         "admmq_packed_gemm": (I32, [P, P, I32, I64, I64, P, I32, I64, I32, P, P, P, S, P]),
         "admmq_packed_dwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),
         "admmq_packed_dwgemm": (I32, [P, P, I64, I64, P, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, S, P]),
+        "admmq_fixed_quantize": (I32, [P, P, I64, P, P]),
+        "admmq_packed_gemm_act": (I32, [P, P, I32, I64, I64, P, I32, I64, I32, P, P, P, P, S, P]),
+        "admmq_packed_dwgemm_act": (I32, [P, P, I64, I64, P, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P,
+                                          S, P]),
         "admmq_mse_sse_table": (I32, [P, I64, I64, I32, I32, P, P, S, P]),
         "admmq_quantize_channel_workspace_size": (S, [P, I32, I32]),
         "admmq_quantize_channel": (I32, [P, P, P, I32, I32, I32, I32, P, S, P]),

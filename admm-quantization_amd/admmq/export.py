@@ -29,6 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
+from . import _lib
 from .packed import PackedTensor, _meta_words, _pair, _weight_dims, load_packed, packed_bytes, packed_dwgemm, packed_gemm
 
 
@@ -64,6 +65,7 @@ class _PackedWeight(nn.Module):
         self.out_features, self.in_features = _weight_dims(p, self.transpose)
         self.register_buffer("codes", p.codes.detach().clone().contiguous())
         self._set_quant(p)
+        self._act = None   # output quantizer: (bits, mn, rng) as resolved float32 values, or None
         if bias is not None:
             _expect_shape((self.out_features,), bias.shape)
             self.bias = nn.Parameter(bias.detach().clone().to(self.codes.device).contiguous(), requires_grad=False)
@@ -86,8 +88,26 @@ class _PackedWeight(nn.Module):
         w = self.packed().dequantize()
         return w.T.contiguous() if self.transpose else w
 
+    @staticmethod
+    def _resolve_act(bits, min_val, max_val):
+        if bits is None:
+            return None
+        from .quantization import act_range, act_record
+        mn, rng = act_range(min_val, max_val)
+        act_record(bits, mn, rng)   # (refuses bits outside 1..24)
+        return (int(bits), mn, rng)
+
+    @staticmethod
+    def _act_arg(a):
+        return None if a is None else _lib.ActQ(a[0], 1, a[1], a[2])
+
+    def set_activation_quant(self, bits=None, min_val=None, max_val=None):
+        """The fixed-range quantizer of the layer's output, applied in the kernel's epilogue
+        (``min_max_quantize(y, bits, min_val, max_val)``'s bits); ``None`` clears it."""
+        self._act = self._resolve_act(bits, min_val, max_val)
+
     def get_extra_state(self):
-        return dict(self._q, transpose=self.transpose)
+        return dict(self._q, transpose=self.transpose, act=list(self._act) if self._act else None)
 
     def set_extra_state(self, state):
         q = {k: state[k] for k in ("shape", "bits", "qscheme", "scale", "zero_point", "mn", "rng", "index")}
@@ -99,14 +119,19 @@ class _PackedWeight(nn.Module):
         self._set_quant(PackedTensor(codes=self.codes, shape=tuple(q["shape"]), bits=int(q["bits"]), qscheme=q["qscheme"],
                                      scale=float(q["scale"]), zero_point=int(q["zero_point"]), mn=float(q["mn"]),
                                      rng=float(q["rng"]), index=int(q["index"])))
+        a = state.get("act")   # (absent in states written before the quantizers existed: none)
+        self._act = (int(a[0]), float(a[1]), float(a[2])) if a else None
 
     def _gemm(self, x):
         return packed_gemm(self.codes, self._meta, self.transpose, self.out_features, self.in_features, x, self._layout,
-                           self.bias)
+                           self.bias, self._act_arg(self._act))
+
+    def _act_repr(self):
+        return "" if self._act is None else f", act=(bits={self._act[0]}, mn={self._act[1]}, rng={self._act[2]})"
 
     def extra_repr(self):
         return (f"{self.in_features}, {self.out_features}, bits={self._q['bits']}, qscheme={self._q['qscheme']}, "
-                f"transpose={self.transpose}, bias={self.bias is not None}")
+                f"transpose={self.transpose}, bias={self.bias is not None}{self._act_repr()}")
 
 
 class PackedLinear(_PackedWeight):
@@ -153,10 +178,16 @@ class PackedDepthwiseConv1x1(_PackedWeight):
         if taps.dtype != torch.float32:
             raise TypeError(f"taps must be float32, got {taps.dtype}")
         self.register_buffer("taps", taps.detach().clone().to(self.codes.device).contiguous())
+        self._mid_act = None   # quantizer of the depthwise stage's output (the reference's behind conv2)
+
+    def set_mid_activation_quant(self, bits=None, min_val=None, max_val=None):
+        """The fixed-range quantizer of the depthwise stage's output, applied as the kernel stages
+        it (the tile's padding stays 0); ``None`` clears it."""
+        self._mid_act = self._resolve_act(bits, min_val, max_val)
 
     def get_extra_state(self):
         return dict(super().get_extra_state(), kernel_size=list(self.kernel_size), stride=list(self.stride),
-                    padding=list(self.padding))
+                    padding=list(self.padding), mid_act=list(self._mid_act) if self._mid_act else None)
 
     def set_extra_state(self, state):
         if tuple(state["kernel_size"]) != self.kernel_size:
@@ -164,17 +195,54 @@ class PackedDepthwiseConv1x1(_PackedWeight):
                              f"({self.kernel_size})")
         super().set_extra_state(state)
         self.stride, self.padding = _pair(state["stride"], "stride"), _pair(state["padding"], "padding")
+        a = state.get("mid_act")
+        self._mid_act = (int(a[0]), float(a[1]), float(a[2])) if a else None
 
     def forward(self, x):
         return packed_dwgemm(self.codes, self._meta, self.out_features, self.in_features, x, self.taps, self.kernel_size,
-                             self.stride, self.padding, self.bias)
+                             self.stride, self.padding, self.bias, self._act_arg(self._act), self._act_arg(self._mid_act))
 
     def extra_repr(self):
+        m = "" if self._mid_act is None else \
+            f", mid_act=(bits={self._mid_act[0]}, mn={self._mid_act[1]}, rng={self._mid_act[2]})"
         return (f"{super().extra_repr()}, kernel_size={self.kernel_size}, stride={self.stride}, "
-                f"padding={self.padding}")
+                f"padding={self.padding}{m}")
 
 
-def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups, fused=False):
+def _stage_acts(act_quant, n, who):
+    """``act_quant`` as a list of ``n`` entries ``(bits, min_val, max_val)`` or ``None`` (``None``: no quantizers)."""
+    if act_quant is None:
+        return [None] * n
+    acts = list(act_quant)
+    if len(acts) != n:
+        raise ValueError(f"{who}: act_quant needs {n} entries (one per unfused stage, None for none), got {len(acts)}")
+    return acts
+
+
+def _with_act(module, act):
+    """A packed stage with its epilogue quantizer set."""
+    if act is not None:
+        module.set_activation_quant(*act)
+    return module
+
+
+def _wrap_fixed(name, module, act):
+    """A float stage followed by a ``FixedQuant`` of the entry's range, laid out as ``add_quant`` does."""
+    if act is None:
+        return module
+    from .actquant import add_quant
+    from .quantization import act_range
+    mn, rng = act_range(act[1], act[2])
+    return add_quant(name, module, 'fixed', bits=int(act[0]), zero_point=mn, scope=rng, min_max=(act[1], act[2]))
+
+
+def _wrap_all(seq, acts):
+    for (name, m), a in zip(list(seq.named_children()), acts):
+        setattr(seq, name, _wrap_fixed(name, m, a))
+    return seq
+
+
+def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups, fused=False, acts=(None,) * 3):
     if groups != 1:
         raise NotImplementedError("packed CP layers support groups=1 only")
     A, B, C = factors
@@ -183,9 +251,12 @@ def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, strid
     _expect_shape((cout, rank, 1, 1), (A.shape[0], A.shape[1], 1, 1))
     dev = C.codes.device
     if fused:
+        conv23 = _with_act(PackedDepthwiseConv1x1(A, C.dequantize(), bias, kernel_size, stride, padding), acts[2])
+        if acts[1] is not None:
+            conv23.set_mid_activation_quant(*acts[1])
         return nn.Sequential(OrderedDict([
-            ('conv1', PackedConv1x1(B, None, transpose=True)),
-            ('conv23', PackedDepthwiseConv1x1(A, C.dequantize(), bias, kernel_size, stride, padding)),
+            ('conv1', _with_act(PackedConv1x1(B, None, transpose=True), acts[0])),
+            ('conv23', conv23),
         ]))
     conv2 = nn.Conv2d(rank, rank, kernel_size=kernel_size, groups=rank, padding=padding, stride=stride, bias=False,
                       device=dev)
@@ -194,41 +265,46 @@ def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, strid
     conv2.weight = nn.Parameter(C.dequantize().reshape(*kernel_size, rank).permute(2, 0, 1)[:, None].contiguous(),
                                 requires_grad=False)
     return nn.Sequential(OrderedDict([
-        ('conv1', PackedConv1x1(B, None, transpose=True)),
-        ('conv2', conv2),
-        ('conv3', PackedConv1x1(A, bias, transpose=False)),
+        ('conv1', _with_act(PackedConv1x1(B, None, transpose=True), acts[0])),
+        ('conv2', _wrap_fixed('conv2', conv2, acts[1])),
+        ('conv3', _with_act(PackedConv1x1(A, bias, transpose=False), acts[2])),
     ]))
 
 
-def _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride):
+def _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride, acts=(None,) * 2):
     A, B = factors
     _expect_shape((rank, cin, 1, 1), (B.shape[1], B.shape[0], 1, 1))
     _expect_shape((cout, rank, 1, 1), (A.shape[0], A.shape[1], 1, 1))
     return nn.Sequential(OrderedDict([
-        ('conv1', PackedConv1x1(B, None, transpose=True, stride=stride, padding=padding)),
-        ('conv2', PackedConv1x1(A, bias, transpose=False)),
+        ('conv1', _with_act(PackedConv1x1(B, None, transpose=True, stride=stride, padding=padding), acts[0])),
+        ('conv2', _with_act(PackedConv1x1(A, bias, transpose=False), acts[1])),
     ]))
 
 
-def _packed_cpfc_layer(rank, factors, bias, fin, fout):
+def _packed_cpfc_layer(rank, factors, bias, fin, fout, acts=(None,) * 2):
     B, A = factors
     _expect_shape((rank, fin), (A.shape[1], A.shape[0]))
     _expect_shape((fout, rank), tuple(B.shape))
     return nn.Sequential(OrderedDict([
-        ('fc1', PackedLinear(A, None, transpose=True)),
-        ('fc2', PackedLinear(B, bias, transpose=False)),
+        ('fc1', _with_act(PackedLinear(A, None, transpose=True), acts[0])),
+        ('fc2', _with_act(PackedLinear(B, bias, transpose=False), acts[1])),
     ]))
 
 
 def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
                    cout: int, kernel_size: Tuple[int, int], padding, stride, groups: int = 1,
-                   fused: bool = False) -> nn.Sequential:
+                   fused: bool = False, act_quant=None) -> nn.Sequential:
     """1x1 (cin -> R) -> depthwise kernel_size (R) -> 1x1 (R -> cout); source/models.py:24-51.
     ``PackedTensor`` factors: conv1 / conv3 become ``PackedConv1x1`` (B transposed, A).
     ``fused`` (``PackedTensor`` factors only): the layout is ``conv1`` -> ``conv23``, a
-    ``PackedDepthwiseConv1x1`` that runs the depthwise and the last 1x1 stage as one kernel."""
+    ``PackedDepthwiseConv1x1`` that runs the depthwise and the last 1x1 stage as one kernel.
+    ``act_quant``: ``[conv1, conv2, conv3]`` entries ``(bits, min_val, max_val)`` or ``None`` (as
+    ``admmq.actquant.collect`` returns them): packed stages quantize in their epilogue (fused:
+    ``conv2``'s entry is ``conv23``'s mid quantizer, ``conv3``'s its output quantizer); a float
+    stage is followed by a ``FixedQuant`` the way ``add_quant`` lays it out."""
+    acts = _stage_acts(act_quant, 3, "build_cp_layer")
     if _is_packed(factors):
-        return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups, fused)
+        return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups, fused, acts)
     if fused:
         raise ValueError("build_cp_layer: fused=True needs PackedTensor factors (the fused stage runs from packed codes)")
     dev = factors[0].device if factors else None
@@ -253,15 +329,16 @@ def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: O
             if bias is not None:
                 _expect(seq.conv3.bias, bias)
                 seq.conv3.bias = _param(bias)
-    return seq
+    return _wrap_all(seq, acts)
 
 
 def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
-                        cout: int, padding, stride) -> nn.Sequential:
+                        cout: int, padding, stride, act_quant=None) -> nn.Sequential:
     """1x1 (cin -> R, with the original padding/stride) -> 1x1 (R -> cout); source/models.py:54-77.
     ``PackedTensor`` factors: both stages become ``PackedConv1x1`` (B transposed, A)."""
+    acts = _stage_acts(act_quant, 2, "build_cp2conv_layer")   # [conv1, conv2], as build_cp_layer's
     if _is_packed(factors):
-        return _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride)
+        return _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride, acts)
     dev = factors[0].device if factors else None
     seq = nn.Sequential(OrderedDict([
         ('conv1', nn.Conv2d(cin, rank, kernel_size=(1, 1), padding=padding, stride=stride, bias=False, device=dev)),
@@ -279,15 +356,16 @@ def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bi
             if bias is not None:
                 _expect(seq.conv2.bias, bias)
                 seq.conv2.bias = _param(bias)
-    return seq
+    return _wrap_all(seq, acts)
 
 
 def build_cpfc_layer(rank: int, factors: Sequence[torch.Tensor], bias: Optional[torch.Tensor], fin: int,
-                     fout: int) -> nn.Sequential:
+                     fout: int, act_quant=None) -> nn.Sequential:
     """Linear fin -> R (A^T) -> Linear R -> fout (B); source/models.py:80-99 (factors = [B, A]).
     ``PackedTensor`` factors: both stages become ``PackedLinear`` (A transposed, B)."""
+    acts = _stage_acts(act_quant, 2, "build_cpfc_layer")   # [fc1, fc2], as build_cp_layer's
     if _is_packed(factors):
-        return _packed_cpfc_layer(rank, factors, bias, fin, fout)
+        return _packed_cpfc_layer(rank, factors, bias, fin, fout, acts)
     B, A = factors
     seq = nn.Sequential(OrderedDict([
         ('fc1', nn.Linear(fin, rank, bias=False, device=A.device)),
@@ -354,14 +432,15 @@ def load_packed_factors(prefix: str, ndim: int, device=None) -> List[PackedTenso
     return [load_packed(prefix + f"mode_{m}_packed.pt", device=dev) for m in range(ndim)]
 
 
-def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor], fused: bool = False) -> nn.Sequential:
+def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor], fused: bool = False,
+                    act_quant=None) -> nn.Sequential:
     """The replacement scripts/calibrate.py:157-184 builds for ``conv`` from its factors.
     ``fused``: ``build_cp_layer(..., fused=True)`` for a ``k x k`` conv (``PackedTensor`` factors only)."""
     bias = conv.bias.detach() if conv.bias is not None else None
     if tuple(conv.kernel_size) != (1, 1):
         return build_cp_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.kernel_size,
-                              conv.padding, conv.stride, conv.groups, fused)
+                              conv.padding, conv.stride, conv.groups, fused, act_quant)
     if fused:
         raise ValueError("factorized_conv: fused=True applies to k x k convs (a 1x1 conv has no depthwise stage)")
     return build_cp2conv_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.padding,
-                               conv.stride)
+                               conv.stride, act_quant)

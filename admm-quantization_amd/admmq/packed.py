@@ -208,11 +208,14 @@ def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
 
 
 def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int, x: torch.Tensor,
-                x_layout: int, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                x_layout: int, bias: Optional[torch.Tensor] = None, act=None) -> torch.Tensor:
     """``Y = W X (+ bias)`` with ``W`` the ``[M, K]`` de-quantization of ``codes`` (``transpose``: of the
     ``[K, M]`` packed tensor's transpose). ``meta_words``: the 8 int32 words of the meta record on
     the CPU. ``x_layout`` 0: ``x [n, K, ...] -> [n, M, ...]``; 1: ``x [..., K] -> [..., M]``.
-    Inference only: an ``x`` that requires grad is refused while grad mode is on."""
+    ``act = (bits, min_val, max_val)``: the fixed-range activation quantizer of ``min_max_quantize``
+    applied to the output inside the kernel (``admmq_packed_gemm_act``): the bits of quantizing the
+    result in a launch of its own. Inference only: an ``x`` that requires grad is refused while grad
+    mode is on."""
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda":
         raise RuntimeError("admmq: packed_gemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
                            "the MI355X path has no CPU implementation")
@@ -221,10 +224,13 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
         raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
                            "under torch.no_grad() or detach x")
     if torch.compiler.is_compiling():   # (see _opaque_packed_gemm below)
-        return _opaque_packed_gemm(codes, meta_words, transpose, M, K, x, x_layout, bias)
+        return _opaque_packed_gemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act)
     M, K, x_layout = int(M), int(K), int(x_layout)
     if bias is not None:
         bias = bias.detach()
+    oq = _act_record(act)
+    if oq is not None and _lib.use_ops():   # torch.ops.admmq.packed_gemm_act -> admmq_packed_gemm_act
+        return _lib.ops().packed_gemm_act(codes, meta_words, bool(transpose), M, K, x, x_layout, bias, oq.bits, oq.mn, oq.rng)
     if _lib.use_ops():   # torch.ops.admmq.packed_gemm (csrc/torch_ops.cpp) -> admmq_packed_gemm
         return _lib.ops().packed_gemm(codes, meta_words, bool(transpose), M, K, x, x_layout, bias)
     lib = _lib.load()
@@ -257,10 +263,26 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
     y = torch.empty(oshape, dtype=torch.float32, device=x.device)
     nbytes = lib.admmq_packed_gemm_workspace_size(M, K, N, nb)
     ws = _lib.workspace(nbytes, x.device)
+    if oq is not None:
+        rc = lib.admmq_packed_gemm_act(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc),
+                                       x_layout, N, nb, _lib.ptr(bc), _lib.ptr(y), ctypes.byref(oq), _lib.ptr(ws),
+                                       ws.numel(), _lib.stream_handle(x.device))
+        _lib.check(rc, "packed_gemm_act")
+        return y
     rc = lib.admmq_packed_gemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc), x_layout, N,
                                nb, _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
     _lib.check(rc, "packed_gemm")
     return y
+
+
+def _act_record(act):
+    """``None`` or the C record of ``act = (bits, min_val, max_val)`` (the range by ``act_range``); a
+    record is taken as it is."""
+    if act is None or isinstance(act, _lib.ActQ):
+        return act
+    from .quantization import act_range, act_record
+    bits, lo, hi = act
+    return act_record(bits, *act_range(lo, hi))
 
 
 # Under torch.compile a packed call stays opaque: the meta record is a host tensor (the host picks
@@ -283,15 +305,15 @@ def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
 
 
 def packed_linear(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
-                  transpose: bool = False) -> torch.Tensor:
+                  transpose: bool = False, act=None) -> torch.Tensor:
     """``F.linear(x, W, bias)`` with ``W = p.dequantize()`` (``transpose``: its transpose) computed
     from the codes: ``x [..., K] -> [..., M]``. Inference only."""
     M, K = _weight_dims(p, transpose)
-    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias)
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias, act)
 
 
 def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None, transpose: bool = False,
-                   stride=1) -> torch.Tensor:
+                   stride=1, act=None) -> torch.Tensor:
     """``F.conv2d(x, W[:, :, None, None], bias, stride=stride)`` with ``W = p.dequantize()``
     (``transpose``: its transpose) computed from the codes: ``x [n, K, H, W] -> [n, M, H', W']``.
     The stride sub-samples ``x`` (a 1x1 kernel without padding commutes with it). Inference only."""
@@ -301,7 +323,7 @@ def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tens
     sh, sw = (stride, stride) if isinstance(stride, int) else tuple(stride)
     if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
         x = x[:, :, ::sh, ::sw]
-    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias)
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias, act)
 
 
 def _pair(v, name: str) -> Tuple[int, int]:
@@ -314,10 +336,13 @@ def _pair(v, name: str) -> Tuple[int, int]:
 
 
 def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, x: torch.Tensor, taps: torch.Tensor,
-                  kernel_size, stride=1, padding=0, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  kernel_size, stride=1, padding=0, bias: Optional[torch.Tensor] = None, act=None,
+                  mid_act=None) -> torch.Tensor:
     """Depthwise ``kernel_size`` convolution of ``x [n, K, H, W]`` by ``taps [kh kw, K]`` followed by
     the 1x1 convolution by the ``[M, K]`` de-quantization of ``codes`` (+ ``bias``), in one kernel
     (``k_packed_dwgemm``): ``-> [n, M, Ho, Wo]``; the ``K``-channel intermediate is never written.
+    ``mid_act`` / ``act = (bits, min_val, max_val)``: fixed-range quantizers of the depthwise stage's
+    output (applied as it is staged; padding stays 0) and of the result (``admmq_packed_dwgemm_act``).
     Inference only: an ``x`` that requires grad is refused while grad mode is on."""
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda" or \
             taps.device.type != "cuda":
@@ -329,12 +354,17 @@ def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
         raise RuntimeError("admmq: packed_dwgemm is inference only (no backward through packed weights): call it "
                            "under torch.no_grad() or detach x")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
-        return _opaque_packed_dwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias)
+        return _opaque_packed_dwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act)
     M, K = int(M), int(K)
     (kh, kw), (sh, sw), (ph, pw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
     taps = taps.detach()
     if bias is not None:
         bias = bias.detach()
+    oq, mq = _act_record(act), _act_record(mid_act)
+    if (oq is not None or mq is not None) and _lib.use_ops():   # torch.ops.admmq.packed_dwgemm_act
+        m3 = (mq.bits, mq.mn, mq.rng) if mq is not None else (0, 0.0, 0.0)
+        o3 = (oq.bits, oq.mn, oq.rng) if oq is not None else (0, 0.0, 0.0)
+        return _lib.ops().packed_dwgemm_act(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias, *m3, *o3)
     if _lib.use_ops():   # torch.ops.admmq.packed_dwgemm (csrc/torch_ops.cpp) -> admmq_packed_dwgemm
         return _lib.ops().packed_dwgemm(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias)
     lib = _lib.load()
@@ -362,6 +392,14 @@ def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     y = torch.empty((nb, M, Ho, Wo), dtype=torch.float32, device=x.device)
     nbytes = lib.admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb)
     ws = _lib.workspace(nbytes, x.device)
+    if oq is not None or mq is not None:
+        rc = lib.admmq_packed_dwgemm_act(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), nb, H, W, _lib.ptr(tc), kh,
+                                         kw, sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y),
+                                         ctypes.byref(mq) if mq is not None else None,
+                                         ctypes.byref(oq) if oq is not None else None, _lib.ptr(ws), ws.numel(),
+                                         _lib.stream_handle(x.device))
+        _lib.check(rc, "packed_dwgemm_act")
+        return y
     rc = lib.admmq_packed_dwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), nb, H, W, _lib.ptr(tc), kh, kw,
                                  sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(),
                                  _lib.stream_handle(x.device))
@@ -374,14 +412,14 @@ _opaque_packed_dwgemm = torch.compiler.disable(packed_dwgemm)
 
 def packed_depthwise_conv1x1(x: torch.Tensor, taps: torch.Tensor, p: "PackedTensor",
                              bias: Optional[torch.Tensor] = None, kernel_size=(3, 3), stride=1,
-                             padding=0) -> torch.Tensor:
+                             padding=0, act=None, mid_act=None) -> torch.Tensor:
     """The last two stages of a 3-way CP layer in one call: ``F.conv2d(z, W[:, :, None, None], bias)`` with
     ``W = p.dequantize()`` (``[M, K]``) and ``z`` the depthwise ``kernel_size`` convolution of ``x [n, K, H, W]``
     (``stride``, zero ``padding``) whose kernel of channel ``k`` is ``taps[:, k]`` (``taps [kh kw, K]``: the
     de-quantized ``C`` factor as it is). ``z`` is formed inside the GEMM's staging and never written; the
     result has the bits of ``packed_conv1x1`` on a ``z`` summed tap by tap in float32. Inference only."""
     M, K = _weight_dims(p, False)
-    return packed_dwgemm(p.codes, _meta_words(p), M, K, x, taps, kernel_size, stride, padding, bias)
+    return packed_dwgemm(p.codes, _meta_words(p), M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act)
 
 
 def save_packed(path: str, p) -> None:

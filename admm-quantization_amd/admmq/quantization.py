@@ -21,14 +21,16 @@ oracle.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["quantize_tensor", "quantize_channel", "quantize_tensor_mse", "min_max_quantize", "quantize_batched", "get_tensor_stats",
-           "mse_sse_table"]
+__all__ = ["quantize_tensor", "quantize_channel", "quantize_tensor_mse", "min_max_quantize", "fixed_quantize",
+           "quantize_batched", "get_tensor_stats", "mse_sse_table", "act_range", "act_record"]
 
 
 def _scheme_code(qscheme: str, dim=None) -> int:
@@ -97,7 +99,6 @@ def quantize_channel(tensor: torch.Tensor, bits: int, qscheme: str, dim: int) ->
     x = tensor.contiguous()
     if _lib.use_ops():
         return _lib.ops().quantize_channel(x, int(bits), code, int(dim))
-    import ctypes
     lib = _lib.load()
     nd = x.dim()
     d = dim + nd if dim < 0 else dim
@@ -140,12 +141,68 @@ def quantize_tensor_mse(x: torch.Tensor, bits: int, num_attempts: int = 200) -> 
     return quantize_batched([x], bits, "tensor_mseminmax_symmetric", num_attempts=num_attempts)[0]
 
 
+def _bound(v):
+    """A bound as (value, is_tensor): a Python number, or a one-element tensor (a GPU tensor is
+    read here: one host sync)."""
+    if isinstance(v, torch.Tensor):
+        if v.numel() != 1:
+            raise ValueError(f"a range bound must be a number or a one-element tensor, got shape {tuple(v.shape)}")
+        return v.detach().reshape(()).item(), True
+    return float(v), False
+
+
+def act_range(min_val, max_val):
+    """``(mn, rng)`` of a fixed range as float32 values, by the type rule torch applies in
+    ``source/quantization.py:58``: two tensors subtract in float32; two Python numbers subtract
+    in double and the difference is rounded once; a tensor and a number both become float32
+    first and subtract in float32. ``mn`` is ``min_val`` as float32 in every case."""
+    (lo, lo_t), (hi, hi_t) = _bound(min_val), _bound(max_val)
+    with np.errstate(all="ignore"):
+        mn = np.float32(lo)
+        rng = np.float32(hi - lo) if not (lo_t or hi_t) else np.float32(np.float32(hi) - mn)
+    return float(mn), float(rng)
+
+
+def act_record(bits: int, mn: float, rng: float) -> "_lib.ActQ":
+    """The C record of a quantizer (``bits`` 1..24: ``2^bits - 1`` is exact in float32)."""
+    bits = int(bits)
+    if not 1 <= bits <= 24:
+        raise ValueError(f"activation quantizer bits must be 1..24, got {bits}")
+    return _lib.ActQ(bits, 1, float(mn), float(rng))
+
+
+def _fixed(input: torch.Tensor, bits: int, mn: float, rng: float) -> torch.Tensor:
+    q = act_record(bits, mn, rng)
+    _lib.require_device(input)
+    x = input.detach().contiguous()
+    y = torch.empty_like(x)
+    if x.numel() == 0:
+        return y
+    if _lib.use_ops():   # torch.ops.admmq.fixed_quantize (csrc/torch_ops.cpp) -> admmq_fixed_quantize
+        return _lib.ops().fixed_quantize(x, q.bits, q.mn, q.rng)
+    _lib.check(_lib.load().admmq_fixed_quantize(_lib.ptr(x), _lib.ptr(y), x.numel(), ctypes.byref(q),
+                                                _lib.stream_handle(x.device)), "fixed_quantize")
+    return y
+
+
+def fixed_quantize(input: torch.Tensor, bits: int, zero_point, scope) -> torch.Tensor:
+    """source/quantization.py:147-161 on the device (``k_fixed_quant``): ``zero_point`` and ``scope``
+    are numbers or one-element tensors (a GPU tensor costs one host sync). No clamp; inference only."""
+    (zp, _), (sc, _) = _bound(zero_point), _bound(scope)
+    with np.errstate(all="ignore"):
+        return _fixed(input, bits, float(np.float32(zp)), float(np.float32(sc)))
+
+
 def min_max_quantize(input: torch.Tensor, bits: int, min_val=None, max_val=None) -> torch.Tensor:
-    """source/quantization.py:48-66 (explicit min_val/max_val are not on the hot path)."""
+    """source/quantization.py:48-66. With either bound ``None`` both come from the input (the
+    ``tensor_minmax`` path). Otherwise the range is fixed: the bounds are Python numbers or
+    one-element tensors (``act_range`` gives the type rule; a GPU tensor bound costs one host
+    sync) and the input is quantized by ``k_fixed_quant``."""
     assert bits >= 1, bits
-    if min_val is not None or max_val is not None:
-        raise NotImplementedError("min_max_quantize with explicit range is outside the ADMM hot path")
-    return quantize_batched([input], bits, "tensor_minmax")[0]
+    if min_val is None or max_val is None:
+        return quantize_batched([input], bits, "tensor_minmax")[0]
+    mn, rng = act_range(min_val, max_val)
+    return _fixed(input, bits, mn, rng)
 
 
 def get_tensor_stats(tensor: torch.Tensor, qscheme: str, mode=0):

@@ -55,6 +55,12 @@ struct PgArgs {
   float scale, mn, rng;
 };
 
+// Output quantizer: the quantized instantiations take the same record with the
+// quantizer behind it, so the plain ones keep their arguments and their code.
+struct PgArgsQ : PgArgs {
+  ActQ oq;
+};
+
 // C/D map of v_mfma_f32_32x32x2_f32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #define PG_ROW(r) (((r) & 3) + 8 * ((r) >> 2) + 4 * h)
 
@@ -63,8 +69,10 @@ struct PgArgs {
 // keeps one dword index and adds a constant; X is read through one pointer plus 8 fixed
 // offsets. FULL steps (all 32 k inside the piece) load without k tests; columns past C read
 // a clamped (valid) address and are zeroed by a select, not a branch.
-template <int BITS, bool TRANS, bool XL>
-__global__ __launch_bounds__(256) void k_packed_gemm(const PgArgs a) {
+// OQ: the serial form's epilogue stores fixed_quant(tot (+ bias)) (the parallel form quantizes
+// in k_packed_reduce_q and runs the plain kernel).
+template <int BITS, bool TRANS, bool XL, bool OQ = false>
+__global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ, PgArgsQ, PgArgs> a) {
   __shared__ float sW[2][kPgBK * kPgLD];
   __shared__ float sX[2][kPgBK * kPgLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -227,7 +235,11 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const PgArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const long long c = c0 + 32 * wn + PG_ROW(r);
-      if (c < C) dst[c * M + m] = bias ? tot[r] + bv : tot[r];
+      if constexpr (OQ) {
+        if (c < C) dst[c * M + m] = fixed_quant(bias ? tot[r] + bv : tot[r], a.oq);
+      } else {
+        if (c < C) dst[c * M + m] = bias ? tot[r] + bv : tot[r];
+      }
     }
   } else {    // lanes along the columns: Y[(b M + m) N + n]
     const long long c = c0 + 32 * wn + i;
@@ -237,7 +249,11 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const PgArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int m = m0 + 32 * wm + PG_ROW(r);
-      if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+      if constexpr (OQ) {
+        if (m < M) dst[ybase + (long long)m * N] = fixed_quant(bias ? tot[r] + bias[m] : tot[r], a.oq);
+      } else {
+        if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+      }
     }
   }
 }
@@ -254,6 +270,18 @@ __global__ __launch_bounds__(256) void k_packed_reduce(const float* __restrict__
   y[e] = s;
 }
 
+// k_packed_reduce with the output quantizer behind the bias (a kernel of its own: the plain one keeps its code)
+__global__ __launch_bounds__(256) void k_packed_reduce_q(const float* __restrict__ part, int np, long long total,
+                                                         const float* __restrict__ bias, float* __restrict__ y, int M,
+                                                         int N, int xl, const ActQ oq) {
+  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  float s = part[e];
+  for (int p = 1; p < np; ++p) s = s + part[(long long)p * total + e];
+  if (bias) s = s + bias[xl ? e % M : (e / N) % M];
+  y[e] = fixed_quant(s, oq);
+}
+
 // Fused depthwise kh x kw + 1x1 stage of a packed CP layer (include/admmq.h "Fused depthwise
 // + 1x1"): k_packed_gemm<BITS, false, false> with the X loader replaced by a
 // stencil. The activation operand Z[k, (b, oh, ow)] = sum_tap taps[tap][k] t[b, k, ih, iw] is
@@ -268,6 +296,11 @@ struct PgDwArgs {
   int kh, kw, sh, sw, ph, pw;
 };
 
+// Quantized forms, as PgArgsQ: the plain record first, the quantizers behind it
+struct PgDwArgsQ : PgDwArgs {
+  ActQ mq, oq;
+};
+
 // A thread's column (b, oh, ow) is fixed over the K steps: its first input position, the
 // rows / columns of the window that lie inside the image (two bit masks) and the channel
 // plane it starts in are derived once; a step then advances one pointer by 32 H W. A thread's
@@ -279,8 +312,23 @@ struct PgDwArgs {
 // values do not fit the register file for the larger windows): the next step's stencil is
 // issued and summed before the current step's 16 MFMAs, the decode and the LDS stores come
 // after them.
-template <int BITS>
-__global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
+// QM bit 0: the mid quantizer - an element of Z becomes fixed_quant(z) as it is staged. Only
+// real elements: a column past C, a k past the piece's or K's end (and with it the zero fill of
+// a partial step) stay exactly 0 - q(0) is not 0 unless 0 lies on the grid, and a quantized
+// padding element would enter every output of the tile. QM bit 1: the output quantizer in the
+// serial form's epilogue, as k_packed_gemm's OQ.
+// PG_DW_CALL: the quantized forms' larger load / store bodies would otherwise stay calls with
+// their captures in scratch; the plain form's calls are written as they were.
+#define PG_DW_CALL(call)             \
+  do {                               \
+    if constexpr (QM != 0) {         \
+      [[clang::always_inline]] call; \
+    } else {                         \
+      call;                          \
+    }                                \
+  } while (0)
+template <int BITS, int QM = 0>
+__global__ __launch_bounds__(256) void k_packed_dwgemm(const std::conditional_t<QM != 0, PgDwArgsQ, PgDwArgs> d) {
   __shared__ float sW[2][kPgBK * kPgLD];
   __shared__ float sX[2][kPgBK * kPgLD];
   const PgArgs& a = d.g;
@@ -331,6 +379,7 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
   unsigned cw[3];
   int nv = 0;
   float rx[8];
+  [[maybe_unused]] unsigned zreal = 0u;   // (mid quantizer) bit j: rx[j] is an element of Z, not padding
   auto load = [&](int k0, auto full) {
     constexpr bool FULL = decltype(full)::value;
     cw[0] = 0u; cw[1] = 0u; cw[2] = 0u;
@@ -401,6 +450,10 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) rx[j] = cok ? z[j] : 0.f;
+    if constexpr ((QM & 1) != 0) {   // the step's real elements, for store()
+      const int nk = FULL ? 8 : (ke - (k0 + xk) + 3) >> 2;   // js with k0 + xk + 4 j < ke
+      zreal = cok ? (nk >= 8 ? 0xFFu : (nk > 0 ? (1u << nk) - 1u : 0u)) : 0u;
+    }
     tp += tstep;
     wp += kPgBK;
   };
@@ -424,11 +477,18 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) sW[buf][(wk + j) * kPgLD + wrow] = j < nv ? dq[j] : 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) sX[buf][(xk + 4 * j) * kPgLD + xc] = rx[j];
+    for (int j = 0; j < 8; ++j) {
+      if constexpr ((QM & 1) != 0) {   // quantized here, after the step's MFMAs: the load phase keeps its registers
+        const float zq = fixed_quant(rx[j], d.mq);
+        sX[buf][(xk + 4 * j) * kPgLD + xc] = ((zreal >> j) & 1u) ? zq : 0.f;
+      } else {
+        sX[buf][(xk + 4 * j) * kPgLD + xc] = rx[j];
+      }
+    }
   };
   auto load_step = [&](int k0) {
-    if (k0 + kPgBK <= ke) load(k0, std::true_type{});
-    else load(k0, std::false_type{});
+    if (k0 + kPgBK <= ke) PG_DW_CALL(load(k0, std::true_type{}));
+    else PG_DW_CALL(load(k0, std::false_type{}));
   };
 
   pg_f32x16 acc, tot;
@@ -436,13 +496,13 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
   for (int r = 0; r < 16; ++r) { acc[r] = 0.f; tot[r] = 0.f; }
   bool first = true;
   int pend = kb + a.kp;
-  load_step(kb);
-  store(0);
+  PG_DW_CALL(load_step(kb));
+  PG_DW_CALL(store(0));
   __syncthreads();
   int buf = 0;
   for (int k0 = kb; k0 < ke; k0 += kPgBK) {
     const bool more = k0 + kPgBK < ke;
-    if (more) load_step(k0 + kPgBK);
+    if (more) PG_DW_CALL(load_step(k0 + kPgBK));
     const float* w = sW[buf] + 32 * wm + i;
     const float* x = sX[buf] + 32 * wn + i;
 #pragma unroll
@@ -460,7 +520,7 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     }
-    if (more) store(buf ^ 1);
+    if (more) PG_DW_CALL(store(buf ^ 1));
     __syncthreads();
     buf ^= 1;
   }
@@ -474,9 +534,15 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const PgDwArgs d) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int m = m0 + 32 * wm + PG_ROW(r);
-    if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+    if constexpr ((QM & 2) != 0) {
+      if (m < M) dst[ybase + (long long)m * N] = fixed_quant(bias ? tot[r] + bias[m] : tot[r], d.oq);
+    } else {
+      if (m < M) dst[ybase + (long long)m * N] = bias ? tot[r] + bias[m] : tot[r];
+    }
   }
 }
+
+#undef PG_DW_CALL
 
 struct PgPlan {
   int kp, np, parallel;
@@ -502,6 +568,19 @@ static bool plan_packed_gemm(int64_t M, int64_t K, int64_t N, int64_t nb, PgPlan
   return true;
 }
 
+// The kernels' form of a caller's quantizer; false for none (NULL or on == 0). bits checked by the caller.
+static bool actq_on(const admmq_actq* q) { return q && q->on != 0; }
+static bool actq_bits_ok(const admmq_actq* q) { return !actq_on(q) || (q->bits >= 1 && q->bits <= 24); }
+
+static int32_t packed_gemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                               const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                               const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream);
+static int32_t packed_dwgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                                 int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
+                                 int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
+                                 const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
 }  // namespace admmq
 
 using namespace admmq;
@@ -517,6 +596,23 @@ size_t admmq_packed_gemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t
 int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
                           const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
                           void* workspace, size_t workspace_bytes, void* stream) {
+  return packed_gemm_run(codes, meta, trans_w, M, K, x, x_layout, N, nb, bias, y, nullptr, workspace, workspace_bytes,
+                         stream);
+}
+
+int32_t admmq_packed_gemm_act(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                              const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                              const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!actq_bits_ok(out_q)) return set_error(ADMMQ_ERR_ARG, "packed_gemm_act: out_q bits must be 1..24");
+  return packed_gemm_run(codes, meta, trans_w, M, K, x, x_layout, N, nb, bias, y, out_q, workspace, workspace_bytes,
+                         stream);
+}
+
+}  // extern "C"
+
+int32_t admmq::packed_gemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                               const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                               const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream) {
   if (!codes || !x || !y || !meta) return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes, meta, x and y must not be NULL");
   if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: M, K, N and nb must be positive");
   if (meta->bits < 1 || meta->bits > 8) return set_error(ADMMQ_ERR_ARG, "packed_gemm: meta bits must be 1..8");
@@ -550,12 +646,22 @@ int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t
   a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-#define ADMMQ_PG_CASE(B)                                                                              \
-  case B:                                                                                             \
-    if (trans_w && x_layout) hipLaunchKernelGGL((k_packed_gemm<B, true, true>), grid, dim3(256), 0, s, a);        \
-    else if (trans_w) hipLaunchKernelGGL((k_packed_gemm<B, true, false>), grid, dim3(256), 0, s, a);  \
-    else if (x_layout) hipLaunchKernelGGL((k_packed_gemm<B, false, true>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((k_packed_gemm<B, false, false>), grid, dim3(256), 0, s, a);              \
+  // the output quantizer: in the serial form's epilogue (the OQ kernels), in the parallel form's reduction
+  const bool oq = actq_on(out_q);
+  PgArgsQ aq;
+  static_cast<PgArgs&>(aq) = a;
+  aq.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+#define ADMMQ_PG_LAUNCH(B, T, X)                                                                      \
+  do {                                                                                                \
+    if (oq && !pl.parallel) hipLaunchKernelGGL((k_packed_gemm<B, T, X, true>), grid, dim3(256), 0, s, aq); \
+    else hipLaunchKernelGGL((k_packed_gemm<B, T, X>), grid, dim3(256), 0, s, a);                      \
+  } while (0)
+#define ADMMQ_PG_CASE(B)                               \
+  case B:                                              \
+    if (trans_w && x_layout) ADMMQ_PG_LAUNCH(B, true, true);   \
+    else if (trans_w) ADMMQ_PG_LAUNCH(B, true, false); \
+    else if (x_layout) ADMMQ_PG_LAUNCH(B, false, true); \
+    else ADMMQ_PG_LAUNCH(B, false, false);             \
     break;
   switch (meta->bits) {
     ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
@@ -563,13 +669,19 @@ int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t
     default: break;   // (refused above)
   }
 #undef ADMMQ_PG_CASE
-  if (pl.parallel)
+#undef ADMMQ_PG_LAUNCH
+  if (pl.parallel && oq)
+    hipLaunchKernelGGL(k_packed_reduce_q, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
+                       pl.total, bias, y, a.M, a.N, a.xl, aq.oq);
+  else if (pl.parallel)
     hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
                        pl.total, bias, y, a.M, a.N, a.xl);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
   return ADMMQ_OK;
 }
+
+extern "C" {
 
 size_t admmq_packed_dwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb) {
   PgPlan pl;
@@ -582,6 +694,28 @@ int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64
                             int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
                             int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y, void* workspace,
                             size_t workspace_bytes, void* stream) {
+  return packed_dwgemm_run(codes, meta, M, K, t, nb, H, W, taps, kh, kw, sh, sw, ph, pw, bias, y, nullptr, nullptr,
+                           workspace, workspace_bytes, stream);
+}
+
+int32_t admmq_packed_dwgemm_act(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                                int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw,
+                                int32_t sh, int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
+                                const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  if (!actq_bits_ok(mid_q)) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm_act: mid_q bits must be 1..24");
+  if (!actq_bits_ok(out_q)) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm_act: out_q bits must be 1..24");
+  return packed_dwgemm_run(codes, meta, M, K, t, nb, H, W, taps, kh, kw, sh, sw, ph, pw, bias, y, mid_q, out_q,
+                           workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+int32_t admmq::packed_dwgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                                 int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
+                                 int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
+                                 const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
   if (!codes || !t || !taps || !y || !meta)
     return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes, meta, t, taps and y must not be NULL");
   if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
@@ -633,20 +767,34 @@ int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64
   d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-#define ADMMQ_PG_CASE(B) \
-  case B: hipLaunchKernelGGL((k_packed_dwgemm<B>), grid, dim3(256), 0, s, d); break;
+  // the mid quantizer runs in the kernel in both forms; the output quantizer in the serial
+  // form's epilogue or in the parallel form's reduction
+  const bool mq = actq_on(mid_q), oq = actq_on(out_q);
+  const int qm = (mq ? 1 : 0) | (oq && !pl.parallel ? 2 : 0);
+  PgDwArgsQ dq;
+  static_cast<PgDwArgs&>(dq) = d;
+  dq.mq = mq ? actq_make(mid_q) : ActQ{0.f, 0.f, 0.f, 0};
+  dq.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+#define ADMMQ_PG_CASE(B)                                                                          \
+  case B:                                                                                         \
+    if (qm == 0) hipLaunchKernelGGL((k_packed_dwgemm<B>), grid, dim3(256), 0, s, d);              \
+    else if (qm == 1) hipLaunchKernelGGL((k_packed_dwgemm<B, 1>), grid, dim3(256), 0, s, dq);     \
+    else if (qm == 2) hipLaunchKernelGGL((k_packed_dwgemm<B, 2>), grid, dim3(256), 0, s, dq);     \
+    else hipLaunchKernelGGL((k_packed_dwgemm<B, 3>), grid, dim3(256), 0, s, dq);                  \
+    break;
   switch (meta->bits) {
     ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
     ADMMQ_PG_CASE(5) ADMMQ_PG_CASE(6) ADMMQ_PG_CASE(7) ADMMQ_PG_CASE(8)
     default: break;   // (refused above)
   }
 #undef ADMMQ_PG_CASE
-  if (pl.parallel)
+  if (pl.parallel && oq)
+    hipLaunchKernelGGL(k_packed_reduce_q, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
+                       pl.total, bias, y, a.M, a.N, 0, dq.oq);
+  else if (pl.parallel)
     hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
                        pl.total, bias, y, a.M, a.N, 0);
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
   return ADMMQ_OK;
 }
-
-}  // extern "C"

@@ -162,6 +162,32 @@ __device__ __forceinline__ float apply_quant(float x, const QParams& p) {
   return (qi * p.rng) / p.n + p.mn;
 }
 
+// Fixed-range activation quantizer (source/quantization.py:147-161, fixed_quantize; DESIGN.md
+// 2.24): the kMinMax arithmetic above with the range given by the caller instead of taken from
+// the tensor. n = float(2^bits - 1), exact for bits <= 24. No clamp: a value outside
+// [mn, mn + rng] lands on a level outside 0..n, as in the reference. One bit is sign(x) - 1
+// with torch's sign, (0 < x) - (x < 0): 0 for a NaN, so a NaN gives -1 there.
+struct ActQ {
+  float mn, rng, n;
+  int bits;
+};
+
+__device__ __forceinline__ float fixed_quant(float x, const ActQ& q) {
+  if (q.bits == 1) return ((x > 0.f ? 1.f : 0.f) - (x < 0.f ? 1.f : 0.f)) - 1.f;
+  const float r = (x - q.mn) / q.rng;
+  const float qi = __builtin_floorf(r * q.n + 0.5f);
+  return (qi * q.rng) / q.n + q.mn;
+}
+
+// host: the kernels' form of a caller's record (include/admmq.h admmq_actq; bits checked by the caller)
+template <class Q>
+inline ActQ actq_make(const Q* q) {
+  ActQ o;
+  o.mn = q->mn; o.rng = q->rng; o.bits = q->bits;
+  o.n = (float)((1 << q->bits) - 1);   // exact: bits <= 24
+  return o;
+}
+
 // The MSE projection clamp(rint(fl(x / s)), qlo, qhi) * s with the quotient from the
 // reciprocal: y = x * (1 / s) is within |y| 2^-23 of x / s (two roundings), so rint(y)
 // is rint(fl(x / s)) unless y lies within |y| 2^-21 of a half-integer - then the IEEE

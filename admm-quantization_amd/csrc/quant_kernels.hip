@@ -1,6 +1,9 @@
 // Standalone quantize_tensor kernels (source/quantization.py:69-115): pack + tensor
 // statistics, and the final elementwise quantization with the resolved parameters.
 // The MSE-minmax candidate search itself lives in mse_search.hip.
+#include <algorithm>
+
+#include "../../include/admmq.h"
 #include "quant_device.h"
 
 namespace admmq {
@@ -183,6 +186,29 @@ void launch_channel_quant(const float* x, float* y, long long A, int C, long lon
                      stats, bits, scheme);
 }
 
+// y = fixed_quant(x) element by element (include/admmq.h admmq_fixed_quantize),
+// grid-stride. Elements [head, head + 4 nvec) go as 16-byte loads and stores (the host sets
+// head so that both pointers are 16-byte aligned there; nvec = 0 when x and y are misaligned
+// differently); the head and the tail behind the vectors, fewer than 4 + 4 elements in the
+// aligned case, go one by one.
+__global__ __launch_bounds__(256) void k_fixed_quant(const float* x, float* y,   // (y may be x: no __restrict__)
+                                                     long long numel, long long head, long long nvec, const ActQ q) {
+  const long long step = (long long)blockDim.x * gridDim.x;
+  const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const float4* xv = reinterpret_cast<const float4*>(x + head);
+  float4* yv = reinterpret_cast<float4*>(y + head);
+  for (long long i = t0; i < nvec; i += step) {
+    const float4 v = xv[i];
+    yv[i] = make_float4(fixed_quant(v.x, q), fixed_quant(v.y, q), fixed_quant(v.z, q), fixed_quant(v.w, q));
+  }
+  const long long vend = head + 4 * nvec;
+  const long long ns = head + (numel - vend);   // scalar elements: [0, head) and [vend, numel)
+  for (long long s = t0; s < ns; s += step) {
+    const long long e = s < head ? s : vend + (s - head);
+    y[e] = fixed_quant(x[e], q);
+  }
+}
+
 void launch_qpack(const QJob* jobs, int njobs, const Chunk* chunks, int nchunks, hipStream_t s) {
   if (nchunks > 0) hipLaunchKernelGGL(k_qpack, dim3(nchunks), dim3(256), 0, s, jobs, chunks);
   if (njobs > 0) hipLaunchKernelGGL(k_qstat, dim3(njobs), dim3(256), 0, s, jobs);
@@ -194,3 +220,28 @@ void launch_qfinal(const QJob* jobs, const Chunk* chunks, int nchunks, int ncand
 }
 
 }  // namespace admmq
+
+extern "C" int32_t admmq_fixed_quantize(const float* x, float* y, int64_t numel, const admmq_actq* q, void* stream) {
+  using namespace admmq;
+  if (!x || !y) return set_error(ADMMQ_ERR_ARG, "fixed_quantize: x and y must not be NULL");
+  if (!q || q->on == 0) return set_error(ADMMQ_ERR_ARG, "fixed_quantize: q must not be NULL or off (on == 0)");
+  if (q->bits < 1 || q->bits > 24) return set_error(ADMMQ_ERR_ARG, "fixed_quantize: bits must be 1..24");
+  if (numel <= 0) return set_error(ADMMQ_ERR_ARG, "fixed_quantize: numel must be positive");
+  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
+  if (((xa | ya) & 3) != 0) return set_error(ADMMQ_ERR_ARG, "fixed_quantize: x and y must be float aligned");
+  const ActQ k = actq_make(q);
+  long long head = numel, nvec = 0;
+  if ((xa & 15) == (ya & 15)) {
+    head = (long long)(((16 - (xa & 15)) & 15) / 4);
+    if (head > numel) head = numel;
+    nvec = (numel - head) / 4;
+  }
+  const long long ns = head + (numel - (head + 4 * nvec));
+  long long nblk = (std::max(nvec, ns) + 255) / 256;
+  nblk = std::min<long long>(std::max<long long>(nblk, 1), 8192);
+  hipLaunchKernelGGL(k_fixed_quant, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), x, y,
+                     (long long)numel, head, nvec, k);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}

@@ -10,6 +10,7 @@
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::packed_gemm             a packed weight times float32 activations
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
+//   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -317,8 +318,21 @@ std::vector<int64_t> packed_gemm_shape(const at::Tensor& x, int64_t M, int64_t K
   return shape;
 }
 
-at::Tensor packed_gemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
-                            const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
+// A quantizer as the ops carry it: bits (0: none) and the float32 range as schema floats (a double
+// holds a float32 exactly). DESIGN.md 2.24.
+admmq_actq actq_of(int64_t bits, double mn, double rng, const char* what) {
+  TORCH_CHECK(bits >= 0 && bits <= 24, "admmq: ", what, ": activation quantizer bits must be 1..24 (0: none), got ", bits);
+  admmq_actq q;
+  q.bits = static_cast<int32_t>(bits);
+  q.on = bits > 0 ? 1 : 0;
+  q.mn = static_cast<float>(mn);
+  q.rng = static_cast<float>(rng);
+  return q;
+}
+
+at::Tensor packed_gemm_impl(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
+                            const admmq_actq* out_q) {
   static_assert(sizeof(admmq_qmeta) == 32, "meta is int32 [8]");
   check_f32_device(x, "x");
   TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
@@ -354,12 +368,62 @@ at::Tensor packed_gemm_cuda(const at::Tensor& codes, const at::Tensor& meta_word
   at::Tensor y = at::empty(oshape, xc.options());
   const size_t nbytes = admmq_packed_gemm_workspace_size(M, K, N, static_cast<int32_t>(nb));
   at::Tensor ws = workspace(nbytes, xc);
+  if (out_q) {
+    check_rc(admmq_packed_gemm_act(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<float>(),
+                                   static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
+                                   bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(), out_q,
+                                   ws.data_ptr(), ws.numel(), stream_of(xc)),
+             "packed_gemm_act");
+    return y;
+  }
   check_rc(admmq_packed_gemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<float>(),
                              static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
                              bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(), ws.data_ptr(),
                              ws.numel(), stream_of(xc)),
            "packed_gemm");
   return y;
+}
+
+at::Tensor packed_gemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
+  return packed_gemm_impl(codes, meta_words, trans_w, M, K, x, x_layout, bias, nullptr);
+}
+
+// packed_gemm with the output quantizer in the kernel (admmq_packed_gemm_act); out_bits 0: none
+at::Tensor packed_gemm_act_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                                const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
+                                int64_t out_bits, double out_mn, double out_rng) {
+  const admmq_actq q = actq_of(out_bits, out_mn, out_rng, "packed_gemm_act");
+  return packed_gemm_impl(codes, meta_words, trans_w, M, K, x, x_layout, bias, &q);
+}
+
+at::Tensor packed_gemm_act_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                                const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
+                                int64_t out_bits, double out_mn, double out_rng) {
+  (void)actq_of(out_bits, out_mn, out_rng, "packed_gemm_act");
+  return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
+}
+
+// --- fixed_quantize -------------------------------------------------------------------------
+// y = q(x) element by element (admmq_fixed_quantize, k_fixed_quant). Inference only.
+at::Tensor fixed_quantize_cuda(const at::Tensor& x, int64_t bits, double mn, double rng) {
+  check_f32_device(x, "x");
+  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
+              "admmq: fixed_quantize is inference only (no backward through the quantizer): call it under "
+              "torch.no_grad() or detach x");
+  TORCH_CHECK(bits >= 1, "admmq: fixed_quantize: activation quantizer bits must be 1..24, got ", bits);
+  const admmq_actq q = actq_of(bits, mn, rng, "fixed_quantize");
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  at::Tensor y = at::empty_like(xc);
+  if (xc.numel() == 0) return y;
+  check_rc(admmq_fixed_quantize(xc.data_ptr<float>(), y.data_ptr<float>(), xc.numel(), &q, stream_of(xc)), "fixed_quantize");
+  return y;
+}
+
+at::Tensor fixed_quantize_meta(const at::Tensor& x, int64_t bits, double mn, double rng) {
+  TORCH_CHECK(bits >= 1 && bits <= 24, "admmq: fixed_quantize: activation quantizer bits must be 1..24, got ", bits);
+  return at::empty(x.sizes(), x.options().dtype(at::kFloat));
 }
 
 at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
@@ -385,9 +449,10 @@ std::vector<int64_t> packed_dwgemm_shape(const at::Tensor& x, const at::Tensor& 
   return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
 }
 
-at::Tensor packed_dwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+at::Tensor packed_dwgemm_impl(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
                               const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
-                              int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias) {
+                              int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias,
+                              const admmq_actq* mid_q, const admmq_actq* out_q) {
   check_f32_device(x, "x");
   TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
               "admmq: packed_dwgemm is inference only (no backward through packed weights): call it under "
@@ -425,6 +490,15 @@ at::Tensor packed_dwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_wo
   at::Tensor y = at::empty(oshape, xc.options());
   const size_t nbytes = admmq_packed_dwgemm_workspace_size(M, K, oshape[2], oshape[3], nb);
   at::Tensor ws = workspace(nbytes, xc);
+  if (mid_q || out_q) {
+    check_rc(admmq_packed_dwgemm_act(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<float>(), nb, xc.size(2), xc.size(3),
+                                     tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
+                                     static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
+                                     static_cast<int32_t>(pw), bc.defined() ? bc.data_ptr<float>() : nullptr,
+                                     y.data_ptr<float>(), mid_q, out_q, ws.data_ptr(), ws.numel(), stream_of(xc)),
+             "packed_dwgemm_act");
+    return y;
+  }
   check_rc(admmq_packed_dwgemm(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<float>(), nb, xc.size(2), xc.size(3),
                                tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
                                static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
@@ -432,6 +506,33 @@ at::Tensor packed_dwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_wo
                                y.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(xc)),
            "packed_dwgemm");
   return y;
+}
+
+at::Tensor packed_dwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                              const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                              int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias) {
+  return packed_dwgemm_impl(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias, nullptr, nullptr);
+}
+
+// packed_dwgemm with the mid and the output quantizer in the kernel (admmq_packed_dwgemm_act); bits 0: none
+at::Tensor packed_dwgemm_act_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                                  const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                                  int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias,
+                                  int64_t mid_bits, double mid_mn, double mid_rng, int64_t out_bits, double out_mn,
+                                  double out_rng) {
+  const admmq_actq mq = actq_of(mid_bits, mid_mn, mid_rng, "packed_dwgemm_act");
+  const admmq_actq oq = actq_of(out_bits, out_mn, out_rng, "packed_dwgemm_act");
+  return packed_dwgemm_impl(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias, &mq, &oq);
+}
+
+at::Tensor packed_dwgemm_act_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                                  const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                                  int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias,
+                                  int64_t mid_bits, double mid_mn, double mid_rng, int64_t out_bits, double out_mn,
+                                  double out_rng) {
+  (void)actq_of(mid_bits, mid_mn, mid_rng, "packed_dwgemm_act");
+  (void)actq_of(out_bits, out_mn, out_rng, "packed_dwgemm_act");
+  return at::empty(packed_dwgemm_shape(x, taps, M, K, kh, kw, sh, sw, ph, pw), x.options().dtype(at::kFloat));
 }
 
 at::Tensor packed_dwgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
@@ -585,6 +686,12 @@ TORCH_LIBRARY(admmq, m) {
         "Tensor? bias=None) -> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
         "int sw, int ph, int pw, Tensor? bias=None) -> Tensor");
+  m.def("packed_gemm_act(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
+        "Tensor? bias, int out_bits, float out_mn, float out_rng) -> Tensor");
+  m.def("packed_dwgemm_act(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
+        "int sw, int ph, int pw, Tensor? bias, int mid_bits, float mid_mn, float mid_rng, int out_bits, float out_mn, "
+        "float out_rng) -> Tensor");
+  m.def("fixed_quantize(Tensor x, int bits, float mn, float rng) -> Tensor");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -598,6 +705,9 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("packed_gemm", &packed_gemm_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
+  m.impl("packed_gemm_act", &packed_gemm_act_cuda);
+  m.impl("packed_dwgemm_act", &packed_dwgemm_act_cuda);
+  m.impl("fixed_quantize", &fixed_quantize_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -610,6 +720,9 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("packed_gemm", &packed_gemm_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
+  m.impl("packed_gemm_act", &packed_gemm_act_meta);
+  m.impl("packed_dwgemm_act", &packed_dwgemm_act_meta);
+  m.impl("fixed_quantize", &fixed_quantize_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

@@ -245,6 +245,50 @@ int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64
                             int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* Fixed-range ("fake") activation quantizer (source/quantization.py:147-161):
+ *   bits == 1:  y = sign(x) - 1 with sign(x) = (0 < x) - (x < 0)   (mn, rng ignored; NaN -> -1)
+ *   else:       r = (x - mn) / rng;  n = float(2^bits - 1);  qi = floor(r * n + 0.5)
+ *               y = (qi * rng) / n + mn
+ * every step a separately rounded float32 operation. There is no clamp: a value outside
+ * [mn, mn + rng] maps to a level outside 0..n, so the result is a float tensor without a
+ * packed-code form. NaN, +-inf, rng == 0 and rng < 0 follow IEEE. The caller derives (mn, rng)
+ * from its (min, max): both as float32, rng = max - min rounded to float32.
+ * A HOST record; on == 0 (or a NULL pointer where one is optional): no quantizer. */
+typedef struct admmq_actq {
+  int32_t bits; /* 1..24 when on != 0 */
+  int32_t on;
+  float mn;
+  float rng;
+} admmq_actq; /* 16 bytes */
+
+/* y[i] = q(x[i]), i < numel: x, y device, float aligned, contiguous (y may be x). One launch,
+ * also for one element. ADMMQ_ERR_ARG for NULL x / y, NULL q or q->on == 0, q->bits outside
+ * 1..24, numel <= 0 - each with its own admmq_last_error text, before any launch. */
+int32_t admmq_fixed_quantize(const float* x, float* y, int64_t numel, const admmq_actq* q, void* stream);
+
+/* admmq_packed_gemm with an output quantizer: Y = q_out(W X (+ bias)), applied to each output
+ * just before it is stored (in the K-piece-parallel regime: after the ordered sum and the
+ * bias; the partial images stay unquantized). The result has the bits of
+ * admmq_fixed_quantize on admmq_packed_gemm's output. out_q NULL or on == 0: the bits (and the
+ * kernels) of admmq_packed_gemm. The workspace size is admmq_packed_gemm_workspace_size's.
+ * Errors as admmq_packed_gemm, plus ADMMQ_ERR_ARG for out_q->on != 0 with bits outside 1..24. */
+int32_t admmq_packed_gemm_act(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                              const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
+                              const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream);
+
+/* admmq_packed_dwgemm with a mid quantizer (z = q_mid(z) after step 1's tap sum: the
+ * reference's quantizer behind the depthwise stage; only the elements of Z are quantized,
+ * the zero fill of a tile's padding stays 0) and an output quantizer (as above). The result
+ * has the bits of admmq_packed_gemm_act on a Z formed by step 1 and quantized by
+ * admmq_fixed_quantize. Either may be NULL or off; with both off: the bits (and the kernels)
+ * of admmq_packed_dwgemm. The workspace size is admmq_packed_dwgemm_workspace_size's. Errors
+ * as admmq_packed_dwgemm, plus ADMMQ_ERR_ARG for a quantizer that is on with bits outside 1..24. */
+int32_t admmq_packed_dwgemm_act(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
+                                int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw,
+                                int32_t sh, int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
+                                const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

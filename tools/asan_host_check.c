@@ -196,6 +196,37 @@ int main(void) {
     fails += DW(c, &q2, 8, 8, x, 1, 6, 6, tp, 3, 3, 1, 1, 1, 1, y, 1 << 20) != ADMMQ_ERR_ARG;
     fails += DW(c, &qm, 512, 1141, x, 1, 2, 2, tp, 3, 3, 1, 1, 1, 1, y, 16) != ADMMQ_ERR_WORKSPACE;
 #undef DW
+    /* fixed-range activation quantizers: the record's checks come before everything else, a
+     * quantizer that is off is not looked at, and the workspace is the parents' */
+    {
+      admmq_actq on = {4, 1, 0.3f, 1.1f}, off = {99, 0, 0.f, 0.f}, wide = {25, 1, 0.f, 1.f}, zero = {0, 1, 0.f, 1.f};
+      fails += sizeof(admmq_actq) != 16;
+      fails += admmq_fixed_quantize(NULL, y, 8, &on, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, NULL, 8, &on, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, 8, NULL, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, 8, &off, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, 8, &wide, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, 8, &zero, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, 0, &on, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize(x, y, -1, &on, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_fixed_quantize((const float*)0x10002, y, 8, &on, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_gemm_act(c, &qm, 0, 8, 8, x, 0, 4, 1, NULL, y, &wide, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_gemm_act(c, &qm, 0, 8, 8, x, 0, 4, 1, NULL, y, &zero, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_gemm_act(NULL, &qm, 0, 8, 8, x, 0, 4, 1, NULL, y, &off, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_gemm_act(c, &qm, 0, 8, 8, x, 1, 4, 2, NULL, y, &on, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_gemm_act(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, &on, ws, 16, NULL) != ADMMQ_ERR_WORKSPACE;
+      fails += admmq_packed_gemm_act(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, NULL, NULL, 0, NULL) != ADMMQ_ERR_WORKSPACE;
+#define DWA(mm, M, K, H, W, mq, oq, wsb) \
+  admmq_packed_dwgemm_act(c, mm, M, K, x, 1, H, W, tp, 3, 3, 1, 1, 1, 1, NULL, y, mq, oq, ws, wsb, NULL)
+      fails += DWA(&qm, 8, 8, 6, 6, &wide, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += DWA(&qm, 8, 8, 6, 6, NULL, &zero, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += DWA(&qm, 8, 8, 6, 6, &on, &wide, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += DWA(NULL, 8, 8, 6, 6, &on, &on, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += DWA(&qm, 8, 8, 0, 6, &off, &on, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += DWA(&qm, 512, 1141, 2, 2, &on, &on, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += DWA(&qm, 512, 1141, 2, 2, NULL, NULL, 16) != ADMMQ_ERR_WORKSPACE;
+#undef DWA
+    }
   }
   printf("last error: %s\n", admmq_last_error());
   printf("%s (%d failures)\n", fails ? "FAIL" : "OK", fails);
