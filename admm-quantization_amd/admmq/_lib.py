@@ -153,6 +153,7 @@ def load() -> ctypes.CDLL:
         "admmq_quantize_channel": (I32, [P, P, P, I32, I32, I32, I32, P, S, P]),
         "admmq_set_exhaustive_search": (I32, [I32]),
         "admmq_debug_set_sel_widen": (I32, [I32]),
+        "admmq_debug_shared_stage2_count": (I64, [I32]),
         "admmq_debug_set_wide_min_tiles": (I32, [ctypes.c_int64]),
         "admmq_set_solve_mode": (I32, [I32]),
         "admmq_get_solve_mode": (I32, []),
@@ -304,12 +305,31 @@ class exhaustive_search(_switch):
 
 class sel_widen(_switch):
     """Context manager (diagnostics): keep every candidate in the two-stage search's
-    selected set, so its multi-candidate paths - the canonical SSEs, and in the fused
-    finalize the record published before the ready word, and the thin loop's stage 2 - run
-    on every call. The answer is exact either way, so the bits are the same."""
+    selected set (``mode`` 1, the default), or the rigorous set plus the two candidates
+    either side of the first stage-1 minimum (``mode`` 2: the list form, 1 < |S| <= 64), so
+    its multi-candidate paths - the canonical SSEs (in the fused finalize the record
+    published before the ready word and the sweep shared among the job's blocks), and the
+    thin loop's stage 2 - run on every call. The answer is exact either way, so the bits are
+    the same."""
 
     _setter, _checked = "admmq_debug_set_sel_widen", (True, True)
-    enable = True
+
+    def __init__(self, mode: int = 1):
+        if mode not in (1, 2):
+            raise ValueError(mode)
+        self.mode = mode
+
+    def _encode(self):
+        return self.mode
+
+
+def shared_stage2_count(reset: bool = False) -> int:
+    """Diagnostics: multi-candidate selections whose stage 2 the fused search launch shared
+    among the job's blocks, since the last reset (synchronises with the device)."""
+    n = int(load().admmq_debug_shared_stage2_count(1 if reset else 0))
+    if n < 0:
+        raise RuntimeError("admmq: shared_stage2_count failed")
+    return n
 
 
 class solve_mode:

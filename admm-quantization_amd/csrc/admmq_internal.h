@@ -274,6 +274,7 @@ void launch_mse_hist(const ProbDesc* d, const QJob* q, const Chunk* chunks, int 
                      int slot, int nv, hipStream_t s);
 size_t hist_lds_bytes(int ncand, int bits);
 size_t hist3_lds_bytes(int ncand, int bits);
+size_t hist3_fin_lds_bytes(int ncand, int bits, int nv);
 int copy_hist_trace(unsigned long long* host, int n);
 int copy_gemm_trace(unsigned long long* host, int n);
 int copy_gemm_trace2(unsigned long long* host, int n);
@@ -285,6 +286,7 @@ int copy_hist_cu(unsigned long long* host, int n);
 int copy_small_trace(unsigned long long* host, int n);
 int copy_thin_loop_trace(unsigned long long* host, int n);
 int copy_sel_stats(unsigned long long* host, int reset);
+long long copy_shared_stage2(int reset);
 int check_thresholds(unsigned seed, int nsamp);
 int check_cells(int n, int bits, unsigned seed, int nsamp, unsigned* maxdev_out);
 bool merged_ok(int ncand, int bits);

@@ -594,10 +594,11 @@ int32_t admmq_debug_set_wide_min_tiles(int64_t t) {
   g_wide_min_tiles = t;
   return ADMMQ_OK;
 }
-// diagnostics: keep every candidate in the selected set S (1) or the rigorous set (0, default):
-// the multi-candidate paths run every time, with the same exact answer
+// diagnostics: keep every candidate in the selected set S (1), S plus the two candidates either
+// side of the first stage-1 minimum (2: the list form, 1 < |S| <= kMaxSel) or the rigorous
+// set (0, default): the multi-candidate paths run every time, with the same exact answer
 int32_t admmq_debug_set_sel_widen(int32_t on) {
-  if (on < 0 || on > 1) return fail(ADMMQ_ERR_ARG, "sel widen must be 0 or 1");
+  if (on < 0 || on > 2) return fail(ADMMQ_ERR_ARG, "sel widen must be 0, 1 or 2");
   if (set_sel_widen_search(on) != 0 || set_sel_widen_thin(on) != 0) return check_hip("sel widen");
   return ADMMQ_OK;
 }
@@ -911,6 +912,9 @@ int32_t admmq_debug_hist_cu(unsigned long long* host, int32_t n) { return copy_h
 int32_t admmq_debug_small_trace(unsigned long long* host, int32_t n) { return copy_small_trace(host, n); }
 int32_t admmq_debug_thin_loop_trace(unsigned long long* host, int32_t n) { return copy_thin_loop_trace(host, n); }
 int32_t admmq_debug_sel_stats(unsigned long long* host, int32_t reset) { return copy_sel_stats(host, reset); }
+// diagnostics: multi-candidate selections whose stage 2 the fused search launch shared among
+// the job's blocks, since the last reset (reset != 0 zeroes the counter); -1 on a HIP error
+int64_t admmq_debug_shared_stage2_count(int32_t reset) { return copy_shared_stage2(reset); }
 int32_t admmq_debug_check_thresholds(uint32_t seed, int32_t nsamp) { return check_thresholds(seed, nsamp); }
 int32_t admmq_debug_check_cells(int32_t n, int32_t bits, uint32_t seed, int32_t nsamp, uint32_t* maxdev) {
   return check_cells(n, bits, seed, nsamp, maxdev);

@@ -91,12 +91,27 @@ int copy_hist_trace(unsigned long long* host, int n) {
 // 2..kMaxSel, exhaustive} counts since the last reset), for admmq_debug_sel_stats.
 __device__ unsigned long long g_sel_stats[3];
 __device__ int g_no_stop = 0;   // stop flag of units without one (standalone quantization)
-// Diagnostics (admmq_debug_set_sel_widen): every candidate stays in S, so the selection's
-// multi-candidate paths (the canonical SSEs; in the fused finalize the record published
-// before the ready word) run every time; the exact answer, hence every bit, is the same.
+// Diagnostics (admmq_debug_set_sel_widen): 1: every candidate stays in S; 2: the rigorous S
+// plus the window of kSelWindow candidates either side of the first stage-1 minimum (at
+// most five more, so the list form 1 < |S| <= kMaxSel). The selection's multi-candidate
+// paths (the canonical SSEs; in the fused finalize the record published before the ready
+// word and the sweep shared among the job's blocks) then run every time; S always holds the
+// rigorous set, so the exact answer, hence every bit, is the same.
 __device__ int g_sel_widen = 0;
 int set_sel_widen_search(int on) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_sel_widen), &on, sizeof(int)) == hipSuccess ? 0 : -1;
+}
+// Diagnostics (admmq_debug_shared_stage2_count): multi-candidate records published by the
+// fused kernel (each one is a stage 2 shared among its job's blocks) since the last reset.
+__device__ unsigned long long g_shared_stage2 = 0ull;
+long long copy_shared_stage2(int reset) {
+  unsigned long long h = 0ull;
+  if (hipMemcpyFromSymbol(&h, HIP_SYMBOL(g_shared_stage2), sizeof(h)) != hipSuccess) return -1;
+  if (reset) {
+    const unsigned long long z = 0ull;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_shared_stage2), &z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return (long long)h;
 }
 int copy_sel_stats(unsigned long long* host, int reset) {
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sel_stats), sizeof(g_sel_stats)) != hipSuccess) return -1;
@@ -219,7 +234,7 @@ __device__ void select_wave(const MseView& v, int* sel, int* lsel, const unsigne
     for (int c = c1 - 1; c >= c0; --c) {
       double lo, hi;
       cx.bounds(c, t1, t2, lo, hi);
-      if (lo <= mymin || g_sel_widen != 0) { keep |= 1ull << (c - c0); ++cnt; }
+      if (lo <= mymin || g_sel_widen != 0) { keep |= 1ull << (c - c0); ++cnt; }   // (this form: 2 widens like 1)
       t1 += H1[c]; t2 += H2[c];
     }
   }
@@ -245,10 +260,17 @@ __device__ void select_wave(const MseView& v, int* sel, int* lsel, const unsigne
   }
 }
 
-// Stage 2 inside the last stage-1 block of a job (|S| > 1 is rare: ~0.1 % of the
-// selections on the benchmark workload): the canonical SSE of every candidate in S
+// Stage 2 inside the last stage-1 block of a job: the canonical SSE of every candidate in S
 // (or of all of them) over the job's quads, 512-quad tiles staged in LDS, into v.sse.
-// Removes a separate stage-2 launch from every iteration.
+// Removes a separate stage-2 launch from every iteration. ONE block sweeps the whole job,
+// about 2.2 us per tile (a dependent load, two barriers, the sweep): 630 us for a
+// 512 x 1141 factor (286 tiles), milliseconds for an 11008-row one, while the rest of the
+// launch has finished. |S| > 1 is rare per selection (~0.07 % on the benchmark workload,
+// 22 per C3 step, 12 of them in big jobs), but each event costs up to 22 ordinary launches. So
+// the fused finalize launch, whose blocks are all resident and wait for the selection
+// anyway, shares the sweep among the job's blocks instead (k_mse_hist3, FIN); this form is
+// left to the launches whose blocks exit after the ticket (k_mse_hist, k_mse_hist3 without
+// FIN, k_mse_small_admm's single block) - DESIGN.md §8.4 names them as the follow-up.
 __device__ void sse_in_block(const MseView& v, const int* lsel, int ncand, int bits, int slot, float mx, float4* xs) {
   const int ns = lsel[0];
   if (ns == 1) return;
@@ -450,12 +472,23 @@ __device__ void select_wave2(const MseView& v, int* sel, int* lsel, const unsign
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) mymin = fmin(mymin, __shfl_xor(mymin, off));
+  const int wd = g_sel_widen;
+  int cmin = 0;
+  if (wd == 2) {   // diagnostics: the first candidate at the minimum
+    unsigned mine = 0x7fffffffu;
+    for (int c = c1 - 1; c >= c0; --c) {
+      double lo, hi;
+      cx.bounds(c, T1v[c], T2v[c], lo, hi);
+      if (hi == mymin) mine = (unsigned)c;
+    }
+    cmin = (int)wave_min_u32(mine);
+  }
   unsigned long long keep = 0ull;                  // bit (c - c0) set: c in S (P <= 16)
   int cnt = 0;
   for (int c = c0; c < c1; ++c) {
     double lo, hi;
     cx.bounds(c, T1v[c], T2v[c], lo, hi);
-    if (lo <= mymin || g_sel_widen != 0) { keep |= 1ull << (c - c0); ++cnt; }
+    if (lo <= mymin || sel_widened(wd, c, cmin)) { keep |= 1ull << (c - c0); ++cnt; }
   }
   int pre = cnt;                                   // inclusive prefix over lanes
 #pragma unroll
@@ -503,7 +536,17 @@ __device__ void select_block(const MseView& v, int* sel, int* lsel, unsigned lon
   __syncthreads();
   double mn = wmin[0];
   for (int k = 1; k < nw; ++k) mn = fmin(mn, wmin[k]);
-  const bool keep = c < n && (lo <= mn || g_sel_widen != 0);
+  const int wd = g_sel_widen;
+  int cmin = 0;
+  if (wd == 2) {   // diagnostics (block-uniform): the first candidate at the minimum
+    const unsigned long long at = __ballot(c < n && hi == mn);
+    if (lane == 0) wcnt[w] = at ? 64 * w + (int)__builtin_ctzll(at) : 0x7fffffff;
+    __syncthreads();
+    cmin = wcnt[0];
+    for (int k = 1; k < nw; ++k) cmin = min(cmin, wcnt[k]);
+    __syncthreads();   // wcnt is reused below
+  }
+  const bool keep = c < n && (lo <= mn || sel_widened(wd, c, cmin));
   const unsigned long long bal = __ballot(keep);
   if (lane == 0) wcnt[w] = __popcll(bal);
   __syncthreads();
@@ -915,6 +958,17 @@ __device__ __forceinline__ void h3_totals(int c, int n, const unsigned short* rn
 // with a stale selection record; the caller re-runs the call with the separate finalize
 // launch (the PyTorch op does). Saves the finalize launch, its dependent parameter chain
 // and its re-read of H_T and U.
+// |S| > 1 (rare): the last block publishes the record BEFORE stage 2, and every block of the
+// job - the last one too - adds the canonical SSE terms of the quads it holds (x4 - u4, the
+// same float32 subtraction and sse_quad as sse_in_block; the terms are integers, so the
+// sums do not depend on who adds them) into v.sse with agent-scope atomics, one per
+// candidate and block. Then a second arrival on the job's ticket word (drain, barrier, one
+// lane adds, one lane polls until 2 x blocks; bounded by `wait_polls` like the first wait,
+// same fault path), an acquire fence, and the first-index argmin as before. One block
+// sweeping the whole job held the launch up to 630 us at C3. The hand-off rules of
+// thin_loop.hip's header hold: only sc1 stores / agent atomics cross blocks, every arrival
+// is preceded by a drain, every spin is bounded. The solve's first tile zeroes ticket and
+// sse before every search launch.
 #ifndef ADMMQ_FIN_STREAM
 #define ADMMQ_FIN_STREAM 1
 #endif
@@ -1155,14 +1209,16 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
       }
       __syncthreads();
     }
-    sse_in_block(v, lsel, n, QMAX == 1 ? 1 : 31 - __builtin_clz(QMAX) + 1, slot, mx, reinterpret_cast<float4*>(smem));
+    if constexpr (!FIN)   // (FIN: stage 2 is shared among the job's blocks, below)
+      sse_in_block(v, lsel, n, QMAX == 1 ? 1 : 31 - __builtin_clz(QMAX) + 1, slot, mx, reinterpret_cast<float4*>(smem));
     trace(ADMMQ_NOW());
     if constexpr (FIN) {
       // publish. A single candidate c* (nearly always) travels in the ready word itself,
       // (iter + 1) << 32 | 1 << 31 | c*: the waiting blocks need nothing else, so neither the
       // record's write-through stores nor their drain sit before it (the record keeps the
       // plain stores of select_block for the later launches). Otherwise the record
-      // write-through, drained, then the ready word.
+      // write-through, drained, then the ready word - before stage 2, which every block of
+      // the job then shares.
       const unsigned long long tag = (unsigned long long)(unsigned)(iter + 1) << 32;
       if (lsel[0] == 1) {
         if (threadIdx.x == 0)
@@ -1172,6 +1228,7 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
         const int nrec = 2 + min(lsel[0], kMaxSel);
         for (int j = threadIdx.x; j < nrec; j += blockDim.x)
           __hip_atomic_store(sel + j, lsel[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0) atomicAdd(&g_shared_stage2, 1ull);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(v.ready + slot, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1215,12 +1272,77 @@ __global__ __launch_bounds__(kH3Threads, 4) void k_mse_hist3(
     QParams qp;
     if (lsel[0] == 1) {
       qp = qparams_mse(bits, cand_t(mx, lsel[2], n));
-    } else {   // |S| > 1: the canonical SSEs decide (written by the last block's atomics)
+    } else {   // |S| > 1 (rare): the canonical SSEs decide, each block adding its own quads' terms
+      const int ns = lsel[0];
+      const bool all = ns >= n;
+      const int nc = all ? n : ns;
+      if (!last && !all)   // the list (the last block holds it already; lsel[0] is not rewritten)
+        for (int j = threadIdx.x; j < nc; j += kH3Threads)
+          lsel[2 + j] = __hip_atomic_load(sel + 2 + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // The block's quads X - U (zero past the unit's end: they add 0) parked in the tables'
+      // LDS, free by now (hist3_fin_lds_bytes), each thread reading back its own in a rolled
+      // loop: formed in registers inside the candidate loop, the quads and their unrolled
+      // temporaries set the kernel's register count (128 VGPRs and scratch at NV = 3; the
+      // elements for the finalize stay in registers - reading them again after the sweep
+      // cost more registers at the join, not fewer). Then the block's per-candidate sums.
+      float4* xq = reinterpret_cast<float4*>(smem);   // [2 NV][kH3Threads]
+      unsigned long long* part = reinterpret_cast<unsigned long long*>(xq + 2 * NV * kH3Threads);
+#pragma unroll
+      for (int hh = 0; hh < 2 * NV; ++hh) {
+        const long long e = (long long)ck.start + 4LL * threadIdx.x + 2048LL * hh;
+        float4 xa = x4[hh];
+        if (ck.U) xa = sub4(xa, u4[hh]);
+        if (e >= total) xa = make_float4(0.f, 0.f, 0.f, 0.f);
+        xq[hh * kH3Threads + threadIdx.x] = xa;
+      }
+      for (int j = threadIdx.x; j < nc; j += kH3Threads) part[j] = 0ull;
+      __syncthreads();
+      {
+        const int K = fixed_exp(mx, v.nq);
+        const float qlo = (float)(-QMAX), qhi = (float)(QMAX - 1), den = (float)(2 * QMAX - 1);
+        const float delta = (float)(QMAX + 1) * 0x1p-21f;   // sse_group's window
+        for (int j = 0; j < nc; ++j) {
+          const int c = all ? j : lsel[2 + j];
+          const float s = (2.0f * cand_t(mx, c, n)) / den;
+          const float rcp = 1.0f / s;
+          unsigned long long acc = 0ull;
+#pragma unroll 1
+          for (int hh = 0; hh < 2 * NV; ++hh)
+            acc += sse_quad(xq[hh * kH3Threads + threadIdx.x], s, rcp, qlo, qhi, delta, K);
+          acc = wave_suffix_u64(acc);   // lane 0: the wave's sum
+          if ((threadIdx.x & 63) == 0 && acc) atomicAdd(&part[j], acc);
+        }
+      }
+      __syncthreads();
+      unsigned long long* gsse = v.sse + (size_t)slot * n;
+      for (int j = threadIdx.x; j < nc; j += kH3Threads)
+        if (part[j])
+          __hip_atomic_fetch_add(&gsse[all ? j : lsel[2 + j]], part[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // second arrival on the job's ticket: every block's sums are in before any block reads them
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
       if (threadIdx.x == 0) {
+        const unsigned want = 2u * (unsigned)(ck.nblk > 0 ? ck.nblk : v.nhist);
+        __hip_atomic_fetch_add(&v.ticket[slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        unsigned polls = 0;
+        int to = 0;
+        while (__hip_atomic_load(&v.ticket[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != want) {
+          __builtin_amdgcn_s_sleep(2);
+          if (++polls >= wait_polls) {
+            __hip_atomic_store(p.flags + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            to = 1;
+            break;
+          }
+        }
+        timed_out = to;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();
+      if (timed_out) {   // internal fault: leave the elements unfinalized (the caller re-runs)
+        __builtin_amdgcn_s_waitcnt(0);
+        return;
+      }
       qp = block_qparams(kMse, bits, v, slot, n, 0, 0.f, 0.f);
     }
     __syncthreads();   // the search tables' LDS is reused as rmax
@@ -1389,6 +1511,13 @@ size_t hist3_lds_bytes(int ncand, int bits) {
   return std::max((bytes + 15) & ~(size_t)15, (size_t)kSseQuads * 16);
 }
 
+// The fused (FIN) launch: also room for the shared stage 2's parked quads (2 nv float4 per
+// thread) and per-candidate sums; more than the tables (hist3_lds_bytes) only for
+// qmax * ncand below ~700 (nv = 2) / ~1180 (nv = 3) at 200 candidates.
+size_t hist3_fin_lds_bytes(int ncand, int bits, int nv) {
+  return std::max(hist3_lds_bytes(ncand, bits), (size_t)2 * nv * kH3Threads * 16 + (size_t)ncand * 8);
+}
+
 size_t hist_lds_bytes(int ncand, int bits) {
   const int qmax = 1 << (bits - 1);
   const size_t nb = (size_t)ncand + 1 + 64;
@@ -1483,7 +1612,7 @@ void launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int
                       const unsigned short* rank0, const unsigned short* groups, int ngroups, int nv, bool fin, int iter,
                       unsigned wait_polls, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
   if (nchunks <= 0) return;
-  const size_t lds = hist3_lds_bytes(ncand, bits);
+  const size_t lds = fin ? hist3_fin_lds_bytes(ncand, bits, nv) : hist3_lds_bytes(ncand, bits);
   // ev0 / ev1 (profiling, may be null): recorded by the dispatch itself at the kernel's start / end
 #define ADMMQ_H3(Q, V, F)                                                                                         \
   hipExtLaunchKernelGGL((k_mse_hist3<Q, V, F>), dim3(nchunks), dim3(kH3Threads), lds, s, ev0, ev1, 0u, d, q, chunks, \
@@ -1527,7 +1656,7 @@ int hist3_fin_capacity(int ncand, int bits, int nv) {
     int n = 0;
     cus[dev] = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess ? n : 0;
   });
-  const size_t lds = hist3_lds_bytes(ncand, bits);
+  const size_t lds = hist3_fin_lds_bytes(ncand, bits, nv);
   int per = 0;
   hipError_t e = hipErrorInvalidValue;
 #define ADMMQ_OCC(Q) \

@@ -241,6 +241,41 @@ __device__ __forceinline__ int wave_argmin_u64(const unsigned long long* sse, in
   return bi;
 }
 
+// The selection knob (admmq_debug_set_sel_widen, diagnostics; mse_search.hip and thin_loop.hip):
+// does value wd keep candidate c beside the rigorous set? 1: every candidate; 2: the
+// kSelWindow candidates either side of cmin, the first candidate at the stage-1 minimum
+// (cmin = 0x7fffffff, "none found", keeps nothing).
+constexpr int kSelWindow = 2;
+__device__ __forceinline__ bool sel_widened(int wd, int c, int cmin) {
+  return wd == 1 || (wd == 2 && (unsigned)(c - cmin + kSelWindow) <= 2u * kSelWindow);
+}
+
+// The canonical fixed-point SSE term of one quad v at scale s (rcp = 1 / s; qlo / qhi the
+// level clamp; delta the near-half-integer window of the reciprocal fast path): the one
+// definition shared by every stage-2 sweep, so they all add the same integers.
+__device__ __forceinline__ unsigned long long sse_quad(float4 v, float s, float rcp, float qlo, float qhi,
+                                                      float delta, int K) {
+  const float y0 = v.x * rcp, y1 = v.y * rcp, y2 = v.z * rcp, y3 = v.w * rcp;
+  float q0 = __builtin_rintf(y0), q1 = __builtin_rintf(y1), q2 = __builtin_rintf(y2), q3 = __builtin_rintf(y3);
+  // distance of each y to the nearest half-integer; one compare per quad
+  const float e0 = __builtin_fabsf(__builtin_fabsf(y0 - q0) - 0.5f);
+  const float e1 = __builtin_fabsf(__builtin_fabsf(y1 - q1) - 0.5f);
+  const float e2 = __builtin_fabsf(__builtin_fabsf(y2 - q2) - 0.5f);
+  const float e3 = __builtin_fabsf(__builtin_fabsf(y3 - q3) - 0.5f);
+  const bool nb = __builtin_fminf(__builtin_fminf(e0, e1), __builtin_fminf(e2, e3)) < delta;
+  if (__builtin_expect(nb, 0)) {   // rare: decide the rounding with the exact IEEE quotient
+    q0 = __builtin_rintf(v.x / s); q1 = __builtin_rintf(v.y / s);
+    q2 = __builtin_rintf(v.z / s); q3 = __builtin_rintf(v.w / s);
+  }
+  q0 = __builtin_amdgcn_fmed3f(q0, qlo, qhi);
+  q1 = __builtin_amdgcn_fmed3f(q1, qlo, qhi);
+  q2 = __builtin_amdgcn_fmed3f(q2, qlo, qhi);
+  q3 = __builtin_amdgcn_fmed3f(q3, qlo, qhi);
+  const float d0 = v.x - q0 * s, d1 = v.y - q1 * s, d2 = v.z - q2 * s, d3 = v.w - q3 * s;
+  const float gq = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  return to_fixed(gq, K);
+}
+
 // ---------------------------------------------------------------------------
 // Canonical SSE of a candidate list over one chunk of quads held in LDS (stage 2 of
 // the search, or the exhaustive sweep when list == nullptr: candidates 0..nc-1).
@@ -274,26 +309,7 @@ __device__ __forceinline__ void sse_group(const float4* __restrict__ xs, int nqc
   const float rcp = 1.0f / s;
   unsigned long long acc = 0;
   for (int k = wsub * S + stream; k < nqc; k += wpg * S) {
-    const float4 v = xs[k];
-    const float y0 = v.x * rcp, y1 = v.y * rcp, y2 = v.z * rcp, y3 = v.w * rcp;
-    float q0 = __builtin_rintf(y0), q1 = __builtin_rintf(y1), q2 = __builtin_rintf(y2), q3 = __builtin_rintf(y3);
-    // distance of each y to the nearest half-integer; one compare per quad
-    const float e0 = __builtin_fabsf(__builtin_fabsf(y0 - q0) - 0.5f);
-    const float e1 = __builtin_fabsf(__builtin_fabsf(y1 - q1) - 0.5f);
-    const float e2 = __builtin_fabsf(__builtin_fabsf(y2 - q2) - 0.5f);
-    const float e3 = __builtin_fabsf(__builtin_fabsf(y3 - q3) - 0.5f);
-    const bool nb = __builtin_fminf(__builtin_fminf(e0, e1), __builtin_fminf(e2, e3)) < delta;
-    if (__builtin_expect(nb, 0)) {   // rare: decide the rounding with the exact IEEE quotient
-      q0 = __builtin_rintf(v.x / s); q1 = __builtin_rintf(v.y / s);
-      q2 = __builtin_rintf(v.z / s); q3 = __builtin_rintf(v.w / s);
-    }
-    q0 = __builtin_amdgcn_fmed3f(q0, qlo, qhi);
-    q1 = __builtin_amdgcn_fmed3f(q1, qlo, qhi);
-    q2 = __builtin_amdgcn_fmed3f(q2, qlo, qhi);
-    q3 = __builtin_amdgcn_fmed3f(q3, qlo, qhi);
-    const float d0 = v.x - q0 * s, d1 = v.y - q1 * s, d2 = v.z - q2 * s, d3 = v.w - q3 * s;
-    const float gq = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-    acc += to_fixed(gq, K);
+    acc += sse_quad(xs[k], s, rcp, qlo, qhi, delta, K);
   }
   for (int off = p2; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
   if (active && stream == 0) atomicAdd(&sse[c], acc);

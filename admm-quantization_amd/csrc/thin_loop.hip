@@ -396,11 +396,17 @@ void launch_thin_solve(const ProbDesc* d, const ThinLoopUnit* units, int nunits,
 // X and max, barrier 1 + max load, threshold table, stage-1 inserts, stage-1 sums + flush,
 // barrier 2, team bins load, suffix sums + bounds + S, stage 2, finalize, barrier 3, slot
 // reset, stop test, iterations}
-// Diagnostics (admmq_debug_set_sel_widen): every candidate stays in S (stage 2 every
-// iteration; the same exact answer)
+// Diagnostics (admmq_debug_set_sel_widen): 1: every candidate stays in S; 2: S plus the
+// kSelWindow candidates either side of the first stage-1 minimum (stage 2 every iteration, in
+// its list form; the same exact answer). Value 2 launches an instantiation of its own
+// (k_thin_loop<..., true>): its window code inside the default kernel, even on a branch never
+// taken, cost the loop 0.1 - 0.9 ms per C3 step (register allocation around the selection).
 __device__ int g_sel_widen_tl = 0;
+static int g_sel_widen_tl_host = 0;
 int set_sel_widen_thin(int on) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_sel_widen_tl), &on, sizeof(int)) == hipSuccess ? 0 : -1;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_sel_widen_tl), &on, sizeof(int)) != hipSuccess) return -1;
+  g_sel_widen_tl_host = on;
+  return 0;
 }
 constexpr int kTLTraceMax = 1024;
 constexpr int kTLPhases = 16;
@@ -450,7 +456,7 @@ size_t thin_loop_lds_bytes(int region_a, int ncand, int bits) {
   return tl_off_H2(region_a, 1 << (bits - 1), ncand) + (size_t)(ncand + 1) * 8;
 }
 
-template <int NR, int QMAX>
+template <int NR, int QMAX, bool WINDOW = false>
 __global__ __launch_bounds__(kTLThreads) void k_thin_loop(const ProbDesc* __restrict__ d,
                                                           const ThinLoopUnit* __restrict__ units,
                                                           ThinSync* __restrict__ syncs, int region_a, int n_iter,
@@ -702,6 +708,31 @@ __global__ __launch_bounds__(kTLThreads) void k_thin_loop(const ProbDesc* __rest
           }
         }
         if (lane == 0) s_wcnt[0] = (int)tot;
+        // diagnostics, value 2 of the knob (its own instantiation): the list again, as S plus
+        // the window around the first minimum
+        if constexpr (WINDOW) {
+          unsigned mine = 0x7fffffffu;
+#pragma unroll
+          for (int j = 3; j >= 0; --j)
+            if (4 * lane + j < n && hi[j] == mn) mine = (unsigned)(4 * lane + j);
+          const int cmin = (int)wave_min_u32(mine);
+          unsigned cnt2 = 0u;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            cnt2 += (4 * lane + j < n && (lo[j] <= mn || sel_widened(2, 4 * lane + j, cmin))) ? 1u : 0u;
+          const unsigned suf2 = wave_suffix_u32(cnt2);
+          const unsigned tot2 = __builtin_amdgcn_readfirstlane(suf2);
+          int pos2 = (int)(tot2 - suf2);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int c = 4 * lane + j;
+            if (c < n && (lo[j] <= mn || sel_widened(2, c, cmin))) {
+              if (pos2 < kMaxSel) lsel[2 + pos2] = c;
+              ++pos2;
+            }
+          }
+          if (lane == 0) s_wcnt[0] = (int)tot2;
+        }
       }
       __syncthreads();
       const int total = s_wcnt[0];
@@ -852,15 +883,19 @@ int launch_thin_loop(const ProbDesc* d, const ThinLoopUnit* units, int nunits, T
                        bits, wait_polls);
     return 0;
   };
-#define ADMMQ_TL(NRV)                            \
+#define ADMMQ_TL(NRV, W)                         \
   switch (bits) {                                \
-    case 2: return run(k_thin_loop<NRV, 2>);     \
-    case 3: return run(k_thin_loop<NRV, 4>);     \
-    case 4: return run(k_thin_loop<NRV, 8>);     \
-    default: return run(k_thin_loop<NRV, 16>);   \
+    case 2: return run(k_thin_loop<NRV, 2, W>);     \
+    case 3: return run(k_thin_loop<NRV, 4, W>);     \
+    case 4: return run(k_thin_loop<NRV, 8, W>);     \
+    default: return run(k_thin_loop<NRV, 16, W>);   \
   }
-  if (NRv == 9) { ADMMQ_TL(9) }
-  ADMMQ_TL(16)
+#define ADMMQ_TLW(W)             \
+  if (NRv == 9) { ADMMQ_TL(9, W) } \
+  ADMMQ_TL(16, W)
+  if (g_sel_widen_tl_host == 2) { ADMMQ_TLW(true) }
+  ADMMQ_TLW(false)
+#undef ADMMQ_TLW
 #undef ADMMQ_TL
 }
 

@@ -509,6 +509,11 @@ int32_t admmq_epc_end64(int64_t m, int64_t n, double* mu, int32_t* info, void* w
 int32_t admmq_cp_colnorm64(const double* A, int64_t rowsA, const double* B, int64_t rowsB, int64_t R, double* outA,
                            double* outB, void* stream);
 
+/* Diagnostics: the multi-candidate MSE selections (|S| > 1) whose canonical-SSE sweep the fused
+ * search + finalize launch shared among the job's workgroups, since the last reset (a host
+ * read of a device counter: synchronises); reset != 0 zeroes it. -1 on a HIP error. */
+int64_t admmq_debug_shared_stage2_count(int32_t reset);
+
 /* Library version (major*10000 + minor*100 + patch) and the last error text of this thread. */
 int32_t admmq_version(void);
 const char* admmq_last_error(void);
