@@ -19,6 +19,8 @@ from .admm import admm_iteration, admm_iteration_batched, init_factors, init_fac
 from .quantization import quantize_tensor, quantize_tensor_mse, min_max_quantize, fixed_quantize, quantize_batched  # noqa: F401
 from .packed import PackedTensor, quantize_packed, dequantize_packed, save_packed, load_packed  # noqa: F401
 from .packed import packed_linear, packed_conv1x1, packed_depthwise_conv1x1  # noqa: F401
+from .packed import QuantizedActivation, act_encode, act_decode, packed_rowsums  # noqa: F401
+from .packed import packed_linear_int, packed_conv1x1_int  # noqa: F401
 from .utils import unfold  # noqa: F401
 
 __version__ = "0.1.0"

@@ -19,6 +19,8 @@ the CP builders accept them in place of float tensors: the 1x1 convs / linears t
 ``PackedConv1x1`` / ``PackedLinear``, which keep the codes and run ``k_packed_gemm`` on them
 (inference only); no float32 copy of such a factor is ever made. ``fused=True`` replaces a
 3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``).
+``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
+activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
 """
 from __future__ import annotations
 
@@ -30,7 +32,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .packed import PackedTensor, _meta_words, _pair, _weight_dims, load_packed, packed_bytes, packed_dwgemm, packed_gemm
+from .packed import (PackedTensor, _int_weight_dims, _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed,
+                     packed_bytes, packed_dwgemm, packed_gemm, packed_rowsums)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -209,6 +212,91 @@ class PackedDepthwiseConv1x1(_PackedWeight):
                 f"padding={self.padding}{m}")
 
 
+class IntegerPackedPair(nn.Module):
+    """A 2-way packed layer that stays in integers from its first stage to its last:
+    the float input is encoded once by ``in_act`` (``k_act_encode``), stage 1 runs from codes to
+    the codes of its output under the inter-stage quantizer, stage 2 from those codes to a float
+    output (quantized where the stage has an output quantizer) - both on ``k_packed_igemm``. The
+    children keep the float layer's names and are its ``PackedConv1x1`` / ``PackedLinear`` stages
+    (stage 1's output quantizer is the inter-stage one); ``in_act`` and the weights' integer row
+    sums travel in this module's extra state. ``last_clamped``: the device counters of the two
+    encodings of the last forward (input, inter-stage); no forward reads them."""
+
+    def __init__(self, names, stage1: _PackedWeight, stage2: _PackedWeight, in_act):
+        super().__init__()
+        self._names = tuple(names)
+        self.add_module(names[0], stage1)
+        self.add_module(names[1], stage2)
+        self._in_act = in_act   # (bits, mn, rng), resolved float32 values
+        self._rs = [None, None]
+        self.last_clamped = None
+        if stage1.codes.device.type == "cuda":
+            self._rowsums(0), self._rowsums(1)
+
+    def _stage(self, i):
+        return getattr(self, self._names[i])
+
+    def _rowsums(self, i):
+        st = self._stage(i)
+        if self._rs[i] is None:
+            self._rs[i] = packed_rowsums(st.packed(), st.transpose)
+        elif self._rs[i].device != st.codes.device:
+            self._rs[i] = self._rs[i].to(st.codes.device)
+        return self._rs[i]
+
+    def get_extra_state(self):
+        return dict(in_act=list(self._in_act), rowsums=[None if r is None else r.detach().cpu() for r in self._rs])
+
+    def set_extra_state(self, state):
+        a = state["in_act"]
+        self._in_act = (int(a[0]), float(a[1]), float(a[2]))
+        rs = []
+        for i, r in enumerate(state.get("rowsums") or [None, None]):
+            if r is not None and (r.dtype != torch.int32 or tuple(r.shape) != (self._stage(i).out_features,)):
+                raise ValueError(f"integer layer state: row sums of stage {i + 1} must be int32 "
+                                 f"[{self._stage(i).out_features}], got {r.dtype} {tuple(r.shape)}")
+            rs.append(r)
+        self._rs = rs
+
+    @torch.compiler.disable
+    def forward(self, x):
+        s1, s2 = self._stage(0), self._stage(1)
+        if isinstance(s1, PackedConv1x1):
+            if s1.padding != (0, 0):
+                x = nn.functional.pad(x, (s1.padding[1], s1.padding[1], s1.padding[0], s1.padding[0]))
+            if s1.stride != (1, 1):
+                x = x[:, :, ::s1.stride[0], ::s1.stride[1]]
+        xq = act_encode(x, _lib.ActQ(self._in_act[0], 1, self._in_act[1], self._in_act[2]), check=False)
+        mid = s1._act
+        if mid is None or not 2 <= mid[0] <= 8:
+            raise ValueError("integer layer: stage 1 needs its output quantizer with 2 <= bits <= 8 (it writes codes)")
+        h = _igemm(s1.codes, s1._meta, s1.transpose, s1.out_features, s1.in_features, xq.codes, self._in_act, self._rowsums(0),
+                   s1._layout, s1.bias, mid, True)
+        self.last_clamped = (xq.clamped, h.clamped)
+        return _igemm(s2.codes, s2._meta, s2.transpose, s2.out_features, s2.in_features, h.codes, mid, self._rowsums(1),
+                      s2._layout, s2.bias, s2._act if s2._act is not None else (0, 0.0, 0.0), False)
+
+    def extra_repr(self):
+        return f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]})"
+
+
+def _integer_pair(who, names, factors, acts, in_act, make):
+    """``integer=True`` of a 2-way builder: argument checks, then the pair over ``make()``'s two stages."""
+    if not _is_packed(factors):
+        raise ValueError(f"{who}: integer=True needs PackedTensor factors (the integer stages run from packed codes)")
+    if in_act is None:
+        raise ValueError(f"{who}: integer=True needs in_act, the (bits, min_val, max_val) quantizer of the layer's input")
+    if acts[0] is None:
+        raise ValueError(f"{who}: integer=True needs the inter-stage entry of act_quant (stage 1 writes codes)")
+    for a, what in ((in_act, "in_act"), (acts[0], "the inter-stage quantizer")):
+        if not 2 <= int(a[0]) <= 8:
+            raise ValueError(f"{who}: {what} needs 2 <= bits <= 8 for activation codes, got {a[0]}")
+    stage1, stage2 = make()
+    for st in (stage1, stage2):
+        _int_weight_dims(st.packed(), st.transpose, who)
+    return IntegerPackedPair(names, stage1, stage2, _PackedWeight._resolve_act(*in_act))
+
+
 def _stage_acts(act_quant, n, who):
     """``act_quant`` as a list of ``n`` entries ``(bits, min_val, max_val)`` or ``None`` (``None``: no quantizers)."""
     if act_quant is None:
@@ -333,10 +421,16 @@ def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: O
 
 
 def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
-                        cout: int, padding, stride, act_quant=None) -> nn.Sequential:
+                        cout: int, padding, stride, act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
     """1x1 (cin -> R, with the original padding/stride) -> 1x1 (R -> cout); source/models.py:54-77.
-    ``PackedTensor`` factors: both stages become ``PackedConv1x1`` (B transposed, A)."""
+    ``PackedTensor`` factors: both stages become ``PackedConv1x1`` (B transposed, A).
+    ``integer`` (``PackedTensor`` factors, ``in_act = (bits, min_val, max_val)`` of the input and the
+    ``conv1`` entry of ``act_quant``, both with bits 2..8): an ``IntegerPackedPair`` of the same two stages."""
     acts = _stage_acts(act_quant, 2, "build_cp2conv_layer")   # [conv1, conv2], as build_cp_layer's
+    if integer:
+        return _integer_pair("build_cp2conv_layer", ("conv1", "conv2"), factors, acts, in_act,
+                             lambda: tuple(_packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride,
+                                                                 acts).children()))
     if _is_packed(factors):
         return _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride, acts)
     dev = factors[0].device if factors else None
@@ -360,10 +454,14 @@ def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bi
 
 
 def build_cpfc_layer(rank: int, factors: Sequence[torch.Tensor], bias: Optional[torch.Tensor], fin: int,
-                     fout: int, act_quant=None) -> nn.Sequential:
+                     fout: int, act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
     """Linear fin -> R (A^T) -> Linear R -> fout (B); source/models.py:80-99 (factors = [B, A]).
-    ``PackedTensor`` factors: both stages become ``PackedLinear`` (A transposed, B)."""
+    ``PackedTensor`` factors: both stages become ``PackedLinear`` (A transposed, B).
+    ``integer``: as ``build_cp2conv_layer``'s, an ``IntegerPackedPair`` of ``fc1`` / ``fc2``."""
     acts = _stage_acts(act_quant, 2, "build_cpfc_layer")   # [fc1, fc2], as build_cp_layer's
+    if integer:
+        return _integer_pair("build_cpfc_layer", ("fc1", "fc2"), factors, acts, in_act,
+                             lambda: tuple(_packed_cpfc_layer(rank, factors, bias, fin, fout, acts).children()))
     if _is_packed(factors):
         return _packed_cpfc_layer(rank, factors, bias, fin, fout, acts)
     B, A = factors

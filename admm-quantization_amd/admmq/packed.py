@@ -12,6 +12,11 @@ a second guess at the float32 result.
 ``packed_depthwise_conv1x1`` runs a depthwise ``k x k`` convolution and the 1x1 convolution by
 such a weight as one kernel (``k_packed_dwgemm``: the tensor between them is never written).
 
+``act_encode`` turns a float activation into ``QuantizedActivation`` codes (one uint8 per element, the
+fixed-range quantizer's level clamped to ``0 .. 2^bits - 1``), and ``packed_linear_int`` /
+``packed_conv1x1_int`` multiply such codes by a packed weight in integer arithmetic
+(``k_packed_igemm``: int8 MFMA, exact int32 sums, one double-precision epilogue).
+
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
 """
@@ -26,7 +31,9 @@ import torch
 from . import _lib
 
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
-           "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1"]
+           "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
+           "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
+           "packed_conv1x1_int"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -324,6 +331,281 @@ def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tens
     if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
         x = x[:, :, ::sh, ::sw]
     return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias, act)
+
+
+# --- integer route -------------------------------------------------------------
+INT_K_MAX = 65536   # 128 * 255 * K must stay below 2^31
+
+
+def _code_act(act, who: str) -> "_lib.ActQ":
+    """The C record of a code quantizer ``act = (bits, min_val, max_val)`` (or a record): bits 2..8."""
+    if act is None:
+        raise ValueError(f"{who}: an activation quantizer (bits, min_val, max_val) is needed")
+    q = _act_record(act)
+    if not 2 <= int(q.bits) <= 8:
+        raise ValueError(f"{who}: activation codes need 2 <= bits <= 8, got {q.bits} (1 bit has three output "
+                         "values and no code form)")
+    return q
+
+
+@dataclass
+class QuantizedActivation:
+    """An activation as codes: ``codes`` uint8 of the float tensor's shape, ``x = (u * rng) / n + mn``
+    with ``n = 2^bits - 1`` (``mn`` / ``rng`` float32 values held as Python floats). ``clamped``: an
+    int32 ``[1]`` tensor on the codes' device, the number of elements whose level lay outside
+    ``0 .. n`` (or was NaN) and was clamped when the codes were made."""
+    codes: torch.Tensor
+    bits: int
+    mn: float
+    rng: float
+    clamped: Optional[torch.Tensor] = None
+
+    def dequantize(self) -> torch.Tensor:
+        """float32 tensor of the codes' shape (``k_act_decode``): where nothing was clamped, the
+        bits of ``fixed_quantize`` on the encoded tensor."""
+        return act_decode(self.codes, self.bits, self.mn, self.rng)
+
+
+def act_encode(x: torch.Tensor, act, check: bool = True) -> QuantizedActivation:
+    """The codes of ``x`` under ``act = (bits, min_val, max_val)`` (bits 2..8; the range by
+    ``act_range``): the level ``fixed_quantize`` computes, clamped to ``0 .. 2^bits - 1``.
+    ``check``: one host read, and a ``ValueError`` when any element was clamped (the clamp is the
+    one difference from the clamp-free quantizer); ``check=False`` makes no sync and leaves the
+    count in ``.clamped`` on the device. Inference only."""
+    q = _code_act(act, "act_encode")
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: act_encode is inference only (no backward through the quantizer): call it under "
+                           "torch.no_grad() or detach x")
+    _lib.require_device(x)
+    if torch.compiler.is_compiling():
+        return _opaque_act_encode(x, q, check)
+    xc = x.detach().contiguous()
+    if _lib.use_ops():   # torch.ops.admmq.act_encode (csrc/torch_ops.cpp) -> admmq_act_encode
+        codes, clamped = _lib.ops().act_encode(xc, q.bits, q.mn, q.rng)
+    else:
+        codes = torch.empty(xc.shape, dtype=torch.uint8, device=xc.device)
+        clamped = torch.zeros(1, dtype=torch.int32, device=xc.device)
+        if xc.numel():
+            _lib.check(_lib.load().admmq_act_encode(_lib.ptr(xc), _lib.ptr(codes), xc.numel(), ctypes.byref(q),
+                                                    _lib.ptr(clamped), _lib.stream_handle(xc.device)), "act_encode")
+    if check:
+        n = int(clamped.item())
+        if n:
+            raise ValueError(f"act_encode: {n} element(s) lie outside the quantizer's range [mn, mn + rng] (or are NaN) "
+                             "and were clamped; pass check=False to accept the clamp")
+    return QuantizedActivation(codes, int(q.bits), float(q.mn), float(q.rng), clamped)
+
+
+_opaque_act_encode = torch.compiler.disable(act_encode)
+
+
+def act_decode(codes: torch.Tensor, bits: int, mn: float, rng: float) -> torch.Tensor:
+    """``(float(u) * rng) / n + mn`` in float32 for every code (``k_act_decode``)."""
+    q = _code_act(_lib.ActQ(int(bits), 1, float(mn), float(rng)), "act_decode")
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8:
+        raise TypeError("act_decode: codes must be a uint8 tensor")
+    if codes.device.type != "cuda":
+        raise RuntimeError("admmq: activation codes must live on a ROCm GPU (device 'cuda'); the MI355X path has no "
+                           "CPU implementation")
+    cc = codes.contiguous()
+    if _lib.use_ops():
+        return _lib.ops().act_decode(cc, q.bits, q.mn, q.rng)
+    y = torch.empty(cc.shape, dtype=torch.float32, device=cc.device)
+    if cc.numel():
+        _lib.check(_lib.load().admmq_act_decode(_lib.ptr(cc), _lib.ptr(y), cc.numel(), ctypes.byref(q),
+                                                _lib.stream_handle(cc.device)), "act_decode")
+    return y
+
+
+def _int_weight_dims(p: "PackedTensor", transpose: bool, who: str) -> Tuple[int, int]:
+    """``_weight_dims`` plus the integer route's refusals (all on the host)."""
+    M, K = _weight_dims(p, transpose)
+    if p.qscheme == "tensor_minmax":
+        raise ValueError(f"{who}: tensor_minmax weights have no integer form (their de-quantization is not "
+                         "scale * integer)")
+    q = 1 << (int(p.bits) - 1)
+    zp = int(p.zero_point) if p.qscheme == "tensor_affine" else 0
+    if -q - zp < -128 or q - 1 - zp > 127:
+        raise ValueError(f"{who}: zero_point {zp} puts (u - {q}) - zero_point outside int8")
+    if K > INT_K_MAX:
+        raise ValueError(f"{who}: K = {K} is past the integer route's limit of {INT_K_MAX}")
+    return M, K
+
+
+def _int_plan(p: "PackedTensor", transpose: bool, who: str) -> list:
+    """``[M, K, row sums or None]`` of ``p`` in one orientation, kept on ``p`` while its codes and the
+    fields they depend on are unchanged (the way the meta words are): the host refusals run once."""
+    codes = p.codes
+    c = getattr(p, "_ip", None)
+    if c is None or c[2] is not codes or c[3] != codes._version or \
+            c[0] != (p.qscheme, p.bits, p.zero_point, p.shape, p.bad):
+        c = p._ip = ((p.qscheme, p.bits, p.zero_point, p.shape, p.bad), {}, codes, codes._version)
+    e = c[1].get(transpose)
+    if e is None:
+        e = c[1][transpose] = [*_int_weight_dims(p, transpose, who), None]
+    return e
+
+
+def packed_rowsums(p: "PackedTensor", transpose: bool = False) -> torch.Tensor:
+    """``A[m] = sum_k a[m, k]`` (int32 ``[M]``) of the integer weight ``a = (u - q) - zero_point`` of
+    ``p`` (``transpose``: of its transpose), by ``k_packed_rowsum``; kept on ``p`` while its codes
+    and fields are unchanged, the way the meta words are."""
+    e = _int_plan(p, bool(transpose), "packed_rowsums")
+    if e[2] is None:
+        if p.codes.device.type != "cuda":
+            raise RuntimeError("admmq: packed codes must live on a ROCm GPU (device 'cuda'); the MI355X path has no "
+                               "CPU implementation")
+        e[2] = _rowsums(p.codes, _meta_words(p), bool(transpose), e[0], e[1])
+    return e[2]
+
+
+@torch.compiler.disable
+def _rowsums(codes, meta_words, transpose, M, K):
+    if _lib.use_ops():
+        return _lib.ops().packed_rowsums(codes, meta_words, transpose, M, K)
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    A = torch.empty(M, dtype=torch.int32, device=cc.device)
+    _lib.check(_lib.load().admmq_packed_rowsums(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(A),
+                                                _lib.stream_handle(cc.device)), "packed_rowsums")
+    return A
+
+
+def _in_triple(xq, who: str) -> Tuple[int, float, float]:
+    """``(bits, mn, rng)`` of the input codes' quantizer, checked."""
+    if not isinstance(xq, QuantizedActivation):
+        raise TypeError(f"{who}: xq must be a QuantizedActivation (act_encode makes one)")
+    bits = int(xq.bits)
+    if not 2 <= bits <= 8:
+        raise ValueError(f"{who}: activation codes need 2 <= bits <= 8, got {bits} (1 bit has three output values "
+                         "and no code form)")
+    return bits, float(xq.mn), float(xq.rng)
+
+
+def _out_triple(act, out_codes: bool, who: str) -> Tuple[int, float, float]:
+    """``(bits, mn, rng)`` of the output quantizer (bits 0: none), checked; ``act`` as ``packed_gemm``'s."""
+    if act is None:
+        if out_codes:
+            raise ValueError(f"{who}: out_codes=True needs act (the output's quantizer)")
+        return 0, 0.0, 0.0
+    q = _act_record(act)
+    if out_codes and not 2 <= int(q.bits) <= 8:
+        raise ValueError(f"{who}: activation codes need 2 <= bits <= 8, got {q.bits} (1 bit has three output values "
+                         "and no code form)")
+    return int(q.bits), float(q.mn), float(q.rng)
+
+
+def packed_igemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int,
+                 xq: QuantizedActivation, rowsums: torch.Tensor, x_layout: int, bias: Optional[torch.Tensor] = None,
+                 act=None, out_codes: bool = False):
+    """``packed_gemm`` on activation codes in integer arithmetic (``admmq_packed_igemm``): ``xq`` holds
+    the uint8 codes of ``x`` and their quantizer, ``rowsums`` is ``packed_rowsums`` of the same weight
+    and orientation. The result is a float tensor (quantized by ``act`` when given) or, with
+    ``out_codes=True`` (needs ``act``, bits 2..8), a ``QuantizedActivation`` whose codes were formed
+    in the kernel's epilogue and whose ``clamped`` count stays on the device. Inference only."""
+    x3 = _in_triple(xq, "packed_igemm")
+    o3 = _out_triple(act, out_codes, "packed_igemm")
+    return _igemm(codes, meta_words, bool(transpose), int(M), int(K), xq.codes, x3, rowsums, int(x_layout), bias, o3,
+                  bool(out_codes))
+
+
+def _igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o3, out_codes):
+    """The call behind ``packed_igemm`` on checked quantizers ``x3`` / ``o3 = (bits, mn, rng)``."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise TypeError("packed_igemm: xq.codes must be a uint8 tensor")
+    if x.device.type != "cuda" or codes.device.type != "cuda":
+        raise RuntimeError("admmq: packed_igemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
+                           "the MI355X path has no CPU implementation")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o3, out_codes)
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_igemm (csrc/torch_ops.cpp) -> admmq_packed_igemm
+        y, clamped = _lib.ops().packed_igemm(codes, meta_words, transpose, M, K, x, x3[0], x3[1], x3[2], rowsums,
+                                             x_layout, bias, o3[0], o3[1], o3[2], out_codes)
+    else:
+        lib = _lib.load()
+        if x_layout == 0:
+            if x.dim() < 3 or x.shape[1] != K:
+                raise ValueError(f"packed_igemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
+            oshape = (x.shape[0], M) + tuple(x.shape[2:])
+            nb = int(x.shape[0])
+        elif x_layout == 1:
+            if x.dim() < 1 or x.shape[-1] != K:
+                raise ValueError(f"packed_igemm: x must be [..., {K}], got {tuple(x.shape)}")
+            oshape = tuple(x.shape[:-1]) + (M,)
+            nb = 1
+        else:
+            raise ValueError("packed_igemm: x_layout must be 0 or 1")
+        xc = x.contiguous()
+        if xc.numel() == 0:
+            raise ValueError("packed_igemm: empty x")
+        N = xc.numel() // (nb * K)
+        cc = codes.contiguous()
+        if cc.data_ptr() % 16:
+            cc = cc.clone()
+        meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+        bc = None
+        if bias is not None:
+            _lib.require_device(bias)
+            if tuple(bias.shape) != (M,):
+                raise ValueError(f"packed_igemm: bias must be [{M}], got {tuple(bias.shape)}")
+            bc = bias.contiguous()
+        if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
+            raise ValueError(f"packed_igemm: rowsums must be int32 [{M}]")
+        xr = _lib.ActQ(x3[0], 1, x3[1], x3[2])
+        oq = _lib.ActQ(o3[0], 1, o3[1], o3[2]) if o3[0] else None
+        y = torch.empty(oshape, dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
+        clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
+        nbytes = lib.admmq_packed_igemm_workspace_size(M, K, N, nb)
+        ws = _lib.workspace(nbytes, x.device)
+        rc = lib.admmq_packed_igemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc),
+                                    ctypes.byref(xr), _lib.ptr(rowsums.contiguous()), x_layout, N, nb, _lib.ptr(bc),
+                                    _lib.ptr(None if out_codes else y), _lib.ptr(y if out_codes else None),
+                                    ctypes.byref(oq) if oq is not None else None,
+                                    _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), ws.numel(),
+                                    _lib.stream_handle(x.device))
+        _lib.check(rc, "packed_igemm")
+    if out_codes:
+        return QuantizedActivation(y, o3[0], o3[1], o3[2], clamped)
+    return y
+
+
+_opaque_igemm = torch.compiler.disable(_igemm)
+
+
+def packed_linear_int(xq: QuantizedActivation, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
+                      transpose: bool = False, act=None, out_codes: bool = False):
+    """``packed_linear`` on activation codes, in integer arithmetic: ``xq.codes [..., K] -> [..., M]``
+    (a float tensor, or with ``out_codes=True`` - which needs ``act`` - a ``QuantizedActivation``).
+    The weight's row sums are computed on the first call and kept on ``p``."""
+    transpose = bool(transpose)
+    e = _int_plan(p, transpose, "packed_linear_int")
+    o3 = _out_triple(act, out_codes, "packed_linear_int")
+    x3 = _in_triple(xq, "packed_linear_int")
+    rs = e[2] if e[2] is not None else packed_rowsums(p, transpose)
+    return _igemm(p.codes, _meta_words(p), transpose, e[0], e[1], xq.codes, x3, rs, 1, bias, o3, bool(out_codes))
+
+
+def packed_conv1x1_int(xq: QuantizedActivation, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
+                       transpose: bool = False, stride=1, act=None, out_codes: bool = False):
+    """``packed_conv1x1`` on activation codes, in integer arithmetic: ``xq.codes [n, K, H, W] ->
+    [n, M, H', W']``. The stride sub-samples the code tensor."""
+    transpose = bool(transpose)
+    e = _int_plan(p, transpose, "packed_conv1x1_int")
+    o3 = _out_triple(act, out_codes, "packed_conv1x1_int")
+    x3 = _in_triple(xq, "packed_conv1x1_int")
+    x = xq.codes
+    if x.dim() != 4:
+        raise ValueError(f"packed_conv1x1_int: x must be [n, {e[1]}, H, W], got {tuple(x.shape)}")
+    if stride != 1:
+        sh, sw = (stride, stride) if isinstance(stride, int) else tuple(stride)
+        if (sh, sw) != (1, 1):
+            x = x[:, :, ::sh, ::sw]
+    rs = e[2] if e[2] is not None else packed_rowsums(p, transpose)
+    return _igemm(p.codes, _meta_words(p), transpose, e[0], e[1], x, x3, rs, 0, bias, o3, bool(out_codes))
 
 
 def _pair(v, name: str) -> Tuple[int, int]:

@@ -11,6 +11,7 @@
 //   admmq::packed_gemm             a packed weight times float32 activations
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
+//   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -426,6 +427,145 @@ at::Tensor fixed_quantize_meta(const at::Tensor& x, int64_t bits, double mn, dou
   return at::empty(x.sizes(), x.options().dtype(at::kFloat));
 }
 
+// --- integer packed GEMM ---------------------------------------------------------
+// Activation codes (uint8, the float tensor's shape), the row sums of a packed weight and the
+// int8-MFMA GEMM over codes (admmq_act_encode / _decode, admmq_packed_rowsums, admmq_packed_igemm).
+// `clamped` is an int32 [1] tensor on the device: the ops make no host read. Inference only.
+admmq_actq codeq_of(int64_t bits, double mn, double rng, const char* what) {
+  TORCH_CHECK(bits >= 2 && bits <= 8, "admmq: ", what, ": activation code bits must be 2..8, got ", bits);
+  return actq_of(bits, mn, rng, what);
+}
+
+std::tuple<at::Tensor, at::Tensor> act_encode_cuda(const at::Tensor& x, int64_t bits, double mn, double rng) {
+  check_f32_device(x, "x");
+  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
+              "admmq: act_encode is inference only (no backward through the quantizer): call it under "
+              "torch.no_grad() or detach x");
+  const admmq_actq q = codeq_of(bits, mn, rng, "act_encode");
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  at::Tensor codes = at::empty(xc.sizes(), xc.options().dtype(at::kByte));
+  at::Tensor clamped = at::empty({1}, xc.options().dtype(at::kInt));
+  if (xc.numel() == 0) return {codes, clamped.zero_()};
+  check_rc(admmq_act_encode(xc.data_ptr<float>(), codes.data_ptr<uint8_t>(), xc.numel(), &q, clamped.data_ptr<int32_t>(),
+                            stream_of(xc)),
+           "act_encode");
+  return {codes, clamped};
+}
+
+std::tuple<at::Tensor, at::Tensor> act_encode_meta(const at::Tensor& x, int64_t bits, double mn, double rng) {
+  (void)codeq_of(bits, mn, rng, "act_encode");
+  return {at::empty(x.sizes(), x.options().dtype(at::kByte)), at::empty({1}, x.options().dtype(at::kInt))};
+}
+
+at::Tensor act_decode_cuda(const at::Tensor& codes, int64_t bits, double mn, double rng) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte, "admmq: act_decode: codes must be a uint8 tensor on the GPU");
+  const admmq_actq q = codeq_of(bits, mn, rng, "act_decode");
+  const c10::DeviceGuard guard(codes.device());
+  const at::Tensor cc = codes.contiguous();
+  at::Tensor y = at::empty(cc.sizes(), cc.options().dtype(at::kFloat));
+  if (cc.numel() == 0) return y;
+  check_rc(admmq_act_decode(cc.data_ptr<uint8_t>(), y.data_ptr<float>(), cc.numel(), &q, stream_of(cc)), "act_decode");
+  return y;
+}
+
+at::Tensor act_decode_meta(const at::Tensor& codes, int64_t bits, double mn, double rng) {
+  (void)codeq_of(bits, mn, rng, "act_decode");
+  return at::empty(codes.sizes(), codes.options().dtype(at::kFloat));
+}
+
+// the host meta record and the 16-byte aligned code stream of a packed weight
+at::Tensor packed_weight_of(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const char* what,
+                            admmq_qmeta& meta) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1, "admmq: ", what,
+              ": codes must be a 1-D uint8 tensor on the GPU");
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8, "admmq: ",
+              what, ": meta_words must be the 8 int32 words of the meta record on the CPU");
+  TORCH_CHECK(M > 0 && K > 0, "admmq: ", what, ": M and K must be positive");
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: ", what, ": bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: ", what, ": a ", M, " x ",
+              K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits), " code bytes, got ",
+              codes.numel());
+  at::Tensor cc = codes.contiguous();
+  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();
+  return cc;
+}
+
+at::Tensor packed_rowsums_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K) {
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_rowsums", meta);
+  const c10::DeviceGuard guard(cc.device());
+  at::Tensor A = at::empty({M}, cc.options().dtype(at::kInt));
+  check_rc(admmq_packed_rowsums(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, A.data_ptr<int32_t>(), stream_of(cc)),
+           "packed_rowsums");
+  return A;
+}
+
+at::Tensor packed_rowsums_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K) {
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_rowsums: M and K must be positive");
+  return at::empty({M}, codes.options().dtype(at::kInt));
+}
+
+std::tuple<at::Tensor, at::Tensor> packed_igemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w,
+                                                     int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits, double x_mn,
+                                                     double x_rng, const at::Tensor& rowsums, int64_t x_layout,
+                                                     const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
+                                                     double out_rng, bool out_codes) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte, "admmq: packed_igemm: x must be a uint8 code tensor on the GPU");
+  const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_igemm");
+  const admmq_actq oq = out_codes ? codeq_of(out_bits, out_mn, out_rng, "packed_igemm") : actq_of(out_bits, out_mn, out_rng, "packed_igemm");
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_igemm", meta);
+  check_same_device(codes, x, "codes");
+  TORCH_CHECK(rowsums.is_cuda() && rowsums.scalar_type() == at::kInt && rowsums.dim() == 1 && rowsums.size(0) == M,
+              "admmq: packed_igemm: rowsums must be an int32 [", M, "] tensor on the GPU");
+  check_same_device(rowsums, x, "rowsums");
+  const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor rc = rowsums.contiguous();
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(!(bias->requires_grad() && at::GradMode::is_enabled()),
+                "admmq: packed_igemm is inference only (no backward through packed weights): call it under "
+                "torch.no_grad() or detach bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_igemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
+  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
+  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_igemm: empty x");
+  at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
+  at::Tensor clamped = at::empty({out_codes ? 1 : 0}, xc.options().dtype(at::kInt));
+  const size_t nbytes = admmq_packed_igemm_workspace_size(M, K, N, static_cast<int32_t>(nb));
+  at::Tensor ws;   // (the serial regime needs none: no allocation)
+  if (nbytes > 0) ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_igemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<uint8_t>(), &xq,
+                              rc.data_ptr<int32_t>(), static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
+                              bc.defined() ? bc.data_ptr<float>() : nullptr, out_codes ? nullptr : y.data_ptr<float>(),
+                              out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq,
+                              out_codes ? clamped.data_ptr<int32_t>() : nullptr, nbytes > 0 ? ws.data_ptr() : nullptr,
+                              nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
+           "packed_igemm");
+  return {y, clamped};
+}
+
+std::tuple<at::Tensor, at::Tensor> packed_igemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w,
+                                                     int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits, double x_mn,
+                                                     double x_rng, const at::Tensor& rowsums, int64_t x_layout,
+                                                     const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
+                                                     double out_rng, bool out_codes) {
+  (void)codeq_of(x_bits, x_mn, x_rng, "packed_igemm");
+  if (out_codes) (void)codeq_of(out_bits, out_mn, out_rng, "packed_igemm");
+  else (void)actq_of(out_bits, out_mn, out_rng, "packed_igemm");
+  return {at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(out_codes ? at::kByte : at::kFloat)),
+          at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
+}
+
 at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
                             const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
@@ -692,6 +832,12 @@ TORCH_LIBRARY(admmq, m) {
         "int sw, int ph, int pw, Tensor? bias, int mid_bits, float mid_mn, float mid_rng, int out_bits, float out_mn, "
         "float out_rng) -> Tensor");
   m.def("fixed_quantize(Tensor x, int bits, float mn, float rng) -> Tensor");
+  m.def("act_encode(Tensor x, int bits, float mn, float rng) -> (Tensor codes, Tensor clamped)");
+  m.def("act_decode(Tensor codes, int bits, float mn, float rng) -> Tensor");
+  m.def("packed_rowsums(Tensor codes, Tensor meta_words, bool trans_w, int M, int K) -> Tensor");
+  m.def("packed_igemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_bits, float x_mn, "
+        "float x_rng, Tensor rowsums, int x_layout, Tensor? bias, int out_bits, float out_mn, float out_rng, "
+        "bool out_codes) -> (Tensor y, Tensor clamped)");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -708,6 +854,10 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_cuda);
   m.impl("fixed_quantize", &fixed_quantize_cuda);
+  m.impl("act_encode", &act_encode_cuda);
+  m.impl("act_decode", &act_decode_cuda);
+  m.impl("packed_rowsums", &packed_rowsums_cuda);
+  m.impl("packed_igemm", &packed_igemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -723,6 +873,10 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("packed_gemm_act", &packed_gemm_act_meta);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_meta);
   m.impl("fixed_quantize", &fixed_quantize_meta);
+  m.impl("act_encode", &act_encode_meta);
+  m.impl("act_decode", &act_decode_meta);
+  m.impl("packed_rowsums", &packed_rowsums_meta);
+  m.impl("packed_igemm", &packed_igemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

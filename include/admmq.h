@@ -289,6 +289,66 @@ int32_t admmq_packed_dwgemm_act(const uint8_t* codes, const admmq_qmeta* meta, i
                                 const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* Integer packed GEMM: activation codes as a tensor of their own, and the
+ * product of a packed weight with such codes in integer arithmetic (v_mfma_i32_32x32x32_i8).
+ *
+ * Activation codes: one uint8 per element, the float tensor's shape and order. The quantizer
+ * is an admmq_actq with bits 2..8 (1 bit has three output values and no code form);
+ * n = float(2^bits - 1).
+ *   encode  r = (x - mn) / rng;  qi = floor(r * n + 0.5f)   (admmq_fixed_quantize's r and qi:
+ *           separately rounded float32 operations, an IEEE division);  u = clamp(qi, 0, n).
+ *           An element whose qi lies outside [0, n] or is NaN is clamped (a NaN encodes as 0)
+ *           and adds 1 to *clamped (device int32, may be NULL; zeroed on the stream first).
+ *   decode  y = ((float)u * rng) / n + mn   in float32.
+ * Where nothing was clamped, decode(encode(x)) has the bits of admmq_fixed_quantize(x). The
+ * clamp is the one deliberate difference from the clamp-free quantizer; the counter shows it.
+ * x, y: device, float aligned; codes: device, any address. ADMMQ_ERR_ARG for NULL x / codes / y,
+ * NULL q or q->on == 0, bits outside 2..8, numel <= 0, misaligned x / y / clamped - before any
+ * launch, each with its own admmq_last_error text. */
+int32_t admmq_act_encode(const float* x, uint8_t* codes, int64_t numel, const admmq_actq* q, int32_t* clamped,
+                         void* stream);
+int32_t admmq_act_decode(const uint8_t* codes, float* y, int64_t numel, const admmq_actq* q, void* stream);
+
+/* Weights: packed codes as admmq_quantize_packed wrote them, schemes mse-minmax, symmetric and
+ * affine. With q = 2^(bits-1): a[m,k] = (uw - q) - zp (zp = 0 unless affine), an integer that
+ * must fit int8; W = scale * a. Activations: x = g * ux + mn_x, g = rng_x / n_x.
+ *   S[m,c] = sum_k a[m,k] ux[k,c]      A[m] = sum_k a[m,k]        (exact integer sums)
+ *   y[m,c] = float( double(scale) * ( (double(rng_x) / double(n_x)) * double(S)
+ *                                     + double(mn_x) * double(A[m]) ) + double(bias[m]) )
+ * every operation in double, rounded separately (no fused multiply-add), one rounding to
+ * float32; without a bias the last term is not added. S is an integer, so the result is the
+ * same bits for every nb, on every call and in both regimes: no summation order is specified.
+ *
+ * admmq_packed_rowsums writes A[m], m < M (device int32), for W = D (trans_w 0, the packed
+ * tensor is [M, K]) or D^T (trans_w 1, it is [K, M]); it runs once per weight and the caller
+ * keeps the result.
+ *
+ * admmq_packed_igemm follows admmq_packed_gemm_act (layouts, trans_w, N, nb, bias, regimes), with
+ * x the uint8 codes of the activations (any address) and x_q their quantizer, rowsums the row
+ * sums of the same weight and orientation, and the output either
+ *   y        float32 (y_codes NULL); with out_q on (bits 1..24): admmq_fixed_quantize of y, or
+ *   y_codes  uint8   (y NULL; out_q on, bits 2..8): encode's code of y, with the same clamped
+ *            counter rule (*clamped, may be NULL, is zeroed on the stream first). Every output
+ *            byte is written by exactly one thread.
+ * `meta` is a HOST record. All refusals come before any launch, each with its own
+ * admmq_last_error text: ADMMQ_ERR_SCHEME for tensor_minmax weights (their de-quantization is
+ * not scale * a); ADMMQ_ERR_ARG for an affine record with -q - zp < -128 or q - 1 - zp > 127,
+ * K > 65536 (128 * 255 * K must stay below 2^31), activation bits outside 2..8, both or neither
+ * of y / y_codes, and admmq_packed_gemm's own refusals (NULL pointers, sizes, bad != 0,
+ * x_layout 1 with nb != 1, misaligned codes / y / bias / rowsums / clamped / workspace);
+ * ADMMQ_ERR_WORKSPACE for a short workspace.
+ * admmq_packed_igemm_workspace_size depends on its arguments only: 0 for arguments out of range
+ * and when none is needed; else the int32 partial images of the K-piece-parallel regime (few
+ * output tiles), which k_packed_ireduce sums. No output is combined with atomics and no
+ * workgroup waits for another. No entry point allocates or synchronises. */
+int32_t admmq_packed_rowsums(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                             int32_t* rowsums, void* stream);
+size_t admmq_packed_igemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t nb);
+int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                           const uint8_t* x, const admmq_actq* x_q, const int32_t* rowsums, int32_t x_layout, int64_t N,
+                           int32_t nb, const float* bias, float* y, uint8_t* y_codes, const admmq_actq* out_q,
+                           int32_t* clamped, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

@@ -227,6 +227,73 @@ int main(void) {
       fails += DWA(&qm, 512, 1141, 2, 2, NULL, NULL, 16) != ADMMQ_ERR_WORKSPACE;
 #undef DWA
     }
+    /* integer packed GEMM: the planner over ragged sizes, then every refusal of
+     * the code, row-sum and GEMM entry points */
+    {
+      const uint8_t* xc = (const uint8_t*)0x10001;
+      uint8_t* yc = (uint8_t*)0x40001;
+      const int32_t* rs = (const int32_t*)0x30000;
+      int32_t* cl = (int32_t*)0x50000;
+      admmq_actq a8 = {8, 1, -1.f, 2.f}, a1 = {1, 1, -1.f, 2.f}, a9 = {9, 1, -1.f, 2.f}, aoff = {8, 0, 0.f, 0.f},
+                 wide = {25, 1, 0.f, 1.f};
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, 6000), K = rnd(1, 70000), N = rnd(1, t % 3 ? 70 : 4000);
+        const int32_t nb = rnd(1, 8);
+        const size_t w = admmq_packed_igemm_workspace_size(M, K, N, nb);
+        fails += w != admmq_packed_igemm_workspace_size(M, K, N, nb);
+        fails += K > 65536 && w != 0;
+      }
+      fails += admmq_packed_igemm_workspace_size(512, 1141, 4, 1) == 0;
+      fails += admmq_packed_igemm_workspace_size(0, 8, 8, 1) != 0;
+      fails += admmq_packed_igemm_workspace_size(8, 65537, 8, 1) != 0;
+      fails += admmq_act_encode(NULL, yc, 8, &a8, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, NULL, 8, &a8, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 8, NULL, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 8, &aoff, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 8, &a1, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 8, &a9, NULL, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 0, &a8, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode((const float*)0x10002, yc, 8, &a8, cl, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_encode(x, yc, 8, &a8, (int32_t*)0x50002, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_decode(NULL, y, 8, &a8, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_decode(xc, NULL, 8, &a8, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_decode(xc, y, 8, &a1, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_decode(xc, y, -1, &a8, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_act_decode(xc, (float*)0x20002, 8, &a8, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_rowsums(NULL, &qm, 0, 8, 8, (int32_t*)rs, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_rowsums(c, &qm, 0, 8, 8, NULL, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_rowsums(c, &qm, 0, 8, 65537, (int32_t*)rs, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_rowsums(c, &qm, 2, 8, 8, (int32_t*)rs, NULL) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX;
+      fails += admmq_packed_rowsums(c, &q2, 0, 8, 8, (int32_t*)rs, NULL) != ADMMQ_ERR_SCHEME;
+#define IG(mm, M, K, xq, N, nb, xl, yy, yyc, oq, wsb) \
+  admmq_packed_igemm(c, mm, 0, M, K, xc, xq, rs, xl, N, nb, NULL, yy, yyc, oq, cl, ws, wsb, NULL)
+      fails += IG(&q2, 8, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_SCHEME;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 1;
+      fails += IG(&q2, 8, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      q2.zero_point = -1;
+      fails += IG(&q2, 8, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      q2.zero_point = 0;
+      fails += IG(&q2, 512, 1141, &a8, 4, 1, 0, y, NULL, NULL, 16) != ADMMQ_ERR_WORKSPACE;
+      q2 = qm; q2.bad = 1;
+      fails += IG(&q2, 8, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(NULL, 8, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, NULL, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a1, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a9, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &aoff, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 65537, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 1, 0, NULL, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 1, 0, y, yc, &a8, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 1, 0, NULL, yc, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 1, 0, NULL, yc, &a9, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 1, 0, y, NULL, &wide, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 8, 8, &a8, 4, 2, 1, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 0, 8, &a8, 4, 1, 0, y, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IG(&qm, 512, 1141, &a8, 4, 1, 0, NULL, yc, &a8, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += IG(&qm, 512, 1141, &a8, 4, 1, 0, y, NULL, NULL, 16) != ADMMQ_ERR_WORKSPACE;
+#undef IG
+    }
   }
   printf("last error: %s\n", admmq_last_error());
   printf("%s (%d failures)\n", fails ? "FAIL" : "OK", fails);
