@@ -165,6 +165,12 @@ def load() -> ctypes.CDLL:
         "admmq_debug_set_legacy_stage1": (I32, [I32]),
         "admmq_debug_set_launch_head": (I32, [I32]),
         "admmq_debug_get_launch_head_default": (I32, []),
+        "admmq_debug_set_spd_form": (I32, [I32]),
+        "admmq_debug_get_spd_form_default": (I32, []),
+        "admmq_debug_set_linv_width": (I32, [I32]),
+        "admmq_debug_linv_width": (I32, [I32]),
+        "admmq_debug_chol_step_work": (I32, [I32, I32, P, I32, P]),
+        "admmq_debug_spd_inverse": (I32, [I32, P, P, ctypes.c_double, P, P, P, P, P, I32, P]),
         "admmq_debug_admm_plan_bytes": (S, [P, I32, I32, P]),
         "admmq_debug_admm_plan_digest": (I32, [P, I32, I32, I32, P, P]),
         "admmq_debug_admm_run_schedule": (I32, [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, P]),
@@ -326,6 +332,73 @@ class sel_widen(_switch):
 
     def _encode(self):
         return self.mode
+
+
+SPD_FUSED_CHOL, SPD_WIDE_LINV, SPD_TILE_MINV = 1, 2, 4
+
+
+class spd_form:
+    """Context manager (diagnostics): which forms of the SPD inverse run (bit 0 the one-launch
+    Cholesky block column, bit 1 the wide L^-1 column slices, bit 2 the register-tile k_minv;
+    0 = the earlier kernels; ``None`` = the library's default) and, for bit 1, the slice
+    width (0 = chosen from the block count, 8 or 16). Same bits either way."""
+
+    def __init__(self, mask=None, linv_width: int = 0):
+        self.default = load().admmq_debug_get_spd_form_default()
+        self.mask = self.default if mask is None else mask
+        self.width = linv_width
+
+    def __enter__(self):
+        check(load().admmq_debug_set_spd_form(self.mask), "spd_form")
+        check(load().admmq_debug_set_linv_width(self.width), "linv_width")
+        return self
+
+    def __exit__(self, *exc):
+        check(load().admmq_debug_set_spd_form(self.default), "spd_form")
+        check(load().admmq_debug_set_linv_width(0), "linv_width")
+        return False
+
+
+def chol_step_work(s: int, nbk: Sequence[int]):
+    """Diagnostics (host only): the workgroups of the fused Cholesky launch ``s`` for a batch
+    with block counts ``nbk``: a list of (problem, i, j) for the workgroups that work (j == s:
+    a column workgroup, j > s: a trailing one) and the launch's workgroup count."""
+    arr = (ctypes.c_int32 * len(nbk))(*nbk)
+    out = (ctypes.c_int32 * 3)()
+    n = load().admmq_debug_chol_step_work(s, len(nbk), arr, 0, out)
+    if n < 0:
+        raise ValueError("chol_step_work: bad arguments")
+    work = []
+    for wid in range(n):
+        if load().admmq_debug_chol_step_work(s, len(nbk), arr, wid, out) != n:
+            raise RuntimeError("chol_step_work failed")
+        if out[0] >= 0:
+            work.append((int(out[0]), int(out[1]), int(out[2])))
+    return work, n
+
+
+def debug_spd_inverse(Gs, shift: float = 0.0, reps: int = 1):
+    """Diagnostics: M = (G + shift I)^-1 of the fp64 matrices ``Gs`` (numpy, R x R) in one
+    batched launch_spd_inverse. Returns a list of dicts with ``M`` (ldm x ldm fp32), ``A``
+    (ldm x ldm fp64: L in the strictly lower 32 x 32 blocks), ``Linv`` (ldm x ldm fp64: lower
+    blocks), ``D`` (ldm x 32 fp64: the diagonal blocks of L) and ``flag`` (a non-positive
+    pivot), and the device time in ms of the last of ``reps`` inverses."""
+    import numpy as np
+    n = len(Gs)
+    Gs = [np.ascontiguousarray(g, dtype=np.float64) for g in Gs]
+    R = [g.shape[0] for g in Gs]
+    ldm = [(r + 31) // 32 * 32 for r in R]
+    out = [dict(M=np.empty((l, l), np.float32), A=np.empty((l, l), np.float64), Linv=np.empty((l, l), np.float64),
+                D=np.empty((l, 32), np.float64)) for l in ldm]
+    vp = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])  # noqa: E731
+    flags = (ctypes.c_int32 * n)()
+    ms = ctypes.c_float(0.0)
+    check(load().admmq_debug_spd_inverse(n, (ctypes.c_int32 * n)(*R), vp(Gs), float(shift), vp([o["M"] for o in out]),
+                                         vp([o["A"] for o in out]), vp([o["Linv"] for o in out]),
+                                         vp([o["D"] for o in out]), flags, reps, ctypes.byref(ms)), "debug_spd_inverse")
+    for o, f in zip(out, flags):
+        o["flag"] = int(f)
+    return out, float(ms.value)
 
 
 def shared_stage2_count(reset: bool = False) -> int:

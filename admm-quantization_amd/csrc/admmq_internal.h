@@ -157,6 +157,12 @@ static_assert(sizeof(GemmTile) == 104, "GemmTile: the workspace carve depends on
 constexpr int kHeadGemmStop = 1;     // solve GEMM: the stop test's inputs from the tile record, decided at the first K-step's wait
 constexpr int kLaunchHeadAll = kHeadGemmStop;
 constexpr int kLaunchHeadDefault = kLaunchHeadAll;
+// Forms of the SPD inverse (spd_kernels.hip; admmq_debug_set_spd_form, same bits either way)
+constexpr int kSpdFusedChol = 1;     // one k_chol_step launch per block column instead of panel + update
+constexpr int kSpdWideLinv = 2;      // L^-1 column slices of 8 or 16 columns instead of 4
+constexpr int kSpdTileMinv = 4;      // k_minv with a 2 x 4 register tile per thread
+constexpr int kSpdFormAll = kSpdFusedChol | kSpdWideLinv | kSpdTileMinv;
+constexpr int kSpdFormDefault = kSpdFormAll;
 constexpr int kKsplitMax = 4;        // pieces per tile at most
 constexpr int kKsplitMinSteps = 6;   // K-steps per piece at least
 // Thin-factor solve workgroup (thin_loop.hip): columns [col0, col0 + cw) of problem `job`,

@@ -25,6 +25,10 @@ int32_t admmq_debug_admm_run_schedule(const admmq_problem* probs, int32_t nprob,
                                       int32_t qscheme, int32_t max_iter, int32_t solve_mode, int32_t fused_finalize,
                                       int32_t has_info, int32_t fin_capacity, int32_t out[16]);
 
+/* diagnostics entry point (csrc/spd_kernels.hip, not in admmq.h): workgroup `id` of the fused
+ * Cholesky launch s -> {problem or -1, i, j}; returns the launch's workgroup count or -1 */
+int32_t admmq_debug_chol_step_work(int32_t s, int32_t nprob, const int32_t* nbk, int32_t id, int32_t* out);
+
 static size_t ws_of(const int (*ir)[2], int n) {
   admmq_problem* p = calloc((size_t)n, sizeof(admmq_problem));
   for (int i = 0; i < n; ++i) { p[i].I = ir[i][0]; p[i].R = ir[i][1]; }
@@ -115,6 +119,24 @@ int main(void) {
   fails += admmq_admm_workspace_size(&bad, 1, 0) != 0;
   fails += admmq_admm_prepare(&bad, 1, 200, NULL, 0, NULL) == ADMMQ_OK;
   fails += admmq_quantize_batched(NULL, 1, 4, 99, 200, NULL, 0, NULL) != ADMMQ_ERR_SCHEME;
+  /* the fused Cholesky launch's workgroup map (csrc/spd_kernels.hip chol_step_work): every
+   * workgroup of every launch of random mixed batches lands on a block of its problem */
+  for (int t = 0; t < 60; ++t) {
+    int32_t nbk[8], out[3];
+    const int n = rnd(1, 8);
+    int maxnbk = 0;
+    for (int i = 0; i < n; ++i) { nbk[i] = rnd(1, t % 10 == 0 ? 56 : 12); if (nbk[i] > maxnbk) maxnbk = nbk[i]; }
+    for (int s = 0; s < maxnbk; ++s) {
+      const int nwg = admmq_debug_chol_step_work(s, n, nbk, 0, out);
+      fails += nwg <= 0;
+      for (int id = 0; id < nwg; ++id) {
+        fails += admmq_debug_chol_step_work(s, n, nbk, id, out) != nwg;
+        fails += out[0] >= n || out[2] < s || out[1] < out[2] || out[1] >= maxnbk || (out[0] >= 0 && out[1] >= nbk[out[0]]);
+      }
+      fails += admmq_debug_chol_step_work(s, n, nbk, nwg, out) != -1;
+    }
+    fails += admmq_debug_chol_step_work(maxnbk, n, nbk, 0, out) != -1;
+  }
   /* packed-weight GEMM: the planner over ragged sizes (a function of its arguments), then
    * every refusal of the entry point (made-up device addresses: nothing may be launched) */
   for (int t = 0; t < 400; ++t) {
