@@ -153,6 +153,11 @@ def load() -> ctypes.CDLL:
         "admmq_packed_rowsums": (I32, [P, P, I32, I64, I64, P, P]),
         "admmq_packed_igemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_igemm": (I32, [P, P, I32, I64, I64, P, P, P, I32, I64, I32, P, P, P, P, P, P, S, P]),
+        "admmq_packed_taps_i8_bytes": (S, [I32, I64]),
+        "admmq_packed_taps_i8": (I32, [P, P, I32, I64, P, P]),
+        "admmq_packed_idwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),
+        "admmq_packed_idwgemm": (I32, [P, P, I64, I64, P, P, I32, I64, I64, P, F32, I32, I32, I32, I32, I32, I32, P, P, P, P,
+                                       P, P, P, P, P, S, P]),
         "admmq_mse_sse_table": (I32, [P, I64, I64, I32, I32, P, P, S, P]),
         "admmq_quantize_channel_workspace_size": (S, [P, I32, I32]),
         "admmq_quantize_channel": (I32, [P, P, P, I32, I32, I32, I32, P, S, P]),

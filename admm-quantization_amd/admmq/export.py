@@ -21,6 +21,8 @@ the CP builders accept them in place of float tensors: the 1x1 convs / linears t
 3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``).
 ``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
 activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
+``integer=True`` of ``build_cp_layer`` returns an ``IntegerPackedCP``: ``conv1`` on ``k_packed_igemm`` and
+the fused depthwise + 1x1 stage on ``k_packed_idwgemm`` (an int8 stencil feeding the int8 MFMA).
 """
 from __future__ import annotations
 
@@ -32,8 +34,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from .packed import (PackedTensor, _int_weight_dims, _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed,
-                     packed_bytes, packed_dwgemm, packed_gemm, packed_rowsums)
+from .packed import (PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _meta_words, _pair, _weight_dims,
+                     _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm, packed_gemm, packed_rowsums,
+                     packed_taps_int, taps_kp)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -297,6 +300,139 @@ def _integer_pair(who, names, factors, acts, in_act, make):
     return IntegerPackedPair(names, stage1, stage2, _PackedWeight._resolve_act(*in_act))
 
 
+def _taps_from_float(taps: torch.Tensor, scale: float) -> torch.Tensor:
+    """The int8 tap image of float taps ``[kh kw, K]`` that are ``float(c) * scale`` (a packed factor's
+    de-quantization): ``c = round(taps / scale)`` is exact for ``|c| <= 128``. One-off, when a state
+    came without the image."""
+    img = torch.zeros((taps.shape[0], taps_kp(taps.shape[1])), dtype=torch.int8, device=taps.device)
+    if scale != 0.0:   # (a zero scale: every tap is 0 and so is every z, whatever the integers)
+        img[:, :taps.shape[1]] = torch.round(taps / scale).to(torch.int8)
+    return img
+
+
+class IntegerPackedCP(nn.Module):
+    """A 3-way packed CP layer whose activations are uint8 codes from its input encode to its last
+    epilogue: the float input is encoded once by ``in_act`` (``k_act_encode``),
+    ``conv1`` (``PackedConv1x1``, ``B^T``) runs from codes to the codes of the rank-``R`` tensor under its
+    output quantizer on ``k_packed_igemm``, and ``conv23`` (``PackedDepthwiseConv1x1``) runs the integer
+    stencil and the last 1x1 stage on ``k_packed_idwgemm`` under its mid quantizer, to a float output
+    (quantized where ``conv23`` has an output quantizer). The children are the ``fused=True`` layout's;
+    ``in_act``, the two row-sum vectors, the depthwise factor's scale and its int8 tap image travel in
+    this module's extra state. ``last_clamped``: the device counters of the last forward (input encode,
+    rank tensor, depthwise output; plus the output's with ``out_codes``); no forward reads them."""
+
+    def __init__(self, conv1: PackedConv1x1, conv23: PackedDepthwiseConv1x1, in_act, taps_scale: float,
+                 taps_i8: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.conv1, self.conv23 = conv1, conv23
+        self._in_act = in_act   # (bits, mn, rng), resolved float32 values
+        self._taps_scale = float(taps_scale)
+        self._taps_i8 = self._check_taps(taps_i8)
+        self._rs = [None, None]
+        self.out_codes = False   # True (needs conv23's output quantizer, bits 2..8): forward returns codes
+        self.last_clamped = None
+        if conv1.codes.device.type == "cuda":
+            self._rowsums(0), self._rowsums(1), self._taps()
+
+    def _stage(self, i):
+        return self.conv1 if i == 0 else self.conv23
+
+    def _rowsums(self, i):
+        st = self._stage(i)
+        if self._rs[i] is None:
+            self._rs[i] = packed_rowsums(st.packed(), st.transpose)
+        elif self._rs[i].device != st.codes.device:
+            self._rs[i] = self._rs[i].to(st.codes.device)
+        return self._rs[i]
+
+    def _check_taps(self, t):
+        c = self.conv23
+        shape = (c.kernel_size[0] * c.kernel_size[1], taps_kp(c.in_features))
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.int8 or tuple(t.shape) != shape):
+            raise ValueError(f"integer layer state: the tap image must be int8 {list(shape)}, got "
+                             f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+        return t
+
+    def _taps(self):
+        c = self.conv23
+        if self._taps_i8 is None:
+            self._taps_i8 = _taps_from_float(c.taps, self._taps_scale)
+        elif self._taps_i8.device != c.codes.device:
+            self._taps_i8 = self._taps_i8.to(c.codes.device)
+        return self._taps_i8
+
+    def get_extra_state(self):
+        return dict(in_act=list(self._in_act), rowsums=[None if r is None else r.detach().cpu() for r in self._rs],
+                    taps_scale=self._taps_scale, taps_i8=None if self._taps_i8 is None else self._taps_i8.detach().cpu())
+
+    def set_extra_state(self, state):
+        a = state["in_act"]
+        self._in_act = (int(a[0]), float(a[1]), float(a[2]))
+        if "taps_scale" not in state:
+            raise ValueError("integer layer state: taps_scale (the depthwise factor's scale) is missing")
+        rs = []
+        for i, r in enumerate(state.get("rowsums") or [None, None]):
+            if r is not None and (r.dtype != torch.int32 or tuple(r.shape) != (self._stage(i).out_features,)):
+                raise ValueError(f"integer layer state: row sums of stage {i + 1} must be int32 "
+                                 f"[{self._stage(i).out_features}], got {r.dtype} {tuple(r.shape)}")
+            rs.append(r)
+        taps = self._check_taps(state.get("taps_i8"))
+        self._rs, self._taps_i8, self._taps_scale = rs, taps, float(state["taps_scale"])
+
+    @torch.compiler.disable
+    def forward(self, x):
+        s1, s2 = self.conv1, self.conv23
+        a0, mid = s1._act, s2._mid_act
+        if a0 is None or not 2 <= a0[0] <= 8:
+            raise ValueError("integer layer: conv1 needs its output quantizer with 2 <= bits <= 8 (it writes codes)")
+        if mid is None or not 2 <= mid[0] <= 8:
+            raise ValueError("integer layer: conv23 needs its mid quantizer with 2 <= bits <= 8 (the depthwise stage "
+                             "writes codes)")
+        out = s2._act if s2._act is not None else (0, 0.0, 0.0)
+        if self.out_codes and not 2 <= out[0] <= 8:
+            raise ValueError("integer layer: out_codes needs conv23's output quantizer with 2 <= bits <= 8")
+        if s1.padding != (0, 0):
+            x = nn.functional.pad(x, (s1.padding[1], s1.padding[1], s1.padding[0], s1.padding[0]))
+        if s1.stride != (1, 1):
+            x = x[:, :, ::s1.stride[0], ::s1.stride[1]]
+        xq = act_encode(x, _lib.ActQ(self._in_act[0], 1, self._in_act[1], self._in_act[2]), check=False)
+        h = _igemm(s1.codes, s1._meta, s1.transpose, s1.out_features, s1.in_features, xq.codes, self._in_act, self._rowsums(0),
+                   0, s1.bias, a0, True)
+        y, midc, outc = _idwgemm(s2.codes, s2._meta, s2.out_features, s2.in_features, h.codes, a0, self._taps(),
+                                 self._taps_scale, s2.kernel_size, s2.stride, s2.padding, self._rowsums(1), s2.bias, mid,
+                                 out, bool(self.out_codes))
+        if self.out_codes:
+            self.last_clamped = (xq.clamped, h.clamped, midc, outc)
+            return QuantizedActivation(y, out[0], out[1], out[2], outc)
+        self.last_clamped = (xq.clamped, h.clamped, midc)
+        return y
+
+    def extra_repr(self):
+        return f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]})"
+
+
+def _integer_cp(who, rank, factors, bias, cin, cout, kernel_size, padding, stride, groups, acts, in_act):
+    """``integer=True`` of the 3-way builder: argument checks, then the integer layer over the fused layout's stages."""
+    if not _is_packed(factors):
+        raise ValueError(f"{who}: integer=True needs PackedTensor factors (the integer stages run from packed codes)")
+    if in_act is None:
+        raise ValueError(f"{who}: integer=True needs in_act, the (bits, min_val, max_val) quantizer of the layer's input")
+    if acts[0] is None:
+        raise ValueError(f"{who}: integer=True needs the conv1 entry of act_quant (conv1 writes codes)")
+    if acts[1] is None:
+        raise ValueError(f"{who}: integer=True needs the conv2 entry of act_quant (the depthwise stage writes codes)")
+    for a, what in ((in_act, "in_act"), (acts[0], "conv1's quantizer"), (acts[1], "conv2's quantizer")):
+        if not 2 <= int(a[0]) <= 8:
+            raise ValueError(f"{who}: {what} needs 2 <= bits <= 8 for activation codes, got {a[0]}")
+    C = factors[2]
+    seq = _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, stride, groups, True, acts)
+    for st in (seq.conv1, seq.conv23):
+        _int_weight_dims(st.packed(), st.transpose, who)
+    _int_weight_dims(C, False, who)
+    taps = packed_taps_int(C) if C.codes.device.type == "cuda" else None
+    return IntegerPackedCP(seq.conv1, seq.conv23, _PackedWeight._resolve_act(*in_act), float(C.scale), taps)
+
+
 def _stage_acts(act_quant, n, who):
     """``act_quant`` as a list of ``n`` entries ``(bits, min_val, max_val)`` or ``None`` (``None``: no quantizers)."""
     if act_quant is None:
@@ -381,7 +517,7 @@ def _packed_cpfc_layer(rank, factors, bias, fin, fout, acts=(None,) * 2):
 
 def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
                    cout: int, kernel_size: Tuple[int, int], padding, stride, groups: int = 1,
-                   fused: bool = False, act_quant=None) -> nn.Sequential:
+                   fused: bool = False, act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
     """1x1 (cin -> R) -> depthwise kernel_size (R) -> 1x1 (R -> cout); source/models.py:24-51.
     ``PackedTensor`` factors: conv1 / conv3 become ``PackedConv1x1`` (B transposed, A).
     ``fused`` (``PackedTensor`` factors only): the layout is ``conv1`` -> ``conv23``, a
@@ -389,8 +525,14 @@ def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: O
     ``act_quant``: ``[conv1, conv2, conv3]`` entries ``(bits, min_val, max_val)`` or ``None`` (as
     ``admmq.actquant.collect`` returns them): packed stages quantize in their epilogue (fused:
     ``conv2``'s entry is ``conv23``'s mid quantizer, ``conv3``'s its output quantizer); a float
-    stage is followed by a ``FixedQuant`` the way ``add_quant`` lays it out."""
+    stage is followed by a ``FixedQuant`` the way ``add_quant`` lays it out.
+    ``integer`` (``PackedTensor`` factors, ``in_act = (bits, min_val, max_val)`` of the input and the
+    ``conv1`` and ``conv2`` entries of ``act_quant``, all with bits 2..8; implies the fused layout): an
+    ``IntegerPackedCP`` of ``conv1`` / ``conv23`` whose activations stay uint8 codes between the stages."""
     acts = _stage_acts(act_quant, 3, "build_cp_layer")
+    if integer:
+        return _integer_cp("build_cp_layer", rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups,
+                           acts, in_act)
     if _is_packed(factors):
         return _packed_cp_layer(rank, factors, bias, cin, cout, tuple(kernel_size), padding, stride, groups, fused, acts)
     if fused:
@@ -531,14 +673,16 @@ def load_packed_factors(prefix: str, ndim: int, device=None) -> List[PackedTenso
 
 
 def factorized_conv(conv: nn.Conv2d, rank: int, factors: Sequence[torch.Tensor], fused: bool = False,
-                    act_quant=None) -> nn.Sequential:
+                    act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
     """The replacement scripts/calibrate.py:157-184 builds for ``conv`` from its factors.
-    ``fused``: ``build_cp_layer(..., fused=True)`` for a ``k x k`` conv (``PackedTensor`` factors only)."""
+    ``fused``: ``build_cp_layer(..., fused=True)`` for a ``k x k`` conv (``PackedTensor`` factors only).
+    ``integer`` / ``in_act``: the builders' integer layers (``IntegerPackedCP`` for a ``k x k`` conv,
+    ``IntegerPackedPair`` for a 1x1 conv)."""
     bias = conv.bias.detach() if conv.bias is not None else None
     if tuple(conv.kernel_size) != (1, 1):
         return build_cp_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.kernel_size,
-                              conv.padding, conv.stride, conv.groups, fused, act_quant)
+                              conv.padding, conv.stride, conv.groups, fused, act_quant, integer, in_act)
     if fused:
         raise ValueError("factorized_conv: fused=True applies to k x k convs (a 1x1 conv has no depthwise stage)")
     return build_cp2conv_layer(rank, list(factors), bias, conv.in_channels, conv.out_channels, conv.padding,
-                               conv.stride, act_quant)
+                               conv.stride, act_quant, integer, in_act)

@@ -16,6 +16,8 @@ such a weight as one kernel (``k_packed_dwgemm``: the tensor between them is nev
 fixed-range quantizer's level clamped to ``0 .. 2^bits - 1``), and ``packed_linear_int`` /
 ``packed_conv1x1_int`` multiply such codes by a packed weight in integer arithmetic
 (``k_packed_igemm``: int8 MFMA, exact int32 sums, one double-precision epilogue).
+``packed_depthwise_conv1x1_int`` is the fused depthwise + 1x1 stage on such codes (``k_packed_idwgemm``: an
+int8 stencil over the codes feeds the int8 MFMA).
 
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
@@ -33,7 +35,7 @@ from . import _lib
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
            "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
-           "packed_conv1x1_int"]
+           "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -615,6 +617,151 @@ def _pair(v, name: str) -> Tuple[int, int]:
     if len(v) != 2:
         raise ValueError(f"{name} must be an int or a pair, got {v}")
     return v
+
+
+# --- integer fused depthwise + 1x1 ---------------------------------------------
+TAPS_MAX = 49   # a 7 x 7 window
+
+
+def taps_kp(K: int) -> int:
+    """Row length of the int8 tap image: ``K`` rounded up to the 64-wide K step."""
+    return 64 * ((int(K) + 63) // 64)
+
+
+def packed_taps_int(C: "PackedTensor") -> torch.Tensor:
+    """The int8 image ``[kh kw, Kp]`` (``Kp = taps_kp(K)``) of the packed depthwise factor ``C [kh kw, K]``:
+    ``c[tap, k] = (u - q) - zero_point``, columns ``k >= K`` zero (``k_packed_taps_i8``). Kept on ``C``
+    while its codes and fields are unchanged, beside the row sums; the host refusals (tensor_minmax, an
+    affine record outside int8, more than 49 taps) run once."""
+    e = _int_plan(C, False, "packed_taps_int")
+    if len(e) < 4:
+        if e[0] > TAPS_MAX:
+            raise ValueError(f"packed_taps_int: {e[0]} taps are past the limit of {TAPS_MAX} (a 7 x 7 window)")
+        e.append(None)
+    if e[3] is None:
+        if C.codes.device.type != "cuda":
+            raise RuntimeError("admmq: packed codes must live on a ROCm GPU (device 'cuda'); the MI355X path has no "
+                               "CPU implementation")
+        e[3] = _taps_i8(C.codes, _meta_words(C), e[0], e[1])
+    return e[3]
+
+
+@torch.compiler.disable
+def _taps_i8(codes, meta_words, ntaps, K):
+    if _lib.use_ops():   # torch.ops.admmq.packed_taps_i8 (csrc/torch_ops.cpp) -> admmq_packed_taps_i8
+        return _lib.ops().packed_taps_i8(codes, meta_words, ntaps, K)
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    image = torch.empty((ntaps, taps_kp(K)), dtype=torch.int8, device=cc.device)
+    _lib.check(_lib.load().admmq_packed_taps_i8(_lib.ptr(cc), ctypes.byref(meta), ntaps, K, _lib.ptr(image),
+                                                _lib.stream_handle(cc.device)), "packed_taps_i8")
+    return image
+
+
+def _idwgemm(codes, meta_words, M, K, x, x3, image, s_c, ks, st, pd, rowsums, bias, m3, o3, out_codes, count_mid=True):
+    """The call behind ``packed_depthwise_conv1x1_int`` on checked quantizers ``x3`` / ``m3`` / ``o3 =
+    (bits, mn, rng)``: ``(y, mid_clamped, clamped)``, the counters int32 device tensors (``mid_clamped``
+    empty without ``count_mid``: the count then costs nothing, not even its memset)."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise TypeError("packed_idwgemm: xq.codes must be a uint8 tensor")
+    if bias is not None and bias.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: packed_idwgemm is inference only (no backward through packed weights): call it "
+                           "under torch.no_grad() or detach bias")
+    if x.device.type != "cuda" or codes.device.type != "cuda" or image.device.type != "cuda":
+        raise RuntimeError("admmq: packed_idwgemm needs its codes, tap image and activations on a ROCm GPU (device "
+                           "'cuda'); the MI355X path has no CPU implementation")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_igemm
+        return _opaque_idwgemm(codes, meta_words, M, K, x, x3, image, s_c, ks, st, pd, rowsums, bias, m3, o3, out_codes,
+                               count_mid)
+    (kh, kw), (sh, sw), (ph, pw) = ks, st, pd
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_idwgemm (csrc/torch_ops.cpp) -> admmq_packed_idwgemm
+        return _lib.ops().packed_idwgemm(codes, meta_words, M, K, x, x3[0], x3[1], x3[2], image, s_c, kh, kw, sh, sw, ph,
+                                         pw, rowsums, bias, m3[0], m3[1], m3[2], o3[0], o3[1], o3[2], out_codes,
+                                         bool(count_mid))
+    lib = _lib.load()
+    if x.dim() != 4 or x.shape[1] != K:
+        raise ValueError(f"packed_idwgemm: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    if image.dtype != torch.int8 or tuple(image.shape) != (kh * kw, taps_kp(K)):
+        raise ValueError(f"packed_idwgemm: the tap image must be int8 [{kh * kw}, {taps_kp(K)}], got {image.dtype} "
+                         f"{tuple(image.shape)}")
+    if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
+        raise ValueError(f"packed_idwgemm: rowsums must be int32 [{M}]")
+    xc, ic = x.contiguous(), image.contiguous()
+    if xc.numel() == 0:
+        raise ValueError("packed_idwgemm: empty x")
+    if ic.data_ptr() % 16:
+        ic = ic.clone()
+    nb, H, W = int(xc.shape[0]), int(xc.shape[2]), int(xc.shape[3])
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    bc = None
+    if bias is not None:
+        _lib.require_device(bias)
+        if tuple(bias.shape) != (M,):
+            raise ValueError(f"packed_idwgemm: bias must be [{M}], got {tuple(bias.shape)}")
+        bc = bias.contiguous()
+    # (a geometry outside the limits leaves Ho / Wo meaningless: the call below refuses it before any launch)
+    Ho = max((H + 2 * ph - kh) // max(sh, 1) + 1, 1)
+    Wo = max((W + 2 * pw - kw) // max(sw, 1) + 1, 1)
+    xr, mr = _lib.ActQ(x3[0], 1, x3[1], x3[2]), _lib.ActQ(m3[0], 1, m3[1], m3[2])
+    oq = _lib.ActQ(o3[0], 1, o3[1], o3[2]) if o3[0] else None
+    y = torch.empty((nb, M, Ho, Wo), dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
+    mid_clamped = torch.empty(1 if count_mid else 0, dtype=torch.int32, device=x.device)
+    clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
+    nbytes = lib.admmq_packed_idwgemm_workspace_size(M, K, Ho, Wo, nb)
+    ws = _lib.workspace(nbytes, x.device)
+    rc = lib.admmq_packed_idwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), ctypes.byref(xr), nb, H, W,
+                                  _lib.ptr(ic), s_c, kh, kw, sh, sw, ph, pw, _lib.ptr(rowsums.contiguous()), _lib.ptr(bc),
+                                  _lib.ptr(None if out_codes else y), _lib.ptr(y if out_codes else None),
+                                  ctypes.byref(mr), ctypes.byref(oq) if oq is not None else None,
+                                  _lib.ptr(mid_clamped if count_mid else None),
+                                  _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), ws.numel(),
+                                  _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_idwgemm")
+    return y, mid_clamped, clamped
+
+
+_opaque_idwgemm = torch.compiler.disable(_idwgemm)
+
+
+def packed_depthwise_conv1x1_int(xq: QuantizedActivation, C_or_image, p: "PackedTensor", kernel_size=(3, 3), stride=1,
+                                 padding=0, bias: Optional[torch.Tensor] = None, mid_act=None, act=None,
+                                 out_codes: bool = False, return_mid_clamped: bool = False):
+    """``packed_depthwise_conv1x1`` on activation codes, in integer arithmetic from the stencil to the GEMM
+    (``k_packed_idwgemm``): ``xq.codes [n, K, H, W] -> [n, M, Ho, Wo]``. ``C_or_image``: the packed depthwise
+    factor ``C [kh kw, K]`` (its int8 image is made on the first call and kept on ``C``), or the pair
+    ``(packed_taps_int(C), C.scale)``. ``p``: the packed ``A [M, K]``; its row sums are kept on ``p``.
+    ``mid_act`` (mandatory, bits 2..8): the quantizer of the depthwise stage's output, whose codes are the
+    GEMM's operand. The result is a float tensor (quantized by ``act`` when given) or, with
+    ``out_codes=True`` (needs ``act``, bits 2..8), a ``QuantizedActivation`` with its ``clamped`` count on the
+    device. ``return_mid_clamped``: return ``(result, mid_clamped)``, the int32 ``[1]`` device count of the
+    depthwise outputs whose code was clamped (counted only when asked for: the count costs a memset on the
+    stream). No host read. Inference only."""
+    who = "packed_depthwise_conv1x1_int"
+    e = _int_plan(p, False, who)
+    x3 = _in_triple(xq, who)
+    mq = _code_act(mid_act, who)
+    m3 = (int(mq.bits), float(mq.mn), float(mq.rng))
+    o3 = _out_triple(act, out_codes, who)
+    ks, st, pd = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
+    if isinstance(C_or_image, PackedTensor):
+        if tuple(C_or_image.shape) != (ks[0] * ks[1], e[1]):
+            raise ValueError(f"{who}: C must be [{ks[0] * ks[1]}, {e[1]}], got {tuple(C_or_image.shape)}")
+        image, s_c = packed_taps_int(C_or_image), float(C_or_image.scale)
+    else:
+        image, s_c = C_or_image
+        s_c = float(s_c)
+    rs = e[2] if e[2] is not None else packed_rowsums(p, False)
+    y, mid_clamped, clamped = _idwgemm(p.codes, _meta_words(p), e[0], e[1], xq.codes, x3, image, s_c, ks, st, pd, rs, bias,
+                                       m3, o3, bool(out_codes), bool(return_mid_clamped))
+    res = QuantizedActivation(y, o3[0], o3[1], o3[2], clamped) if out_codes else y
+    return (res, mid_clamped) if return_mid_clamped else res
 
 
 def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, x: torch.Tensor, taps: torch.Tensor,

@@ -615,3 +615,398 @@ int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
 }
 
 }  // extern "C"
+
+// --- integer fused depthwise + 1x1 stage (include/admmq.h "Integer fused depthwise + 1x1") ---
+// k_packed_igemm<BITS, false, false, OUT> with the X loader replaced by an integer stencil over
+// the codes of t: for an element (k, column) of the step's block
+//   D  = sum_V c[tap,k] ut[b,k,ih,iw]      Cv = sum_V c[tap,k]      (V: the taps inside the image)
+//   z  = float(double(s_c) (g_t double(D) + double(mn_t) double(Cv)))     uz = act_code(z; mid_q)
+// and uz - 128 is the byte of the [c][k] image. A thread owns one column and the 16 k of its
+// wave (xk = 16 wave), as the layout-0 loader of k_packed_igemm: the tap weights of a step are
+// one aligned 16-byte uniform load a tap from the int8 image [tap][Kp] (k_packed_taps_i8). The
+// column's window position, its validity masks and its plane pointer are derived once, as in
+// k_packed_dwgemm; a tap outside the image reads the plane's first byte and enters with the
+// weight 0 (a select, no branch around the load); a tap's 16 byte loads are issued together,
+// ahead of the selects (the empty asm). Elements that are not real (a column past C, a k past
+// the piece or K) are the int8 value 0 and are neither encoded nor counted. z, its code and the
+// bias by 128 are formed in the load phase: four packed dwords are all that lives across the
+// step's two MFMAs. Workgroups with blockIdx.y == 0 count the clamped codes of Z: the column
+// tiles and the K pieces partition Z, the row tiles repeat it.
+namespace admmq {
+
+struct IgDwArgs {
+  IgArgs g;                  // x = t's codes [nb, K, H, W]; N = Ho Wo; C = nb N; g, mnx: the mid quantizer's
+  const signed char* taps;   // [kh kw][Kp] int8
+  int* midc;                 // clamp counter of Z, or NULL
+  long long H, W, HW, Kp;
+  int Wo;
+  int kh, kw, sh, sw, ph, pw;
+  double sc, gt, mnt;        // s_c, rng_t / n_t, mn_t
+  ActQ mq;
+};
+
+__global__ __launch_bounds__(256) void k_packed_taps_i8(const unsigned char* __restrict__ codes, long long nbytes, int bits,
+                                                        int ntaps, int K, int Kp, int off, signed char* __restrict__ image) {
+  const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;   // ntaps Kp <= 49 * 65536
+  if (e >= ntaps * Kp) return;
+  const int tap = e / Kp, k = e - tap * Kp;
+  image[e] = k < K ? (signed char)((int)code_at(codes, (long long)tap * K + k, bits, nbytes) - off) : (signed char)0;
+}
+
+template <int BITS, int OUT>
+__global__ __launch_bounds__(256) void k_packed_idwgemm(const IgDwArgs d) {
+  __shared__ __attribute__((aligned(16))) unsigned char sW[2][kIgBM * kIgLD];
+  __shared__ __attribute__((aligned(16))) unsigned char sX[2][kIgBN * kIgLD];
+  const IgArgs& a = d.g;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
+  const int M = a.M, K = a.K, N = a.N;
+  const long long C = a.C;
+  const int m0 = (int)blockIdx.y * kIgBM;
+  const long long c0 = (long long)blockIdx.x * kIgBN;
+  const int piece = (int)blockIdx.z;
+  const int kb = a.parallel ? piece * a.kp : 0;
+  const int ke = a.parallel ? min(K, kb + a.kp) : K;
+  const unsigned char* __restrict__ codes = a.codes;
+  const long long nbytes = a.nbytes;
+
+  // W: as k_packed_igemm with TRANS = 0
+  int wrow[2], wk[2], nvm[2], wsh[2];
+  long long wq[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int id = tid + 256 * u;
+    wrow[u] = id >> 3;
+    wk[u] = 8 * (id & 7);
+    nvm[u] = m0 + wrow[u] < M ? 8 : 0;
+    const long long bit0 = ((long long)(m0 + wrow[u]) * K + (kb + wk[u])) * BITS;
+    wsh[u] = (int)(bit0 & 31);
+    wq[u] = bit0 >> 5;
+  }
+  const long long wstep = 2 * BITS;
+  // Z: one column, k = xk .. xk + 15 (uniform over the wave)
+  const int xc = tid & 63;
+  const int xk = __builtin_amdgcn_readfirstlane(16 * (tid >> 6));
+  const bool cok = c0 + xc < C;
+  const int kh = d.kh, kw = d.kw;
+  const long long W = d.W, HW = d.HW;
+  long long tbase;                   // byte offset of the window's first position in a channel plane (may be negative)
+  unsigned rmask = 0u, cmask = 0u;   // bit a / b: window row a / column b lies inside the image
+  const unsigned char* __restrict__ tp;
+  {
+    const long long c = min(c0 + xc, C - 1);   // (a column past C reads a valid one and is zeroed)
+    const long long b = c / N;
+    const int n = (int)(c - b * N);
+    const int oh = n / d.Wo, ow = n - oh * d.Wo;
+    const long long ih0 = (long long)oh * d.sh - d.ph, iw0 = (long long)ow * d.sw - d.pw;
+    for (int ta = 0; ta < kh; ++ta)
+      if (ih0 + ta >= 0 && ih0 + ta < d.H) rmask |= 1u << ta;
+    for (int tb = 0; tb < kw; ++tb)
+      if (iw0 + tb >= 0 && iw0 + tb < W) cmask |= 1u << tb;
+    tbase = ih0 * W + iw0;
+    tp = a.x + (b * K + (kb + xk)) * HW;
+  }
+  const signed char* __restrict__ wp = d.taps + (kb + xk);
+  const long long tstep = (long long)kIgBK * HW;
+  const bool counting = d.midc != nullptr && blockIdx.y == 0;   // (uniform)
+
+  unsigned cw[2][3];
+  int nv[2] = {0, 0};
+  unsigned rx[4];
+  int mcnt = 0;
+  auto load = [&](int k0, auto full) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(full)::value;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      cw[u][0] = 0u; cw[u][1] = 0u; cw[u][2] = 0u;
+      if (FULL) nv[u] = nvm[u];
+      else nv[u] = nvm[u] > 0 ? min(8, ke - (k0 + wk[u])) : 0;
+      if (nv[u] > 0) {
+        if (4 * wq[u] + 12 <= nbytes) {
+          const unsigned* q = reinterpret_cast<const unsigned*>(codes + 4 * wq[u]);
+          cw[u][0] = q[0]; cw[u][1] = q[1]; cw[u][2] = q[2];
+        } else {
+          cw[u][0] = code_dword(codes, wq[u], nbytes);
+          cw[u][1] = code_dword(codes, wq[u] + 1, nbytes);
+          cw[u][2] = code_dword(codes, wq[u] + 2, nbytes);
+        }
+      }
+      wq[u] += wstep;
+    }
+    const int nk = FULL ? 16 : max(0, min(16, ke - (k0 + xk)));   // the thread's real k of this step (uniform)
+    rx[0] = 0u; rx[1] = 0u; rx[2] = 0u; rx[3] = 0u;
+    if (nk > 0) {
+      long long jo[16];   // plane offsets of the 16 k; a k past the end reads the last real one and is dropped
+#pragma unroll
+      for (int j = 0; j < 16; ++j) jo[j] = (long long)(FULL ? j : min(j, nk - 1)) * HW;
+      int D[16], Cv[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { D[j] = 0; Cv[j] = 0; }
+      const int ntap = kh * kw;
+      int ta = 0, tb = 0;
+      for (int tap = 0; tap < ntap; ++tap) {
+        const bool ok = ((rmask >> ta) & (cmask >> tb) & 1u) != 0u;
+        const unsigned char* __restrict__ p = tp + (ok ? tbase + ta * W + tb : 0);   // outside: the plane's first byte, not used
+        const ig_i32x4 wv = *reinterpret_cast<const ig_i32x4*>(wp + (long long)tap * d.Kp);   // 16 int8 weights, uniform
+        unsigned v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = p[jo[j]];
+        // one statement over all 16: the loads are issued together and ahead of the selects (with
+        // one statement an element the prologue's copy of this loop waited for every load by itself)
+        asm("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                 "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
+        const int okm = ok ? -1 : 0;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int c = (wv[j >> 2] << (24 - 8 * (j & 3))) >> 24;   // (uniform: scalar)
+          const int cm = c & okm;
+          D[j] += __mul24(cm, (int)v[j]);   // 8-bit operands: the full-rate 24-bit multiply-add
+          Cv[j] += cm;
+        }
+        if (++tb == kw) { tb = 0; ++ta; }
+      }
+#pragma unroll
+      for (int dd = 0; dd < 4; ++dd) {
+        unsigned w = 0u;
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const int j = 4 * dd + jj;
+          const double zd = d.sc * (d.gt * (double)D[j] + d.mnt * (double)Cv[j]);
+          int cl = 0;
+          const unsigned u = act_code((float)zd, d.mq, cl);
+          const bool real = cok && j < nk;
+          mcnt += real ? cl : 0;
+          w |= (real ? (u ^ 0x80u) : 0u) << (8 * jj);
+        }
+        rx[dd] = w;
+      }
+    }
+    tp += tstep;
+    wp += kIgBK;
+  };
+  auto store = [&](int buf) __attribute__((always_inline)) {
+    constexpr unsigned mask = (1u << BITS) - 1u;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int p2 = wsh[u] + 4 * BITS;
+      const bool up = p2 >= 32;
+      unsigned long long win[2];
+      win[0] = (((unsigned long long)cw[u][1] << 32) | cw[u][0]) >> wsh[u];
+      win[1] = (((unsigned long long)(up ? cw[u][2] : cw[u][1]) << 32) | (up ? cw[u][1] : cw[u][0])) >> (p2 & 31);
+      unsigned b[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int v = (int)((unsigned)(win[j >> 2] >> ((j & 3) * BITS)) & mask) - a.off;
+        b[j] = j < nv[u] ? ((unsigned)v & 255u) : 0u;
+      }
+      const unsigned lo = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+      const unsigned hi = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
+      *reinterpret_cast<uint2*>(&sW[buf][wrow[u] * kIgLD + wk[u]]) = make_uint2(lo, hi);
+    }
+    *reinterpret_cast<uint4*>(&sX[buf][xc * kIgLD + xk]) = make_uint4(rx[0], rx[1], rx[2], rx[3]);
+  };
+  auto load_step = [&](int k0) __attribute__((always_inline)) {
+    if (k0 + kIgBK <= ke) load(k0, std::true_type{});
+    else load(k0, std::false_type{});
+  };
+
+  ig_i32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0;
+  load_step(kb);
+  store(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kb; k0 < ke; k0 += kIgBK) {
+    const bool more = k0 + kIgBK < ke;
+    if (more) load_step(k0 + kIgBK);
+    const unsigned char* w = sW[buf] + (32 * wm + i) * kIgLD + 16 * h;
+    const unsigned char* x = sX[buf] + (32 * wn + i) * kIgLD + 16 * h;
+#pragma unroll
+    for (int kk = 0; kk < kIgBK / 32; ++kk) {
+      const ig_i32x4 av = *reinterpret_cast<const ig_i32x4*>(w + 32 * kk);
+      const ig_i32x4 bv = *reinterpret_cast<const ig_i32x4*>(x + 32 * kk);
+      acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, acc, 0, 0, 0);
+    }
+    if (more) store(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // Epilogue: k_packed_igemm's for x_layout 0
+  int cnt = 0;
+  {
+    const long long c = c0 + 32 * wn + i;
+    const bool ok = c < C;
+    const long long cc = ok ? c : 0;
+    const long long b = cc / N;
+    const long long ybase = b * M * N + (cc - b * N);
+    const bool hb = a.bias != nullptr;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int m = m0 + 32 * wm + IG_ROW(r);
+      if (!ok || m >= M) continue;
+      const long long e = ybase + (long long)m * N;
+      if (a.parallel) {
+        a.part[(long long)piece * a.total + e] = acc[r];
+      } else {
+        const float v = ig_value(acc[r], a.rowsum[m], a, hb, hb ? a.bias[m] : 0.f);
+        if constexpr (OUT == kIgCodes) a.yc[e] = (unsigned char)act_code(v, a.oq, cnt);
+        else if constexpr (OUT == kIgQuant) a.y[e] = fixed_quant(v, a.oq);
+        else a.y[e] = v;
+      }
+    }
+  }
+  if (counting) block_count_add(mcnt, d.midc);   // (uniform; every thread arrives: no return above)
+  if constexpr (OUT == kIgCodes) {
+    if (a.clamped) {
+      __syncthreads();   // block_count_add's LDS words are those of the call above
+      block_count_add(cnt, a.clamped);
+    }
+  }
+}
+
+static int64_t taps_kp(int64_t K) { return kIgBK * ((K + kIgBK - 1) / kIgBK); }
+
+}  // namespace admmq
+
+extern "C" {
+
+size_t admmq_packed_taps_i8_bytes(int32_t ntaps, int64_t K) {
+  if (ntaps <= 0 || ntaps > 49 || K <= 0 || K > kIgKMax) return 0;
+  return (size_t)ntaps * (size_t)taps_kp(K);
+}
+
+int32_t admmq_packed_taps_i8(const uint8_t* codes, const admmq_qmeta* meta, int32_t ntaps, int64_t K, int8_t* image,
+                             void* stream) {
+  if (!codes || !meta || !image) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: codes, meta and image must not be NULL");
+  if (ntaps <= 0 || K <= 0) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: ntaps and K must be positive");
+  if (ntaps > 49) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: ntaps must be at most 49 (a 7 x 7 window)");
+  int off = 0;
+  const int32_t rc = igemm_meta_check(meta, "packed_taps_i8", off);
+  if (rc != ADMMQ_OK) return rc;
+  if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: K must be at most 65536");
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: codes must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(image) & 15) != 0) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: image must be 16-byte aligned");
+  const int Kp = (int)taps_kp(K);
+  const long long nbytes = (long long)admmq_packed_bytes((int64_t)ntaps * K, meta->bits);
+  const unsigned nblk = (unsigned)(((long long)ntaps * Kp + 255) / 256);
+  hipLaunchKernelGGL(k_packed_taps_i8, dim3(nblk), dim3(256), 0, static_cast<hipStream_t>(stream), codes, nbytes,
+                     (int)meta->bits, (int)ntaps, (int)K, Kp, off, reinterpret_cast<signed char*>(image));
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
+
+size_t admmq_packed_idwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb) {
+  IgPlan pl;
+  if (Ho <= 0 || Wo <= 0 || Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30)) return 0;
+  if (!plan_packed_igemm(M, K, Ho * Wo, nb, pl)) return 0;
+  return pl.ws;
+}
+
+int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const uint8_t* t_codes,
+                             const admmq_actq* t_q, int32_t nb, int64_t H, int64_t W, const int8_t* taps_i8, float s_c,
+                             int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw,
+                             const int32_t* rowsums, const float* bias, float* y, uint8_t* y_codes,
+                             const admmq_actq* mid_q, const admmq_actq* out_q, int32_t* mid_clamped, int32_t* clamped,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (!codes || !meta || !t_codes || !t_q || !taps_i8 || !rowsums)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: codes, meta, t_codes, t_q, taps_i8 and rowsums must not be NULL");
+  if ((y == nullptr) == (y_codes == nullptr))
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: exactly one of y and y_codes must be given");
+  if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: M, K, H, W and nb must be positive");
+  int off = 0;
+  const int32_t rc = igemm_meta_check(meta, "packed_idwgemm", off);
+  if (rc != ADMMQ_OK) return rc;
+  if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: K must be at most 65536 (the int32 sum 128 * 255 * K)");
+  if (!act_bits_ok(t_q)) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: t_q must be on with bits 2..8");
+  if (!act_bits_ok(mid_q))
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: mid_q must be given and on with bits 2..8 (the GEMM operand is codes)");
+  const bool oq = out_q && out_q->on != 0;
+  if (y_codes && !act_bits_ok(out_q))
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: a codes output needs out_q on with bits 2..8");
+  if (y && oq && (out_q->bits < 1 || out_q->bits > 24)) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: out_q bits must be 1..24");
+  if (kh < 1 || kh > 7 || kw < 1 || kw > 7) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: kernel size must be 1..7 x 1..7");
+  if (sh < 1 || sw < 1) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: stride must be at least 1");
+  if (ph < 0 || ph >= kh || pw < 0 || pw >= kw)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: padding must be in [0, kernel size)");
+  if (H > (int64_t(1) << 40) || W > (int64_t(1) << 40) || H > (int64_t(1) << 40) / W)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range");
+  if (H + 2 * ph < kh || W + 2 * pw < kw)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: the window does not fit the padded image (Ho, Wo >= 1)");
+  const int64_t Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: codes must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(taps_i8) & 15) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: taps_i8 must be 16-byte aligned");
+  if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(rowsums) |
+        reinterpret_cast<uintptr_t>(clamped) | reinterpret_cast<uintptr_t>(mid_clamped)) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: y, bias, rowsums, mid_clamped and clamped must be 4-byte aligned");
+  IgPlan pl;
+  if (Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30) || !plan_packed_igemm(M, K, Ho * Wo, nb, pl))
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range");
+  const int64_t tmax = (int64_t(1) << 40) - 1;   // nb K H W <= tmax, without overflow
+  if (K > tmax / (H * W) || nb > tmax / (H * W * K))
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range (nb K H W must be below 2^40)");
+  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
+  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: workspace must be int32 aligned");
+  IgDwArgs d;
+  IgArgs& a = d.g;
+  a.codes = codes; a.x = t_codes; a.bias = bias; a.rowsum = rowsums; a.y = y; a.yc = y_codes;
+  a.part = pl.parallel ? static_cast<int*>(workspace) : nullptr;
+  a.clamped = y_codes ? clamped : nullptr;
+  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
+  a.total = pl.total; a.C = pl.C;
+  a.M = (int)M; a.K = (int)K; a.N = (int)(Ho * Wo);
+  a.xl = 0;
+  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
+  a.off = off;
+  a.xal = 0;
+  const int out = y_codes ? kIgCodes : (oq ? kIgQuant : kIgFloat);
+  a.out = out;
+  a.s = (double)meta->scale;
+  a.g = (double)mid_q->rng / (double)((1 << mid_q->bits) - 1);
+  a.mnx = (double)mid_q->mn;
+  a.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+  d.taps = reinterpret_cast<const signed char*>(taps_i8);
+  d.midc = mid_clamped;
+  d.H = H; d.W = W; d.HW = H * W; d.Kp = taps_kp(K);
+  d.Wo = (int)Wo;
+  d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
+  d.sc = (double)s_c;
+  d.gt = (double)t_q->rng / (double)((1 << t_q->bits) - 1);
+  d.mnt = (double)t_q->mn;
+  d.mq = actq_make(mid_q);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (mid_clamped) {
+    const hipError_t e = hipMemsetAsync(mid_clamped, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
+  }
+  if (a.clamped) {
+    const hipError_t e = hipMemsetAsync(a.clamped, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
+  }
+  const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
+  const int kout = pl.parallel ? kIgFloat : out;   // the parallel form's epilogue runs in k_packed_ireduce
+#define ADMMQ_IDW_CASE(B)                                                                                   \
+  case B:                                                                                                   \
+    if (kout == kIgCodes) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgCodes>), grid, dim3(256), 0, s, d);      \
+    else if (kout == kIgQuant) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgQuant>), grid, dim3(256), 0, s, d); \
+    else hipLaunchKernelGGL((k_packed_idwgemm<B, kIgFloat>), grid, dim3(256), 0, s, d);                     \
+    break;
+  switch (meta->bits) {
+    ADMMQ_IDW_CASE(1) ADMMQ_IDW_CASE(2) ADMMQ_IDW_CASE(3) ADMMQ_IDW_CASE(4)
+    ADMMQ_IDW_CASE(5) ADMMQ_IDW_CASE(6) ADMMQ_IDW_CASE(7) ADMMQ_IDW_CASE(8)
+    default: break;   // (refused above)
+  }
+#undef ADMMQ_IDW_CASE
+  if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_ireduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
+
+}  // extern "C"

@@ -12,6 +12,7 @@
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
+//   admmq::packed_taps_i8, packed_idwgemm   int8 tap image and the integer fused depthwise + 1x1 stage
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
 //   admmq::cp_rel_error            <- scripts/factorize.py:246-253 + source/admm.py:14-15
@@ -566,6 +567,116 @@ std::tuple<at::Tensor, at::Tensor> packed_igemm_meta(const at::Tensor& codes, co
           at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
 }
 
+// --- integer fused depthwise + 1x1 -------------------------------------------------
+// packed_taps_i8: the int8 image [ntaps, Kp] of a packed depthwise factor (once per weight);
+// packed_idwgemm: admmq_packed_idwgemm on the codes x [nb, K, H, W] -> [nb, M, Ho, Wo] (float or
+// codes). Both counters are int32 [1] device tensors (clamped is empty without a codes output,
+// mid_clamped without count_mid: a counter that is not asked for costs no memset).
+int64_t taps_kp(int64_t K) { return 64 * ((K + 63) / 64); }
+
+at::Tensor packed_taps_i8_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t ntaps, int64_t K) {
+  TORCH_CHECK(ntaps >= 1 && ntaps <= 49, "admmq: packed_taps_i8: ntaps must be 1..49, got ", ntaps);
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, ntaps, K, "packed_taps_i8", meta);
+  const c10::DeviceGuard guard(cc.device());
+  at::Tensor image = at::empty({ntaps, taps_kp(K)}, cc.options().dtype(at::kChar));
+  check_rc(admmq_packed_taps_i8(cc.data_ptr<uint8_t>(), &meta, static_cast<int32_t>(ntaps), K, image.data_ptr<int8_t>(),
+                                stream_of(cc)),
+           "packed_taps_i8");
+  return image;
+}
+
+at::Tensor packed_taps_i8_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t ntaps, int64_t K) {
+  TORCH_CHECK(ntaps >= 1 && ntaps <= 49, "admmq: packed_taps_i8: ntaps must be 1..49, got ", ntaps);
+  TORCH_CHECK(K > 0, "admmq: packed_taps_i8: K must be positive");
+  return at::empty({ntaps, taps_kp(K)}, codes.options().dtype(at::kChar));
+}
+
+std::vector<int64_t> packed_idwgemm_shape(const at::Tensor& x, const at::Tensor& taps, int64_t M, int64_t K, int64_t kh,
+                                          int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_idwgemm: M and K must be positive");
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == K, "admmq: packed_idwgemm: x must be [n, ", K, ", H, W], got ", x.sizes());
+  TORCH_CHECK(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "admmq: packed_idwgemm: kernel size must be 1..7 x 1..7");
+  TORCH_CHECK(sh >= 1 && sw >= 1, "admmq: packed_idwgemm: stride must be at least 1");
+  TORCH_CHECK(ph >= 0 && ph < kh && pw >= 0 && pw < kw, "admmq: packed_idwgemm: padding must be in [0, kernel size)");
+  TORCH_CHECK(taps.dim() == 2 && taps.size(0) == kh * kw && taps.size(1) == taps_kp(K),
+              "admmq: packed_idwgemm: taps_i8 must be [", kh * kw, ", ", taps_kp(K), "], got ", taps.sizes());
+  const int64_t H = x.size(2), W = x.size(3);
+  TORCH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "admmq: packed_idwgemm: the ", kh, " x ", kw,
+              " window does not fit the padded image of x ", x.sizes());
+  return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_cuda(
+    const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits,
+    double x_mn, double x_rng, const at::Tensor& taps_i8, double s_c, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+    int64_t ph, int64_t pw, const at::Tensor& rowsums, const std::optional<at::Tensor>& bias, int64_t mid_bits,
+    double mid_mn, double mid_rng, int64_t out_bits, double out_mn, double out_rng, bool out_codes, bool count_mid) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte, "admmq: packed_idwgemm: x must be a uint8 code tensor on the GPU");
+  TORCH_CHECK(taps_i8.is_cuda() && taps_i8.scalar_type() == at::kChar,
+              "admmq: packed_idwgemm: taps_i8 must be an int8 tensor on the GPU (packed_taps_i8 makes it)");
+  const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_idwgemm");
+  const admmq_actq mq = codeq_of(mid_bits, mid_mn, mid_rng, "packed_idwgemm");
+  const admmq_actq oq = out_codes ? codeq_of(out_bits, out_mn, out_rng, "packed_idwgemm") : actq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_idwgemm", meta);
+  check_same_device(codes, x, "codes");
+  check_same_device(taps_i8, x, "taps_i8");
+  TORCH_CHECK(rowsums.is_cuda() && rowsums.scalar_type() == at::kInt && rowsums.dim() == 1 && rowsums.size(0) == M,
+              "admmq: packed_idwgemm: rowsums must be an int32 [", M, "] tensor on the GPU");
+  check_same_device(rowsums, x, "rowsums");
+  const std::vector<int64_t> oshape = packed_idwgemm_shape(x, taps_i8, M, K, kh, kw, sh, sw, ph, pw);
+  TORCH_CHECK(std::max(sh, sw) <= INT32_MAX && x.size(0) <= INT32_MAX, "admmq: packed_idwgemm: sizes out of range");
+  TORCH_CHECK(x.numel() > 0, "admmq: packed_idwgemm: empty x");
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor rc = rowsums.contiguous();
+  at::Tensor tc = taps_i8.contiguous();
+  if ((reinterpret_cast<uintptr_t>(tc.data_ptr()) & 15) != 0) tc = tc.clone();   // (a view into a larger buffer)
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(!(bias->requires_grad() && at::GradMode::is_enabled()),
+                "admmq: packed_idwgemm is inference only (no backward through packed weights): call it under "
+                "torch.no_grad() or detach bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_idwgemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int32_t nb = static_cast<int32_t>(xc.size(0));
+  at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
+  at::Tensor mid_clamped = at::empty({count_mid ? 1 : 0}, xc.options().dtype(at::kInt));   // (not counted: no memset)
+  at::Tensor clamped = at::empty({out_codes ? 1 : 0}, xc.options().dtype(at::kInt));
+  const size_t nbytes = admmq_packed_idwgemm_workspace_size(M, K, oshape[2], oshape[3], nb);
+  at::Tensor ws;   // (the serial regime needs none: no allocation)
+  if (nbytes > 0) ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_idwgemm(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<uint8_t>(), &xq, nb, xc.size(2), xc.size(3),
+                                tc.data_ptr<int8_t>(), static_cast<float>(s_c), static_cast<int32_t>(kh),
+                                static_cast<int32_t>(kw), static_cast<int32_t>(sh), static_cast<int32_t>(sw),
+                                static_cast<int32_t>(ph), static_cast<int32_t>(pw), rc.data_ptr<int32_t>(),
+                                bc.defined() ? bc.data_ptr<float>() : nullptr, out_codes ? nullptr : y.data_ptr<float>(),
+                                out_codes ? y.data_ptr<uint8_t>() : nullptr, &mq, &oq, count_mid ? mid_clamped.data_ptr<int32_t>() : nullptr,
+                                out_codes ? clamped.data_ptr<int32_t>() : nullptr, nbytes > 0 ? ws.data_ptr() : nullptr,
+                                nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
+           "packed_idwgemm");
+  return {y, mid_clamped, clamped};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_meta(
+    const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits,
+    double x_mn, double x_rng, const at::Tensor& taps_i8, double s_c, int64_t kh, int64_t kw, int64_t sh, int64_t sw,
+    int64_t ph, int64_t pw, const at::Tensor& rowsums, const std::optional<at::Tensor>& bias, int64_t mid_bits,
+    double mid_mn, double mid_rng, int64_t out_bits, double out_mn, double out_rng, bool out_codes, bool count_mid) {
+  (void)codeq_of(x_bits, x_mn, x_rng, "packed_idwgemm");
+  (void)codeq_of(mid_bits, mid_mn, mid_rng, "packed_idwgemm");
+  if (out_codes) (void)codeq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
+  else (void)actq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
+  return {at::empty(packed_idwgemm_shape(x, taps_i8, M, K, kh, kw, sh, sw, ph, pw),
+                    x.options().dtype(out_codes ? at::kByte : at::kFloat)),
+          at::empty({count_mid ? 1 : 0}, x.options().dtype(at::kInt)),
+          at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
+}
+
 at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
                             const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias) {
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
@@ -838,6 +949,11 @@ TORCH_LIBRARY(admmq, m) {
   m.def("packed_igemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_bits, float x_mn, "
         "float x_rng, Tensor rowsums, int x_layout, Tensor? bias, int out_bits, float out_mn, float out_rng, "
         "bool out_codes) -> (Tensor y, Tensor clamped)");
+  m.def("packed_taps_i8(Tensor codes, Tensor meta_words, int ntaps, int K) -> Tensor");
+  m.def("packed_idwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, int x_bits, float x_mn, float x_rng, "
+        "Tensor taps_i8, float s_c, int kh, int kw, int sh, int sw, int ph, int pw, Tensor rowsums, Tensor? bias, "
+        "int mid_bits, float mid_mn, float mid_rng, int out_bits, float out_mn, float out_rng, bool out_codes, "
+        "bool count_mid) -> (Tensor y, Tensor mid_clamped, Tensor clamped)");
   m.def("quantize_channel(Tensor x, int bits, int qscheme, int dim) -> Tensor");
   m.def("cp_gram_mttkrp(Tensor[] W, Tensor[] factors, int mode) -> (Tensor[] G, Tensor[] F)");
   m.def("cp_rel_error(Tensor[] W, Tensor[] factors) -> Tensor");
@@ -858,6 +974,8 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("act_decode", &act_decode_cuda);
   m.impl("packed_rowsums", &packed_rowsums_cuda);
   m.impl("packed_igemm", &packed_igemm_cuda);
+  m.impl("packed_taps_i8", &packed_taps_i8_cuda);
+  m.impl("packed_idwgemm", &packed_idwgemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_cuda);
   m.impl("cp_rel_error", &cp_rel_error_cuda);
@@ -877,6 +995,8 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("act_decode", &act_decode_meta);
   m.impl("packed_rowsums", &packed_rowsums_meta);
   m.impl("packed_igemm", &packed_igemm_meta);
+  m.impl("packed_taps_i8", &packed_taps_i8_meta);
+  m.impl("packed_idwgemm", &packed_idwgemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);
   m.impl("cp_gram_mttkrp", &cp_gram_mttkrp_meta);
   m.impl("cp_rel_error", &cp_rel_error_meta);

@@ -349,6 +349,59 @@ int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
                            int32_t nb, const float* bias, float* y, uint8_t* y_codes, const admmq_actq* out_q,
                            int32_t* clamped, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Integer fused depthwise + 1x1: admmq_packed_dwgemm_act's stage on activation
+ * codes, in integer arithmetic from the stencil to the GEMM (v_mfma_i32_32x32x32_i8). With it a
+ * 3-way CP layer's activations are uint8 codes from its input encode to its last epilogue.
+ *   t_codes [nb, K, H, W] uint8 codes of the first 1x1 stage's output, t_q their quantizer (bits
+ *           2..8): t = g_t ut + mn_t, g_t = double(rng_t) / double(n_t), n_t = 2^bits - 1
+ *   taps_i8 [kh*kw][Kp] int8, Kp = 64 ceil(K / 64): the depthwise factor C [kh*kw, K] as integers
+ *           c[tap,k] = (uc - q_c) - zp_c (columns k >= K are 0), written once per weight by
+ *           admmq_packed_taps_i8; s_c is the scale of C's host meta record (passed as the float)
+ *   codes, meta, rowsums   the packed weight D [M, K] and its row sums, as for admmq_packed_igemm
+ *   mid_q   the quantizer of the depthwise stage's output, MANDATORY, bits 2..8
+ * 1. For the output position (b, oh, ow) and channel k let V be the taps (a, bb) whose input
+ *    position (oh*sh - ph + a, ow*sw - pw + bb) lies inside the image. With the exact integers
+ *      D = sum_V c[tap,k] ut[b,k,ih,iw]        Cv = sum_V c[tap,k]        (|D| <= 49 * 128 * 255)
+ *      z = float( double(s_c) * ( g_t * double(D) + double(mn_t) * double(Cv) ) )
+ *    every operation in double, rounded separately, one rounding to float32. This is zero padding
+ *    of the de-quantized t: a position outside the image contributes the value 0, not the code 0,
+ *    so Cv depends on the position at the border. uz = encode(z; mid_q), admmq_act_encode's code
+ *    (r, qi, clamp, a NaN encodes as 0).
+ * 2. Y = D decode(uz) (+ bias) with exactly admmq_packed_igemm's contract for (M, K, N = Ho*Wo,
+ *    nb), trans_w = 0, x_layout = 0, x_q = mid_q: the same output formula, output forms (y float,
+ *    y + out_q, or y_codes under out_q) and clamped rule. The result has the bits of
+ *    admmq_packed_igemm on a uz formed by step 1, for every nb, on every call and in both
+ *    regimes; no summation order is specified.
+ * Counters (device int32, each may be NULL, each zeroed on the stream first): *mid_clamped counts
+ * the elements (b, k, oh, ow) of Z whose code was clamped, each once; *clamped is the codes
+ * output's counter as for admmq_packed_igemm.
+ * Limits: admmq_packed_dwgemm's geometry limits (1 <= kh, kw <= 7; sh, sw >= 1; 0 <= ph < kh,
+ * 0 <= pw < kw; Ho, Wo >= 1; nb*K*H*W < 2^40; no dilation, no groups) and admmq_packed_igemm's
+ * (K <= 65536, an int8-fitting a, no tensor_minmax). codes and taps_i8: device, 16-byte aligned;
+ * t_codes: device, any address. All refusals come before any launch, each with its own
+ * admmq_last_error text: the union of admmq_packed_dwgemm's and admmq_packed_igemm's, plus
+ * ADMMQ_ERR_ARG for mid_q NULL / off / bits outside 2..8 and t_q bits outside 2..8;
+ * ADMMQ_ERR_WORKSPACE for a short workspace. No allocation, no synchronisation.
+ * admmq_packed_idwgemm_workspace_size(M, K, Ho, Wo, nb) equals
+ * admmq_packed_igemm_workspace_size(M, K, Ho*Wo, nb): there is no buffer for Z or its codes.
+ *
+ * admmq_packed_taps_i8 expands the packed C (codes: device, 16-byte aligned; meta: its HOST
+ * record; ntaps = kh*kw <= 49) into `image` (device, 16-byte aligned,
+ * admmq_packed_taps_i8_bytes(ntaps, K) = ntaps * Kp bytes; 0 for arguments out of range). It
+ * refuses what admmq_packed_rowsums refuses of a record (ADMMQ_ERR_SCHEME for tensor_minmax,
+ * ADMMQ_ERR_ARG for an affine record outside int8 or bad != 0), NULL pointers, non-positive
+ * sizes, ntaps > 49, K > 65536 and misaligned pointers. */
+size_t admmq_packed_taps_i8_bytes(int32_t ntaps, int64_t K);
+int32_t admmq_packed_taps_i8(const uint8_t* codes, const admmq_qmeta* meta, int32_t ntaps, int64_t K, int8_t* image,
+                             void* stream);
+size_t admmq_packed_idwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb);
+int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const uint8_t* t_codes,
+                             const admmq_actq* t_q, int32_t nb, int64_t H, int64_t W, const int8_t* taps_i8, float s_c,
+                             int32_t kh, int32_t kw, int32_t sh, int32_t sw, int32_t ph, int32_t pw,
+                             const int32_t* rowsums, const float* bias, float* y, uint8_t* y_codes,
+                             const admmq_actq* mid_q, const admmq_actq* out_q, int32_t* mid_clamped, int32_t* clamped,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

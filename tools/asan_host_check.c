@@ -315,6 +315,75 @@ int main(void) {
       fails += IG(&qm, 512, 1141, &a8, 4, 1, 0, NULL, yc, &a8, 16) != ADMMQ_ERR_WORKSPACE;
       fails += IG(&qm, 512, 1141, &a8, 4, 1, 0, y, NULL, NULL, 16) != ADMMQ_ERR_WORKSPACE;
 #undef IG
+      /* integer fused depthwise + 1x1: the workspace identity over ragged sizes, the
+       * tap image's size, then every refusal of the two entry points */
+      const int8_t* ti = (const int8_t*)0x70000;
+      int32_t* mc = (int32_t*)0x60000;
+      admmq_actq a6 = {6, 1, -1.f, 2.f};
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, 6000), K = rnd(1, 70000), Ho = rnd(1, t % 3 ? 9 : 70), Wo = rnd(1, t % 3 ? 9 : 70);
+        const int32_t nb = rnd(1, 8);
+        const size_t w = admmq_packed_idwgemm_workspace_size(M, K, Ho, Wo, nb);
+        fails += w != admmq_packed_igemm_workspace_size(M, K, Ho * Wo, nb);
+        fails += K > 65536 && w != 0;
+        const int32_t nt = rnd(1, 49);
+        fails += admmq_packed_taps_i8_bytes(nt, K) != (K > 65536 ? 0 : (size_t)nt * (size_t)(64 * ((K + 63) / 64)));
+      }
+      fails += admmq_packed_idwgemm_workspace_size(512, 1141, 7, 7, 1) != (size_t)18 * 512 * 49 * 4;
+      fails += admmq_packed_idwgemm_workspace_size(8, 8, 0, 4, 1) != 0;
+      fails += admmq_packed_idwgemm_workspace_size(8, 8, 4, (int64_t)1 << 31, 1) != 0;
+      fails += admmq_packed_taps_i8_bytes(0, 8) != 0;
+      fails += admmq_packed_taps_i8_bytes(50, 8) != 0;
+      fails += admmq_packed_taps_i8_bytes(9, 0) != 0;
+      fails += admmq_packed_taps_i8(NULL, &qm, 9, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, NULL, 9, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 9, 8, NULL, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 0, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 50, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 9, 0, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 9, 65537, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      fails += admmq_packed_taps_i8(c, &qm, 9, 8, (int8_t*)0x70004, NULL) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX;
+      fails += admmq_packed_taps_i8(c, &q2, 9, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_SCHEME;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 1;
+      fails += admmq_packed_taps_i8(c, &q2, 9, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 1;
+      fails += admmq_packed_taps_i8(c, &q2, 9, 8, (int8_t*)ti, NULL) != ADMMQ_ERR_ARG;
+#define IDW(mm, M, K, tq, H, W, tt, kh, sh, ph, yy, yyc, mq, oq, wsb)                                                     \
+  admmq_packed_idwgemm(c, mm, M, K, xc, tq, 1, H, W, tt, 0.125f, kh, 3, sh, 1, ph, 1, rs, NULL, yy, yyc, mq, oq, mc, cl, ws, \
+                       wsb, NULL)
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX;
+      fails += IDW(&q2, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_SCHEME;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = -1;
+      fails += IDW(&q2, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(NULL, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, NULL, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a1, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a9, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, NULL, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, (const int8_t*)0x70008, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, NULL, NULL, 1 << 20) != ADMMQ_ERR_ARG;   /* mid_q is mandatory */
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &aoff, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a1, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a9, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, NULL, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, yc, &a6, &a8, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, NULL, yc, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, NULL, yc, &a6, &a9, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, &wide, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 8, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 0, 1, 0, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 0, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, 3, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 6, 6, ti, 3, 1, -1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 8, &a8, 1, 6, ti, 5, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;   /* 1 + 2 < 5 */
+      fails += IDW(&qm, 8, 8, &a8, 0, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 0, 8, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 65537, &a8, 6, 6, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 8, 65536, &a8, 1 << 12, 1 << 12, ti, 3, 1, 1, y, NULL, &a6, NULL, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += IDW(&qm, 512, 1141, &a8, 2, 2, ti, 3, 1, 1, y, NULL, &a6, NULL, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += IDW(&qm, 512, 1141, &a8, 2, 2, ti, 3, 1, 1, NULL, yc, &a6, &a8, 16) != ADMMQ_ERR_WORKSPACE;
+#undef IDW
     }
   }
   printf("last error: %s\n", admmq_last_error());
