@@ -324,6 +324,25 @@ void launch_qfinal_pack(const QJob* jobs, const Chunk* chunks, int nchunks, int 
                         ::admmq_qmeta* meta, int ncand, int bits, int qscheme, hipStream_t s);
 void launch_dequant_pack(const DqBatch& b, int nblocks, const ::admmq_qmeta* meta, hipStream_t s);
 
+// Host side of the packed layers (packed_gemm.hip; used by packed_igemm.hip too). The plan of
+// one call: K pieces of kp, np of them, run in parallel (one workgroup per piece, partial
+// images in the workspace of ws bytes) or serially; 64 x 64 tiles over M and the C = nb N columns.
+struct PackedPlan {
+  int kp, np, parallel;
+  long long tiles_m, tiles_c, C, total;
+  size_t ws;
+};
+bool plan_packed(int64_t M, int64_t K, int64_t N, int64_t nb, int BK, int64_t Kmax, size_t elem_bytes, PackedPlan& pl);
+bool plan_packed_dw(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int64_t nb, int BK, int64_t Kmax, size_t elem_bytes,
+                    PackedPlan& pl);
+// Argument checks: ADMMQ_OK, or the error set as "<who>: <what>" (set_error) and its code
+int packed_fail(const char* who, int code, const char* what);
+int packed_meta_check(const ::admmq_qmeta* meta, const char* who, bool integer_form, int* off);
+int packed_dw_geometry_check(const char* who, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+                             int64_t* Ho, int64_t* Wo);
+int packed_dw_extent_check(const char* who, int64_t nb, int64_t K, int64_t H, int64_t W);
+int packed_ws_check(const char* who, const PackedPlan& pl, const void* workspace, size_t workspace_bytes, const char* elem);
+
 constexpr int kSseQuads = 512;      // quads per stage-2 / exhaustive SSE work unit (8 KiB LDS)
 constexpr int kHistElems = 4096;    // elements per stage-1 work unit x hist_nv (1024 x 4 legacy, 512 x 8 merged)
 constexpr int kHistMultiRounds = 2;   // non-fused search: units per block sized for ~2 rounds of kHistMaxUnits blocks

@@ -19,25 +19,25 @@
 // workgroup runs all pieces of its tile and folds the accumulator at each piece end) and
 // parallel (one workgroup per piece writes its partial image to the workspace, and
 // k_packed_reduce adds the images in piece order). The planner takes the parallel form when
-// the serial one would start fewer than kPgParallelBelow workgroups (the weight-streaming
+// the serial one would start fewer than kPackedParallelBelow workgroups (the weight-streaming
 // regime: few columns, the work is reading the code stream). No workgroup waits for
 // another, and nothing is combined with atomics.
+//
+// The host pieces that the integer path (packed_igemm.hip) uses too - the planner and the
+// argument checks - are defined here and declared in admmq_internal.h.
 #include <algorithm>
 #include <type_traits>
 
 #include "../../include/admmq.h"
-#include "quant_device.h"
+#include "packed_tile.h"
 
 namespace admmq {
 
-constexpr int kPgBM = 64, kPgBN = 64, kPgBK = 32;
+constexpr int kPgBK = 32;               // the K step
 constexpr int kPgLD = 65;               // LDS row stride: the k-major fragment reads and both store patterns spread over the banks
-constexpr int kPgPieceMin = 64;         // K per piece at least
-constexpr int kPgPiecesMax = 32;        // pieces at most
-constexpr int kPgParallelBelow = 256;   // tiles below which the pieces run in parallel (one workgroup per CU at least)
+constexpr int64_t kPgKMax = int64_t(1) << 24;
 
 typedef float pg_f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(1))) const unsigned gcu32;   // (gcf32: admmq_internal.h)
 
 struct PgArgs {
   const unsigned char* codes;
@@ -61,16 +61,13 @@ struct PgArgsQ : PgArgs {
   ActQ oq;
 };
 
-// C/D map of v_mfma_f32_32x32x2_f32: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#define PG_ROW(r) (((r) & 3) + 8 * ((r) >> 2) + 4 * h)
-
 // The per-step addresses are hoisted: a run's bit offset in its first dword is the same in
 // every step (a step advances the stream by 32 (x M) BITS bits: whole dwords), so the thread
 // keeps one dword index and adds a constant; X is read through one pointer plus 8 fixed
 // offsets. FULL steps (all 32 k inside the piece) load without k tests; columns past C read
 // a clamped (valid) address and are zeroed by a select, not a branch.
 // OQ: the serial form's epilogue stores fixed_quant(tot (+ bias)) (the parallel form quantizes
-// in k_packed_reduce_q and runs the plain kernel).
+// in k_packed_reduce<true> and runs the plain kernel).
 template <int BITS, bool TRANS, bool XL, bool OQ = false>
 __global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ, PgArgsQ, PgArgs> a) {
   __shared__ float sW[2][kPgBK * kPgLD];
@@ -79,8 +76,8 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ
   const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
   const int M = a.M, K = a.K, N = a.N;
   const long long C = a.C;
-  const int m0 = (int)blockIdx.y * kPgBM;
-  const long long c0 = (long long)blockIdx.x * kPgBN;
+  const int m0 = (int)blockIdx.y * kPackedBM;
+  const long long c0 = (long long)blockIdx.x * kPackedBN;
   const int piece = (int)blockIdx.z;
   const int kb = a.parallel ? piece * a.kp : 0;
   const int ke = a.parallel ? min(K, kb + a.kp) : K;
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ
     const float bv = bias ? bias[m] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const long long c = c0 + 32 * wn + PG_ROW(r);
+      const long long c = c0 + 32 * wn + PACKED_ROW(r);
       if constexpr (OQ) {
         if (c < C) dst[c * M + m] = fixed_quant(bias ? tot[r] + bv : tot[r], a.oq);
       } else {
@@ -248,7 +245,7 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ
     const long long ybase = b * M * N + (c - b * N);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * wm + PG_ROW(r);
+      const int m = m0 + 32 * wm + PACKED_ROW(r);
       if constexpr (OQ) {
         if (m < M) dst[ybase + (long long)m * N] = fixed_quant(bias ? tot[r] + bias[m] : tot[r], a.oq);
       } else {
@@ -259,27 +256,17 @@ __global__ __launch_bounds__(256) void k_packed_gemm(const std::conditional_t<OQ
 }
 
 // Y[e] = ((part_0[e] + part_1[e]) + ...) + bias[m(e)]: the piece order of the serial form
+// OQ: the output quantizer behind the bias (the plain form does not read oq)
+template <bool OQ>
 __global__ __launch_bounds__(256) void k_packed_reduce(const float* __restrict__ part, int np, long long total,
                                                        const float* __restrict__ bias, float* __restrict__ y, int M,
-                                                       int N, int xl) {
+                                                       int N, int xl, const ActQ oq) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
   float s = part[e];
   for (int p = 1; p < np; ++p) s = s + part[(long long)p * total + e];
   if (bias) s = s + bias[xl ? e % M : (e / N) % M];
-  y[e] = s;
-}
-
-// k_packed_reduce with the output quantizer behind the bias (a kernel of its own: the plain one keeps its code)
-__global__ __launch_bounds__(256) void k_packed_reduce_q(const float* __restrict__ part, int np, long long total,
-                                                         const float* __restrict__ bias, float* __restrict__ y, int M,
-                                                         int N, int xl, const ActQ oq) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  float s = part[e];
-  for (int p = 1; p < np; ++p) s = s + part[(long long)p * total + e];
-  if (bias) s = s + bias[xl ? e % M : (e / N) % M];
-  y[e] = fixed_quant(s, oq);
+  y[e] = OQ ? fixed_quant(s, oq) : s;
 }
 
 // Fused depthwise kh x kw + 1x1 stage of a packed CP layer (include/admmq.h "Fused depthwise
@@ -336,8 +323,8 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const std::conditional_t<
   const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
   const int M = a.M, K = a.K, N = a.N;
   const long long C = a.C;
-  const int m0 = (int)blockIdx.y * kPgBM;
-  const long long c0 = (long long)blockIdx.x * kPgBN;
+  const int m0 = (int)blockIdx.y * kPackedBM;
+  const long long c0 = (long long)blockIdx.x * kPackedBN;
   const int piece = (int)blockIdx.z;
   const int kb = a.parallel ? piece * a.kp : 0;
   const int ke = a.parallel ? min(K, kb + a.kp) : K;
@@ -533,7 +520,7 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const std::conditional_t<
   const long long ybase = b * M * N + (c - b * N);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int m = m0 + 32 * wm + PG_ROW(r);
+    const int m = m0 + 32 * wm + PACKED_ROW(r);
     if constexpr ((QM & 2) != 0) {
       if (m < M) dst[ybase + (long long)m * N] = fixed_quant(bias ? tot[r] + bias[m] : tot[r], d.oq);
     } else {
@@ -544,42 +531,236 @@ __global__ __launch_bounds__(256) void k_packed_dwgemm(const std::conditional_t<
 
 #undef PG_DW_CALL
 
-struct PgPlan {
-  int kp, np, parallel;
-  long long tiles_m, tiles_c, C, total;
-  size_t ws;
-};
+// --- host pieces shared with packed_igemm.hip (declared in admmq_internal.h) -----------------------
 
-// A function of the four sizes alone; false when they are out of range.
-static bool plan_packed_gemm(int64_t M, int64_t K, int64_t N, int64_t nb, PgPlan& pl) {
+int packed_fail(const char* who, int code, const char* what) {
+  static thread_local char msg[200];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  return set_error(code, msg);
+}
+
+// A function of the sizes alone; false when they are out of range. A K step of BK, K <= Kmax,
+// partial images of elem_bytes an element.
+bool plan_packed(int64_t M, int64_t K, int64_t N, int64_t nb, int BK, int64_t Kmax, size_t elem_bytes, PackedPlan& pl) {
   if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return false;
-  if (M > (int64_t(1) << 22) || K > (int64_t(1) << 24) || N > (int64_t(1) << 30) || nb > (int64_t(1) << 30)) return false;
-  if (M * K >= (int64_t(1) << 40)) return false;
+  if (M > (int64_t(1) << 22) || K > Kmax || N > (int64_t(1) << 30) || nb > (int64_t(1) << 30)) return false;
   const int64_t C = nb * N;
   if (C > (int64_t(1) << 30)) return false;
   pl.C = C;
   pl.total = C * M;   // < 2^52
-  pl.kp = (int)std::max<int64_t>(kPgPieceMin, 32 * ((K + 32 * kPgPiecesMax - 1) / (32 * kPgPiecesMax)));
+  const int64_t span = (int64_t)BK * kPackedPiecesMax;
+  pl.kp = (int)std::max<int64_t>(kPackedPieceMin, BK * ((K + span - 1) / span));
   pl.np = (int)((K + pl.kp - 1) / pl.kp);
-  pl.tiles_m = (M + kPgBM - 1) / kPgBM;
-  pl.tiles_c = (C + kPgBN - 1) / kPgBN;
-  pl.parallel = (pl.np > 1 && pl.tiles_m * pl.tiles_c < kPgParallelBelow) ? 1 : 0;
-  pl.ws = pl.parallel ? (size_t)pl.np * (size_t)pl.total * sizeof(float) : 0;
+  pl.tiles_m = (M + kPackedBM - 1) / kPackedBM;
+  pl.tiles_c = (C + kPackedBN - 1) / kPackedBN;
+  pl.parallel = (pl.np > 1 && pl.tiles_m * pl.tiles_c < kPackedParallelBelow) ? 1 : 0;
+  pl.ws = pl.parallel ? (size_t)pl.np * (size_t)pl.total * elem_bytes : 0;
   return true;
+}
+
+// plan_packed for a depthwise stage's Ho x Wo output positions
+bool plan_packed_dw(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int64_t nb, int BK, int64_t Kmax, size_t elem_bytes,
+                    PackedPlan& pl) {
+  if (Ho <= 0 || Wo <= 0 || Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30)) return false;
+  return plan_packed(M, K, Ho * Wo, nb, BK, Kmax, elem_bytes, pl);
+}
+
+// The weight record's checks. The float form takes every tensor scheme (tensor_minmax from 2
+// bits); the integer form needs W = scale * int8: no tensor_minmax, and (u - q) - zero_point
+// inside int8 - then *off = q + zero_point.
+int packed_meta_check(const ::admmq_qmeta* meta, const char* who, bool integer_form, int* off) {
+  if (meta->bits < 1 || meta->bits > 8) return packed_fail(who, ADMMQ_ERR_ARG, "meta bits must be 1..8");
+  if (meta->scheme < kMse || meta->scheme > kAffine)
+    return packed_fail(who, ADMMQ_ERR_ARG, "unknown meta scheme (the four tensor schemes only)");
+  if (integer_form && meta->scheme == kMinMax)
+    return packed_fail(who, ADMMQ_ERR_SCHEME,
+                       "tensor_minmax weights have no integer form (their de-quantization is not scale * integer)");
+  if (!integer_form && meta->scheme == kMinMax && meta->bits == 1)
+    return packed_fail(who, ADMMQ_ERR_ARG, "tensor_minmax has no 1 bit code");
+  if (meta->bad != 0) return packed_fail(who, ADMMQ_ERR_ARG, "meta bad != 0: not a valid packed tensor");
+  if (integer_form) {
+    const int64_t q = int64_t(1) << (meta->bits - 1);
+    const int64_t zp = meta->scheme == kAffine ? (int64_t)meta->zero_point : 0;
+    if (-q - zp < -128 || q - 1 - zp > 127)
+      return packed_fail(who, ADMMQ_ERR_ARG, "affine zero_point puts (u - q) - zero_point outside int8");
+    *off = (int)(q + zp);
+  }
+  return ADMMQ_OK;
+}
+
+// The depthwise window's checks; the output's Ho x Wo on success
+int packed_dw_geometry_check(const char* who, int64_t H, int64_t W, int kh, int kw, int sh, int sw, int ph, int pw,
+                             int64_t* Ho, int64_t* Wo) {
+  if (kh < 1 || kh > 7 || kw < 1 || kw > 7) return packed_fail(who, ADMMQ_ERR_ARG, "kernel size must be 1..7 x 1..7");
+  if (sh < 1 || sw < 1) return packed_fail(who, ADMMQ_ERR_ARG, "stride must be at least 1");
+  if (ph < 0 || ph >= kh || pw < 0 || pw >= kw) return packed_fail(who, ADMMQ_ERR_ARG, "padding must be in [0, kernel size)");
+  if (H > (int64_t(1) << 40) || W > (int64_t(1) << 40) || H > (int64_t(1) << 40) / W)
+    return packed_fail(who, ADMMQ_ERR_ARG, "sizes out of range");
+  if (H + 2 * ph < kh || W + 2 * pw < kw)
+    return packed_fail(who, ADMMQ_ERR_ARG, "the window does not fit the padded image (Ho, Wo >= 1)");
+  *Ho = (H + 2 * ph - kh) / sh + 1;
+  *Wo = (W + 2 * pw - kw) / sw + 1;
+  return ADMMQ_OK;
+}
+
+// The depthwise input's extent: nb K H W <= 2^40 - 1, tested without overflow
+int packed_dw_extent_check(const char* who, int64_t nb, int64_t K, int64_t H, int64_t W) {
+  const int64_t tmax = (int64_t(1) << 40) - 1;
+  if (K > tmax / (H * W) || nb > tmax / (H * W * K))
+    return packed_fail(who, ADMMQ_ERR_ARG, "sizes out of range (nb K H W must be below 2^40)");
+  return ADMMQ_OK;
+}
+
+// The parallel form's workspace: present, large enough, aligned for its elements (elem: their name in the message)
+int packed_ws_check(const char* who, const PackedPlan& pl, const void* workspace, size_t workspace_bytes, const char* elem) {
+  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
+  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0) {
+    char what[64];
+    snprintf(what, sizeof what, "workspace must be %s aligned", elem);
+    return packed_fail(who, ADMMQ_ERR_ARG, what);
+  }
+  return ADMMQ_OK;
+}
+
+// --- the float entry points -------------------------------------------------------------------------
+
+// The float path's plan: K up to 2^24, and the code stream's M K below 2^40
+static bool plan_pg(int64_t M, int64_t K, int64_t N, int64_t nb, PackedPlan& pl) {
+  return plan_packed(M, K, N, nb, kPgBK, kPgKMax, sizeof(float), pl) && M * K < (int64_t(1) << 40);
+}
+static bool plan_pg_dw(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int64_t nb, PackedPlan& pl) {
+  return plan_packed_dw(M, K, Ho, Wo, nb, kPgBK, kPgKMax, sizeof(float), pl) && M * K < (int64_t(1) << 40);
 }
 
 // The kernels' form of a caller's quantizer; false for none (NULL or on == 0). bits checked by the caller.
 static bool actq_on(const admmq_actq* q) { return q && q->on != 0; }
 static bool actq_bits_ok(const admmq_actq* q) { return !actq_on(q) || (q->bits >= 1 && q->bits <= 24); }
+static ActQ actq_or_none(const admmq_actq* q) { return actq_on(q) ? actq_make(q) : ActQ{0.f, 0.f, 0.f, 0}; }
+
+static void pg_fill(PgArgs& a, const uint8_t* codes, const admmq_qmeta* meta, const float* x, const float* bias, float* y,
+                    void* workspace, const PackedPlan& pl, int64_t M, int64_t K, int64_t N, int32_t x_layout) {
+  a.codes = codes; a.x = x; a.bias = bias; a.y = y;
+  a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
+  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
+  a.total = pl.total; a.C = pl.C;
+  a.M = (int)M; a.K = (int)K; a.N = (int)N;
+  a.xl = x_layout;
+  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
+  a.scheme = meta->scheme;
+  a.zp = meta->scheme == kAffine ? meta->zero_point : 0;   // (the other schemes' table has none)
+  a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
+}
+
+static dim3 packed_grid(const PackedPlan& pl) {
+  return dim3((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
+}
+
+// The parallel form's second kernel (the output quantizer runs here, behind the bias), then the launches' status
+static int32_t pg_finish(const PgArgs& a, const PackedPlan& pl, bool oq, const ActQ& q, hipStream_t s) {
+  const dim3 grid((unsigned)((pl.total + 255) / 256));
+  if (pl.parallel && oq)
+    hipLaunchKernelGGL(k_packed_reduce<true>, grid, dim3(256), 0, s, a.part, pl.np, pl.total, a.bias, a.y, a.M, a.N, a.xl, q);
+  else if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_reduce<false>, grid, dim3(256), 0, s, a.part, pl.np, pl.total, a.bias, a.y, a.M, a.N, a.xl, q);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
 
 static int32_t packed_gemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
                                const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
-                               const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream);
+                               const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* const who = "packed_gemm";
+  if (!codes || !x || !y || !meta) return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes, meta, x and y must not be NULL");
+  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: M, K, N and nb must be positive");
+  int32_t rc = packed_meta_check(meta, who, false, nullptr);
+  if (rc != ADMMQ_OK) return rc;
+  if (trans_w != 0 && trans_w != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: trans_w must be 0 or 1");
+  if (x_layout != 0 && x_layout != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout must be 0 or 1");
+  if (x_layout == 1 && nb != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout 1 (linear) needs nb = 1");
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes must be 16-byte aligned");
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_gemm: x, y and bias must be float aligned");
+  PackedPlan pl;
+  if (!plan_pg(M, K, N, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_gemm: sizes out of range");
+  rc = packed_ws_check(who, pl, workspace, workspace_bytes, "float");
+  if (rc != ADMMQ_OK) return rc;
+  PgArgsQ aq;   // the plain record, the output quantizer behind it
+  PgArgs& a = aq;
+  pg_fill(a, codes, meta, x, bias, y, workspace, pl, M, K, N, x_layout);
+  // the output quantizer: in the serial form's epilogue (the OQ kernels), in the parallel form's reduction
+  const bool oq = actq_on(out_q);
+  aq.oq = actq_or_none(out_q);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid = packed_grid(pl);
+#define ADMMQ_PG_LAUNCH(B, T, X)                                                                           \
+  do {                                                                                                     \
+    if (oq && !pl.parallel) hipLaunchKernelGGL((k_packed_gemm<B, T, X, true>), grid, dim3(256), 0, s, aq); \
+    else hipLaunchKernelGGL((k_packed_gemm<B, T, X>), grid, dim3(256), 0, s, a);                           \
+  } while (0)
+#define ADMMQ_PG_BITS(B)                                     \
+  if (trans_w && x_layout) ADMMQ_PG_LAUNCH(B, true, true);   \
+  else if (trans_w) ADMMQ_PG_LAUNCH(B, true, false);         \
+  else if (x_layout) ADMMQ_PG_LAUNCH(B, false, true);        \
+  else ADMMQ_PG_LAUNCH(B, false, false)
+  PACKED_BITS_SWITCH(meta->bits, ADMMQ_PG_BITS)
+#undef ADMMQ_PG_BITS
+#undef ADMMQ_PG_LAUNCH
+  return pg_finish(a, pl, oq, aq.oq, s);
+}
+
 static int32_t packed_dwgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
                                  int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
                                  int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
                                  const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
-                                 size_t workspace_bytes, void* stream);
+                                 size_t workspace_bytes, void* stream) {
+  const char* const who = "packed_dwgemm";
+  if (!codes || !t || !taps || !y || !meta)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes, meta, t, taps and y must not be NULL");
+  if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: M, K, H, W and nb must be positive");
+  int32_t rc = packed_meta_check(meta, who, false, nullptr);
+  if (rc != ADMMQ_OK) return rc;
+  int64_t Ho = 0, Wo = 0;
+  rc = packed_dw_geometry_check(who, H, W, kh, kw, sh, sw, ph, pw, &Ho, &Wo);
+  if (rc != ADMMQ_OK) return rc;
+  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes must be 16-byte aligned");
+  if (((reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(y) |
+        reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
+    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: t, taps, y and bias must be float aligned");
+  PackedPlan pl;
+  if (!plan_pg_dw(M, K, Ho, Wo, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range");
+  rc = packed_dw_extent_check(who, nb, K, H, W);
+  if (rc != ADMMQ_OK) return rc;
+  rc = packed_ws_check(who, pl, workspace, workspace_bytes, "float");
+  if (rc != ADMMQ_OK) return rc;
+  PgDwArgsQ dq;   // the plain record, the quantizers behind it
+  PgDwArgs& d = dq;
+  PgArgs& a = d.g;
+  pg_fill(a, codes, meta, t, bias, y, workspace, pl, M, K, Ho * Wo, 0);
+  d.taps = taps;
+  d.H = H; d.W = W; d.HW = H * W;
+  d.Wo = (int)Wo;
+  d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
+  // the mid quantizer runs in the kernel in both forms; the output quantizer in the serial
+  // form's epilogue or in the parallel form's reduction
+  const bool mq = actq_on(mid_q), oq = actq_on(out_q);
+  const int qm = (mq ? 1 : 0) | (oq && !pl.parallel ? 2 : 0);
+  dq.mq = actq_or_none(mid_q);
+  dq.oq = actq_or_none(out_q);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid = packed_grid(pl);
+#define ADMMQ_PG_BITS(B)                                                                        \
+  if (qm == 0) hipLaunchKernelGGL((k_packed_dwgemm<B>), grid, dim3(256), 0, s, d);              \
+  else if (qm == 1) hipLaunchKernelGGL((k_packed_dwgemm<B, 1>), grid, dim3(256), 0, s, dq);     \
+  else if (qm == 2) hipLaunchKernelGGL((k_packed_dwgemm<B, 2>), grid, dim3(256), 0, s, dq);     \
+  else hipLaunchKernelGGL((k_packed_dwgemm<B, 3>), grid, dim3(256), 0, s, dq)
+  PACKED_BITS_SWITCH(meta->bits, ADMMQ_PG_BITS)
+#undef ADMMQ_PG_BITS
+  return pg_finish(a, pl, oq, dq.oq, s);
+}
 
 }  // namespace admmq
 
@@ -588,9 +769,8 @@ using namespace admmq;
 extern "C" {
 
 size_t admmq_packed_gemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t nb) {
-  PgPlan pl;
-  if (!plan_packed_gemm(M, K, N, nb, pl)) return 0;
-  return pl.ws;
+  PackedPlan pl;
+  return plan_pg(M, K, N, nb, pl) ? pl.ws : 0;
 }
 
 int32_t admmq_packed_gemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
@@ -608,86 +788,9 @@ int32_t admmq_packed_gemm_act(const uint8_t* codes, const admmq_qmeta* meta, int
                          stream);
 }
 
-}  // extern "C"
-
-int32_t admmq::packed_gemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
-                               const float* x, int32_t x_layout, int64_t N, int32_t nb, const float* bias, float* y,
-                               const admmq_actq* out_q, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!codes || !x || !y || !meta) return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes, meta, x and y must not be NULL");
-  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: M, K, N and nb must be positive");
-  if (meta->bits < 1 || meta->bits > 8) return set_error(ADMMQ_ERR_ARG, "packed_gemm: meta bits must be 1..8");
-  if (meta->scheme < kMse || meta->scheme > kAffine)
-    return set_error(ADMMQ_ERR_ARG, "packed_gemm: unknown meta scheme (the four tensor schemes only)");
-  if (meta->scheme == kMinMax && meta->bits == 1)
-    return set_error(ADMMQ_ERR_ARG, "packed_gemm: tensor_minmax has no 1 bit code");
-  if (meta->bad != 0) return set_error(ADMMQ_ERR_ARG, "packed_gemm: meta bad != 0: not a valid packed tensor");
-  if (trans_w != 0 && trans_w != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: trans_w must be 0 or 1");
-  if (x_layout != 0 && x_layout != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout must be 0 or 1");
-  if (x_layout == 1 && nb != 1) return set_error(ADMMQ_ERR_ARG, "packed_gemm: x_layout 1 (linear) needs nb = 1");
-  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_gemm: codes must be 16-byte aligned");
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_gemm: x, y and bias must be float aligned");
-  PgPlan pl;
-  if (!plan_packed_gemm(M, K, N, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_gemm: sizes out of range");
-  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
-  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_gemm: workspace must be float aligned");
-  PgArgs a;
-  a.codes = codes; a.x = x; a.bias = bias; a.y = y;
-  a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
-  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
-  a.total = pl.total; a.C = pl.C;
-  a.M = (int)M; a.K = (int)K; a.N = (int)N;
-  a.xl = x_layout;
-  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
-  a.scheme = meta->scheme;
-  a.zp = meta->scheme == kAffine ? meta->zero_point : 0;   // (the other schemes' table has none)
-  a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-  // the output quantizer: in the serial form's epilogue (the OQ kernels), in the parallel form's reduction
-  const bool oq = actq_on(out_q);
-  PgArgsQ aq;
-  static_cast<PgArgs&>(aq) = a;
-  aq.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
-#define ADMMQ_PG_LAUNCH(B, T, X)                                                                      \
-  do {                                                                                                \
-    if (oq && !pl.parallel) hipLaunchKernelGGL((k_packed_gemm<B, T, X, true>), grid, dim3(256), 0, s, aq); \
-    else hipLaunchKernelGGL((k_packed_gemm<B, T, X>), grid, dim3(256), 0, s, a);                      \
-  } while (0)
-#define ADMMQ_PG_CASE(B)                               \
-  case B:                                              \
-    if (trans_w && x_layout) ADMMQ_PG_LAUNCH(B, true, true);   \
-    else if (trans_w) ADMMQ_PG_LAUNCH(B, true, false); \
-    else if (x_layout) ADMMQ_PG_LAUNCH(B, false, true); \
-    else ADMMQ_PG_LAUNCH(B, false, false);             \
-    break;
-  switch (meta->bits) {
-    ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
-    ADMMQ_PG_CASE(5) ADMMQ_PG_CASE(6) ADMMQ_PG_CASE(7) ADMMQ_PG_CASE(8)
-    default: break;   // (refused above)
-  }
-#undef ADMMQ_PG_CASE
-#undef ADMMQ_PG_LAUNCH
-  if (pl.parallel && oq)
-    hipLaunchKernelGGL(k_packed_reduce_q, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
-                       pl.total, bias, y, a.M, a.N, a.xl, aq.oq);
-  else if (pl.parallel)
-    hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
-                       pl.total, bias, y, a.M, a.N, a.xl);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
-  return ADMMQ_OK;
-}
-
-extern "C" {
-
 size_t admmq_packed_dwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb) {
-  PgPlan pl;
-  if (Ho <= 0 || Wo <= 0 || Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30)) return 0;
-  if (!plan_packed_gemm(M, K, Ho * Wo, nb, pl)) return 0;
-  return pl.ws;
+  PackedPlan pl;
+  return plan_pg_dw(M, K, Ho, Wo, nb, pl) ? pl.ws : 0;
 }
 
 int32_t admmq_packed_dwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
@@ -710,91 +813,3 @@ int32_t admmq_packed_dwgemm_act(const uint8_t* codes, const admmq_qmeta* meta, i
 }
 
 }  // extern "C"
-
-int32_t admmq::packed_dwgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* t,
-                                 int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw, int32_t sh,
-                                 int32_t sw, int32_t ph, int32_t pw, const float* bias, float* y,
-                                 const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  if (!codes || !t || !taps || !y || !meta)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes, meta, t, taps and y must not be NULL");
-  if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: M, K, H, W and nb must be positive");
-  if (meta->bits < 1 || meta->bits > 8) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: meta bits must be 1..8");
-  if (meta->scheme < kMse || meta->scheme > kAffine)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: unknown meta scheme (the four tensor schemes only)");
-  if (meta->scheme == kMinMax && meta->bits == 1)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: tensor_minmax has no 1 bit code");
-  if (meta->bad != 0) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: meta bad != 0: not a valid packed tensor");
-  if (kh < 1 || kh > 7 || kw < 1 || kw > 7) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: kernel size must be 1..7 x 1..7");
-  if (sh < 1 || sw < 1) return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: stride must be at least 1");
-  if (ph < 0 || ph >= kh || pw < 0 || pw >= kw)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: padding must be in [0, kernel size)");
-  if (H > (int64_t(1) << 40) || W > (int64_t(1) << 40) || H > (int64_t(1) << 40) / W)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range");
-  if (H + 2 * ph < kh || W + 2 * pw < kw)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: the window does not fit the padded image (Ho, Wo >= 1)");
-  const int64_t Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
-  if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: codes must be 16-byte aligned");
-  if (((reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(taps) | reinterpret_cast<uintptr_t>(y) |
-        reinterpret_cast<uintptr_t>(bias)) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: t, taps, y and bias must be float aligned");
-  PgPlan pl;
-  if (Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30) || !plan_packed_gemm(M, K, Ho * Wo, nb, pl))
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range");
-  const int64_t tmax = (int64_t(1) << 40) - 1;   // nb K H W <= tmax, without overflow
-  if (K > tmax / (H * W) || nb > tmax / (H * W * K))
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: sizes out of range (nb K H W must be below 2^40)");
-  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
-  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_dwgemm: workspace must be float aligned");
-  PgDwArgs d;
-  PgArgs& a = d.g;
-  a.codes = codes; a.x = t; a.bias = bias; a.y = y;
-  a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
-  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
-  a.total = pl.total; a.C = pl.C;
-  a.M = (int)M; a.K = (int)K; a.N = (int)(Ho * Wo);
-  a.xl = 0;
-  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
-  a.scheme = meta->scheme;
-  a.zp = meta->scheme == kAffine ? meta->zero_point : 0;
-  a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
-  d.taps = taps;
-  d.H = H; d.W = W; d.HW = H * W;
-  d.Wo = (int)Wo;
-  d.kh = kh; d.kw = kw; d.sh = sh; d.sw = sw; d.ph = ph; d.pw = pw;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-  // the mid quantizer runs in the kernel in both forms; the output quantizer in the serial
-  // form's epilogue or in the parallel form's reduction
-  const bool mq = actq_on(mid_q), oq = actq_on(out_q);
-  const int qm = (mq ? 1 : 0) | (oq && !pl.parallel ? 2 : 0);
-  PgDwArgsQ dq;
-  static_cast<PgDwArgs&>(dq) = d;
-  dq.mq = mq ? actq_make(mid_q) : ActQ{0.f, 0.f, 0.f, 0};
-  dq.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
-#define ADMMQ_PG_CASE(B)                                                                          \
-  case B:                                                                                         \
-    if (qm == 0) hipLaunchKernelGGL((k_packed_dwgemm<B>), grid, dim3(256), 0, s, d);              \
-    else if (qm == 1) hipLaunchKernelGGL((k_packed_dwgemm<B, 1>), grid, dim3(256), 0, s, dq);     \
-    else if (qm == 2) hipLaunchKernelGGL((k_packed_dwgemm<B, 2>), grid, dim3(256), 0, s, dq);     \
-    else hipLaunchKernelGGL((k_packed_dwgemm<B, 3>), grid, dim3(256), 0, s, dq);                  \
-    break;
-  switch (meta->bits) {
-    ADMMQ_PG_CASE(1) ADMMQ_PG_CASE(2) ADMMQ_PG_CASE(3) ADMMQ_PG_CASE(4)
-    ADMMQ_PG_CASE(5) ADMMQ_PG_CASE(6) ADMMQ_PG_CASE(7) ADMMQ_PG_CASE(8)
-    default: break;   // (refused above)
-  }
-#undef ADMMQ_PG_CASE
-  if (pl.parallel && oq)
-    hipLaunchKernelGGL(k_packed_reduce_q, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
-                       pl.total, bias, y, a.M, a.N, 0, dq.oq);
-  else if (pl.parallel)
-    hipLaunchKernelGGL(k_packed_reduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a.part, pl.np,
-                       pl.total, bias, y, a.M, a.N, 0);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
-  return ADMMQ_OK;
-}

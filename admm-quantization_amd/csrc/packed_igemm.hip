@@ -23,15 +23,12 @@
 #include <algorithm>
 
 #include "../../include/admmq.h"
-#include "quant_device.h"
+#include "packed_tile.h"
 
 namespace admmq {
 
-constexpr int kIgBM = 64, kIgBN = 64, kIgBK = 64;
+constexpr int kIgBK = 64;                // the K step (kPackedPieceMin is a multiple of it)
 constexpr int kIgLD = 80;                // LDS row stride in bytes: 16-byte aligned rows, 20 dwords apart
-constexpr int kIgPieceMin = 64;          // K per piece at least (a multiple of kIgBK)
-constexpr int kIgPiecesMax = 32;         // pieces at most
-constexpr int kIgParallelBelow = 256;    // tiles below which the pieces run in parallel (plan_packed_gemm's rule)
 constexpr int64_t kIgKMax = 65536;       // 128 255 K < 2^31
 
 typedef int ig_i32x16 __attribute__((ext_vector_type(16)));
@@ -175,9 +172,6 @@ struct IgArgs {
   ActQ oq;
 };
 
-// C/D map of the 32 x 32 MFMAs: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-#define IG_ROW(r) (((r) & 3) + 8 * ((r) >> 2) + 4 * h)
-
 // The output formula: double operations rounded one by one (-ffp-contract=off), one rounding to float32.
 // acc = sum_k a (ux - 128); S = acc + 128 A is exact in int64 and in double.
 __device__ __forceinline__ float ig_value(int acc, int A, const IgArgs& a, bool has_bias, float bv) {
@@ -191,14 +185,14 @@ constexpr int kIgFloat = 0, kIgQuant = 1, kIgCodes = 2;
 
 template <int BITS, bool TRANS, bool XL, int OUT>
 __global__ __launch_bounds__(256) void k_packed_igemm(const IgArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char sW[2][kIgBM * kIgLD];
-  __shared__ __attribute__((aligned(16))) unsigned char sX[2][kIgBN * kIgLD];
+  __shared__ __attribute__((aligned(16))) unsigned char sW[2][kPackedBM * kIgLD];
+  __shared__ __attribute__((aligned(16))) unsigned char sX[2][kPackedBN * kIgLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
   const int M = a.M, K = a.K, N = a.N;
   const long long C = a.C;
-  const int m0 = (int)blockIdx.y * kIgBM;
-  const long long c0 = (long long)blockIdx.x * kIgBN;
+  const int m0 = (int)blockIdx.y * kPackedBM;
+  const long long c0 = (long long)blockIdx.x * kPackedBN;
   const int piece = (int)blockIdx.z;
   const int kb = a.parallel ? piece * a.kp : 0;
   const int ke = a.parallel ? min(K, kb + a.kp) : K;
@@ -344,7 +338,7 @@ __global__ __launch_bounds__(256) void k_packed_igemm(const IgArgs a) {
     const float bv = (mok && hb && !a.parallel) ? a.bias[m] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const long long c = c0 + 32 * wn + IG_ROW(r);
+      const long long c = c0 + 32 * wn + PACKED_ROW(r);
       if (!mok || c >= C) continue;
       const long long e = c * M + m;
       if (a.parallel) {
@@ -365,7 +359,7 @@ __global__ __launch_bounds__(256) void k_packed_igemm(const IgArgs a) {
     const bool hb = a.bias != nullptr;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * wm + IG_ROW(r);
+      const int m = m0 + 32 * wm + PACKED_ROW(r);
       if (!ok || m >= M) continue;
       const long long e = ybase + (long long)m * N;
       if (a.parallel) {
@@ -400,48 +394,13 @@ __global__ __launch_bounds__(256) void k_packed_ireduce(const IgArgs a) {
   if (a.out == kIgCodes && a.clamped) block_count_add(cnt, a.clamped);
 }
 
-struct IgPlan {
-  int kp, np, parallel;
-  long long tiles_m, tiles_c, C, total;
-  size_t ws;
-};
-
-// plan_packed_gemm's limits and regime rule (packed_gemm.hip) with K <= 65536, pieces that are
-// multiples of the 64-wide K step and int32 partial images. A function of the four sizes alone.
-static bool plan_packed_igemm(int64_t M, int64_t K, int64_t N, int64_t nb, IgPlan& pl) {
-  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return false;
-  if (M > (int64_t(1) << 22) || K > kIgKMax || N > (int64_t(1) << 30) || nb > (int64_t(1) << 30)) return false;
-  const int64_t C = nb * N;
-  if (C > (int64_t(1) << 30)) return false;
-  pl.C = C;
-  pl.total = C * M;   // < 2^52
-  pl.kp = (int)std::max<int64_t>(kIgPieceMin, kIgBK * ((K + kIgBK * kIgPiecesMax - 1) / (kIgBK * kIgPiecesMax)));
-  pl.np = (int)((K + pl.kp - 1) / pl.kp);
-  pl.tiles_m = (M + kIgBM - 1) / kIgBM;
-  pl.tiles_c = (C + kIgBN - 1) / kIgBN;
-  pl.parallel = (pl.np > 1 && pl.tiles_m * pl.tiles_c < kIgParallelBelow) ? 1 : 0;
-  pl.ws = pl.parallel ? (size_t)pl.np * (size_t)pl.total * sizeof(int32_t) : 0;
-  return true;
+// The integer path's plan (plan_packed, packed_gemm.hip): K <= 65536, pieces that are multiples of
+// the 64-wide K step, int32 partial images
+static bool plan_ig(int64_t M, int64_t K, int64_t N, int64_t nb, PackedPlan& pl) {
+  return plan_packed(M, K, N, nb, kIgBK, kIgKMax, sizeof(int32_t), pl);
 }
-
-// The weight record's checks shared by the row sums and the GEMM; off = q + zp on success.
-static int32_t igemm_meta_check(const admmq_qmeta* meta, const char* who, int& off) {
-  static thread_local char msg[160];
-  auto fail = [&](int32_t code, const char* what) {
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return set_error(code, msg);
-  };
-  if (meta->bits < 1 || meta->bits > 8) return fail(ADMMQ_ERR_ARG, "meta bits must be 1..8");
-  if (meta->scheme < kMse || meta->scheme > kAffine) return fail(ADMMQ_ERR_ARG, "unknown meta scheme (the four tensor schemes only)");
-  if (meta->scheme == kMinMax)
-    return fail(ADMMQ_ERR_SCHEME, "tensor_minmax weights have no integer form (their de-quantization is not scale * integer)");
-  if (meta->bad != 0) return fail(ADMMQ_ERR_ARG, "meta bad != 0: not a valid packed tensor");
-  const int64_t q = int64_t(1) << (meta->bits - 1);
-  const int64_t zp = meta->scheme == kAffine ? (int64_t)meta->zero_point : 0;
-  if (-q - zp < -128 || q - 1 - zp > 127)
-    return fail(ADMMQ_ERR_ARG, "affine zero_point puts (u - q) - zero_point outside int8");
-  off = (int)(q + zp);
-  return ADMMQ_OK;
+static bool plan_ig_dw(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int64_t nb, PackedPlan& pl) {
+  return plan_packed_dw(M, K, Ho, Wo, nb, kIgBK, kIgKMax, sizeof(int32_t), pl);
 }
 
 static bool act_bits_ok(const admmq_actq* q) { return q && q->on != 0 && q->bits >= 2 && q->bits <= 8; }
@@ -453,6 +412,46 @@ static void vec_split(uintptr_t bytes_ptr, uintptr_t float_ptr, long long numel,
   if (head > numel) head = numel;
   if (((float_ptr + 4 * (uintptr_t)head) & 15) == 0) nvec = (numel - head) / 16;
   else head = numel;
+}
+
+// The GEMM's arguments common to admmq_packed_igemm and admmq_packed_idwgemm. x_q: the quantizer
+// of the GEMM's activation operand (x, or the mid quantizer of the fused stage).
+static void ig_fill(IgArgs& a, const uint8_t* codes, const admmq_qmeta* meta, int off, const uint8_t* x,
+                    const admmq_actq* x_q, const int32_t* rowsums, const float* bias, float* y, uint8_t* y_codes,
+                    const admmq_actq* out_q, int32_t* clamped, void* workspace, const PackedPlan& pl, int64_t M, int64_t K,
+                    int64_t N, int32_t x_layout) {
+  const bool oq = out_q && out_q->on != 0;
+  a.codes = codes; a.x = x; a.bias = bias; a.rowsum = rowsums; a.y = y; a.yc = y_codes;
+  a.part = pl.parallel ? static_cast<int*>(workspace) : nullptr;
+  a.clamped = y_codes ? clamped : nullptr;
+  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
+  a.total = pl.total; a.C = pl.C;
+  a.M = (int)M; a.K = (int)K; a.N = (int)N;
+  a.xl = x_layout;
+  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
+  a.off = off;
+  a.xal = (x_layout == 1 && (reinterpret_cast<uintptr_t>(x) & 3) == 0 && (K & 3) == 0) ? 1 : 0;
+  a.out = y_codes ? kIgCodes : (oq ? kIgQuant : kIgFloat);
+  a.s = (double)meta->scale;
+  a.g = (double)x_q->rng / (double)((1 << x_q->bits) - 1);
+  a.mnx = (double)x_q->mn;
+  a.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+}
+
+// Zeroes a clamp counter on the stream (none: nothing)
+static int32_t counter_reset(int32_t* counter, hipStream_t s) {
+  if (!counter) return ADMMQ_OK;
+  const hipError_t e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+  return e == hipSuccess ? ADMMQ_OK : set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
+}
+
+// The parallel form's second kernel, then the launches' status
+static int32_t ig_finish(const IgArgs& a, const PackedPlan& pl, hipStream_t s) {
+  if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_ireduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
 }
 
 }  // namespace admmq
@@ -511,7 +510,7 @@ int32_t admmq_packed_rowsums(const uint8_t* codes, const admmq_qmeta* meta, int3
   if (!codes || !meta || !rowsums) return set_error(ADMMQ_ERR_ARG, "packed_rowsums: codes, meta and rowsums must not be NULL");
   if (M <= 0 || K <= 0) return set_error(ADMMQ_ERR_ARG, "packed_rowsums: M and K must be positive");
   int off = 0;
-  const int32_t rc = igemm_meta_check(meta, "packed_rowsums", off);
+  const int32_t rc = packed_meta_check(meta, "packed_rowsums", true, &off);
   if (rc != ADMMQ_OK) return rc;
   if (trans_w != 0 && trans_w != 1) return set_error(ADMMQ_ERR_ARG, "packed_rowsums: trans_w must be 0 or 1");
   if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_rowsums: K must be at most 65536");
@@ -528,9 +527,8 @@ int32_t admmq_packed_rowsums(const uint8_t* codes, const admmq_qmeta* meta, int3
 }
 
 size_t admmq_packed_igemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t nb) {
-  IgPlan pl;
-  if (!plan_packed_igemm(M, K, N, nb, pl)) return 0;
-  return pl.ws;
+  PackedPlan pl;
+  return plan_ig(M, K, N, nb, pl) ? pl.ws : 0;
 }
 
 int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
@@ -543,7 +541,7 @@ int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
     return set_error(ADMMQ_ERR_ARG, "packed_igemm: exactly one of y and y_codes must be given");
   if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return set_error(ADMMQ_ERR_ARG, "packed_igemm: M, K, N and nb must be positive");
   int off = 0;
-  const int32_t rc = igemm_meta_check(meta, "packed_igemm", off);
+  int32_t rc = packed_meta_check(meta, "packed_igemm", true, &off);
   if (rc != ADMMQ_OK) return rc;
   if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_igemm: K must be at most 65536 (the int32 sum 128 * 255 * K)");
   if (!act_bits_ok(x_q)) return set_error(ADMMQ_ERR_ARG, "packed_igemm: x_q must be on with bits 2..8");
@@ -558,60 +556,32 @@ int32_t admmq_packed_igemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
   if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(rowsums) |
         reinterpret_cast<uintptr_t>(clamped)) & 3) != 0)
     return set_error(ADMMQ_ERR_ARG, "packed_igemm: y, bias, rowsums and clamped must be 4-byte aligned");
-  IgPlan pl;
-  if (!plan_packed_igemm(M, K, N, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_igemm: sizes out of range");
-  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
-  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_igemm: workspace must be int32 aligned");
+  PackedPlan pl;
+  if (!plan_ig(M, K, N, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_igemm: sizes out of range");
+  rc = packed_ws_check("packed_igemm", pl, workspace, workspace_bytes, "int32");
+  if (rc != ADMMQ_OK) return rc;
   IgArgs a;
-  a.codes = codes; a.x = x; a.bias = bias; a.rowsum = rowsums; a.y = y; a.yc = y_codes;
-  a.part = pl.parallel ? static_cast<int*>(workspace) : nullptr;
-  a.clamped = y_codes ? clamped : nullptr;
-  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
-  a.total = pl.total; a.C = pl.C;
-  a.M = (int)M; a.K = (int)K; a.N = (int)N;
-  a.xl = x_layout;
-  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
-  a.off = off;
-  a.xal = (x_layout == 1 && (reinterpret_cast<uintptr_t>(x) & 3) == 0 && (K & 3) == 0) ? 1 : 0;
-  const int out = y_codes ? kIgCodes : (oq ? kIgQuant : kIgFloat);
-  a.out = out;
-  a.s = (double)meta->scale;
-  a.g = (double)x_q->rng / (double)((1 << x_q->bits) - 1);
-  a.mnx = (double)x_q->mn;
-  a.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+  ig_fill(a, codes, meta, off, x, x_q, rowsums, bias, y, y_codes, out_q, clamped, workspace, pl, M, K, N, x_layout);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (a.clamped) {
-    const hipError_t e = hipMemsetAsync(a.clamped, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
-  }
+  rc = counter_reset(a.clamped, s);
+  if (rc != ADMMQ_OK) return rc;
   const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-  const int kout = pl.parallel ? kIgFloat : out;   // the parallel form's epilogue runs in k_packed_ireduce
-#define ADMMQ_IG_LAUNCH(B, T, X)                                                                        \
-  do {                                                                                                  \
+  const int kout = pl.parallel ? kIgFloat : a.out;   // the parallel form's epilogue runs in k_packed_ireduce
+#define ADMMQ_IG_LAUNCH(B, T, X)                                                                                  \
+  do {                                                                                                            \
     if (kout == kIgCodes) hipLaunchKernelGGL((k_packed_igemm<B, T, X, kIgCodes>), grid, dim3(256), 0, s, a);      \
     else if (kout == kIgQuant) hipLaunchKernelGGL((k_packed_igemm<B, T, X, kIgQuant>), grid, dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((k_packed_igemm<B, T, X, kIgFloat>), grid, dim3(256), 0, s, a);             \
+    else hipLaunchKernelGGL((k_packed_igemm<B, T, X, kIgFloat>), grid, dim3(256), 0, s, a);                       \
   } while (0)
-#define ADMMQ_IG_CASE(B)                                     \
-  case B:                                                    \
-    if (trans_w && x_layout) ADMMQ_IG_LAUNCH(B, true, true); \
-    else if (trans_w) ADMMQ_IG_LAUNCH(B, true, false);       \
-    else if (x_layout) ADMMQ_IG_LAUNCH(B, false, true);      \
-    else ADMMQ_IG_LAUNCH(B, false, false);                   \
-    break;
-  switch (meta->bits) {
-    ADMMQ_IG_CASE(1) ADMMQ_IG_CASE(2) ADMMQ_IG_CASE(3) ADMMQ_IG_CASE(4)
-    ADMMQ_IG_CASE(5) ADMMQ_IG_CASE(6) ADMMQ_IG_CASE(7) ADMMQ_IG_CASE(8)
-    default: break;   // (refused above)
-  }
-#undef ADMMQ_IG_CASE
+#define ADMMQ_IG_BITS(B)                                   \
+  if (trans_w && x_layout) ADMMQ_IG_LAUNCH(B, true, true); \
+  else if (trans_w) ADMMQ_IG_LAUNCH(B, true, false);       \
+  else if (x_layout) ADMMQ_IG_LAUNCH(B, false, true);      \
+  else ADMMQ_IG_LAUNCH(B, false, false)
+  PACKED_BITS_SWITCH(meta->bits, ADMMQ_IG_BITS)
+#undef ADMMQ_IG_BITS
 #undef ADMMQ_IG_LAUNCH
-  if (pl.parallel)
-    hipLaunchKernelGGL(k_packed_ireduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
-  return ADMMQ_OK;
+  return ig_finish(a, pl, s);
 }
 
 }  // extern "C"
@@ -655,15 +625,15 @@ __global__ __launch_bounds__(256) void k_packed_taps_i8(const unsigned char* __r
 
 template <int BITS, int OUT>
 __global__ __launch_bounds__(256) void k_packed_idwgemm(const IgDwArgs d) {
-  __shared__ __attribute__((aligned(16))) unsigned char sW[2][kIgBM * kIgLD];
-  __shared__ __attribute__((aligned(16))) unsigned char sX[2][kIgBN * kIgLD];
+  __shared__ __attribute__((aligned(16))) unsigned char sW[2][kPackedBM * kIgLD];
+  __shared__ __attribute__((aligned(16))) unsigned char sX[2][kPackedBN * kIgLD];
   const IgArgs& a = d.g;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1, i = lane & 31, h = lane >> 5;
   const int M = a.M, K = a.K, N = a.N;
   const long long C = a.C;
-  const int m0 = (int)blockIdx.y * kIgBM;
-  const long long c0 = (long long)blockIdx.x * kIgBN;
+  const int m0 = (int)blockIdx.y * kPackedBM;
+  const long long c0 = (long long)blockIdx.x * kPackedBN;
   const int piece = (int)blockIdx.z;
   const int kb = a.parallel ? piece * a.kp : 0;
   const int ke = a.parallel ? min(K, kb + a.kp) : K;
@@ -844,7 +814,7 @@ __global__ __launch_bounds__(256) void k_packed_idwgemm(const IgDwArgs d) {
     const bool hb = a.bias != nullptr;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = m0 + 32 * wm + IG_ROW(r);
+      const int m = m0 + 32 * wm + PACKED_ROW(r);
       if (!ok || m >= M) continue;
       const long long e = ybase + (long long)m * N;
       if (a.parallel) {
@@ -883,7 +853,7 @@ int32_t admmq_packed_taps_i8(const uint8_t* codes, const admmq_qmeta* meta, int3
   if (ntaps <= 0 || K <= 0) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: ntaps and K must be positive");
   if (ntaps > 49) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: ntaps must be at most 49 (a 7 x 7 window)");
   int off = 0;
-  const int32_t rc = igemm_meta_check(meta, "packed_taps_i8", off);
+  const int32_t rc = packed_meta_check(meta, "packed_taps_i8", true, &off);
   if (rc != ADMMQ_OK) return rc;
   if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: K must be at most 65536");
   if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0) return set_error(ADMMQ_ERR_ARG, "packed_taps_i8: codes must be 16-byte aligned");
@@ -899,10 +869,8 @@ int32_t admmq_packed_taps_i8(const uint8_t* codes, const admmq_qmeta* meta, int3
 }
 
 size_t admmq_packed_idwgemm_workspace_size(int64_t M, int64_t K, int64_t Ho, int64_t Wo, int32_t nb) {
-  IgPlan pl;
-  if (Ho <= 0 || Wo <= 0 || Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30)) return 0;
-  if (!plan_packed_igemm(M, K, Ho * Wo, nb, pl)) return 0;
-  return pl.ws;
+  PackedPlan pl;
+  return plan_ig_dw(M, K, Ho, Wo, nb, pl) ? pl.ws : 0;
 }
 
 int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const uint8_t* t_codes,
@@ -911,6 +879,7 @@ int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
                              const int32_t* rowsums, const float* bias, float* y, uint8_t* y_codes,
                              const admmq_actq* mid_q, const admmq_actq* out_q, int32_t* mid_clamped, int32_t* clamped,
                              void* workspace, size_t workspace_bytes, void* stream) {
+  const char* const who = "packed_idwgemm";
   if (!codes || !meta || !t_codes || !t_q || !taps_i8 || !rowsums)
     return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: codes, meta, t_codes, t_q, taps_i8 and rowsums must not be NULL");
   if ((y == nullptr) == (y_codes == nullptr))
@@ -918,7 +887,7 @@ int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
   if (M <= 0 || K <= 0 || H <= 0 || W <= 0 || nb <= 0)
     return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: M, K, H, W and nb must be positive");
   int off = 0;
-  const int32_t rc = igemm_meta_check(meta, "packed_idwgemm", off);
+  int32_t rc = packed_meta_check(meta, who, true, &off);
   if (rc != ADMMQ_OK) return rc;
   if (K > kIgKMax) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: K must be at most 65536 (the int32 sum 128 * 255 * K)");
   if (!act_bits_ok(t_q)) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: t_q must be on with bits 2..8");
@@ -928,48 +897,24 @@ int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
   if (y_codes && !act_bits_ok(out_q))
     return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: a codes output needs out_q on with bits 2..8");
   if (y && oq && (out_q->bits < 1 || out_q->bits > 24)) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: out_q bits must be 1..24");
-  if (kh < 1 || kh > 7 || kw < 1 || kw > 7) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: kernel size must be 1..7 x 1..7");
-  if (sh < 1 || sw < 1) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: stride must be at least 1");
-  if (ph < 0 || ph >= kh || pw < 0 || pw >= kw)
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: padding must be in [0, kernel size)");
-  if (H > (int64_t(1) << 40) || W > (int64_t(1) << 40) || H > (int64_t(1) << 40) / W)
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range");
-  if (H + 2 * ph < kh || W + 2 * pw < kw)
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: the window does not fit the padded image (Ho, Wo >= 1)");
-  const int64_t Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
+  int64_t Ho = 0, Wo = 0;
+  rc = packed_dw_geometry_check(who, H, W, kh, kw, sh, sw, ph, pw, &Ho, &Wo);
+  if (rc != ADMMQ_OK) return rc;
   if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: codes must be 16-byte aligned");
   if ((reinterpret_cast<uintptr_t>(taps_i8) & 15) != 0)
     return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: taps_i8 must be 16-byte aligned");
   if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(rowsums) |
         reinterpret_cast<uintptr_t>(clamped) | reinterpret_cast<uintptr_t>(mid_clamped)) & 3) != 0)
     return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: y, bias, rowsums, mid_clamped and clamped must be 4-byte aligned");
-  IgPlan pl;
-  if (Ho > (int64_t(1) << 30) || Wo > (int64_t(1) << 30) || !plan_packed_igemm(M, K, Ho * Wo, nb, pl))
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range");
-  const int64_t tmax = (int64_t(1) << 40) - 1;   // nb K H W <= tmax, without overflow
-  if (K > tmax / (H * W) || nb > tmax / (H * W * K))
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range (nb K H W must be below 2^40)");
-  if (pl.ws > 0 && (!workspace || workspace_bytes < pl.ws)) return set_error(ADMMQ_ERR_WORKSPACE, "workspace too small");
-  if (pl.ws > 0 && (reinterpret_cast<uintptr_t>(workspace) & 3) != 0)
-    return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: workspace must be int32 aligned");
+  PackedPlan pl;
+  if (!plan_ig_dw(M, K, Ho, Wo, nb, pl)) return set_error(ADMMQ_ERR_ARG, "packed_idwgemm: sizes out of range");
+  rc = packed_dw_extent_check(who, nb, K, H, W);
+  if (rc != ADMMQ_OK) return rc;
+  rc = packed_ws_check(who, pl, workspace, workspace_bytes, "int32");
+  if (rc != ADMMQ_OK) return rc;
   IgDwArgs d;
-  IgArgs& a = d.g;
-  a.codes = codes; a.x = t_codes; a.bias = bias; a.rowsum = rowsums; a.y = y; a.yc = y_codes;
-  a.part = pl.parallel ? static_cast<int*>(workspace) : nullptr;
-  a.clamped = y_codes ? clamped : nullptr;
-  a.nbytes = (long long)admmq_packed_bytes(M * K, meta->bits);
-  a.total = pl.total; a.C = pl.C;
-  a.M = (int)M; a.K = (int)K; a.N = (int)(Ho * Wo);
-  a.xl = 0;
-  a.kp = pl.kp; a.np = pl.np; a.parallel = pl.parallel;
-  a.off = off;
-  a.xal = 0;
-  const int out = y_codes ? kIgCodes : (oq ? kIgQuant : kIgFloat);
-  a.out = out;
-  a.s = (double)meta->scale;
-  a.g = (double)mid_q->rng / (double)((1 << mid_q->bits) - 1);
-  a.mnx = (double)mid_q->mn;
-  a.oq = oq ? actq_make(out_q) : ActQ{0.f, 0.f, 0.f, 0};
+  IgArgs& a = d.g;   // (the GEMM's activation operand is Z: the mid quantizer's codes)
+  ig_fill(a, codes, meta, off, t_codes, mid_q, rowsums, bias, y, y_codes, out_q, clamped, workspace, pl, M, K, Ho * Wo, 0);
   d.taps = reinterpret_cast<const signed char*>(taps_i8);
   d.midc = mid_clamped;
   d.H = H; d.W = W; d.HW = H * W; d.Kp = taps_kp(K);
@@ -980,33 +925,19 @@ int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
   d.mnt = (double)t_q->mn;
   d.mq = actq_make(mid_q);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mid_clamped) {
-    const hipError_t e = hipMemsetAsync(mid_clamped, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
-  }
-  if (a.clamped) {
-    const hipError_t e = hipMemsetAsync(a.clamped, 0, sizeof(int32_t), s);
-    if (e != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(e));
-  }
+  rc = counter_reset(mid_clamped, s);
+  if (rc != ADMMQ_OK) return rc;
+  rc = counter_reset(a.clamped, s);
+  if (rc != ADMMQ_OK) return rc;
   const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
-  const int kout = pl.parallel ? kIgFloat : out;   // the parallel form's epilogue runs in k_packed_ireduce
-#define ADMMQ_IDW_CASE(B)                                                                                   \
-  case B:                                                                                                   \
-    if (kout == kIgCodes) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgCodes>), grid, dim3(256), 0, s, d);      \
-    else if (kout == kIgQuant) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgQuant>), grid, dim3(256), 0, s, d); \
-    else hipLaunchKernelGGL((k_packed_idwgemm<B, kIgFloat>), grid, dim3(256), 0, s, d);                     \
-    break;
-  switch (meta->bits) {
-    ADMMQ_IDW_CASE(1) ADMMQ_IDW_CASE(2) ADMMQ_IDW_CASE(3) ADMMQ_IDW_CASE(4)
-    ADMMQ_IDW_CASE(5) ADMMQ_IDW_CASE(6) ADMMQ_IDW_CASE(7) ADMMQ_IDW_CASE(8)
-    default: break;   // (refused above)
-  }
-#undef ADMMQ_IDW_CASE
-  if (pl.parallel)
-    hipLaunchKernelGGL(k_packed_ireduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
-  return ADMMQ_OK;
+  const int kout = pl.parallel ? kIgFloat : a.out;   // the parallel form's epilogue runs in k_packed_ireduce
+#define ADMMQ_IDW_BITS(B)                                                                                   \
+  if (kout == kIgCodes) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgCodes>), grid, dim3(256), 0, s, d);      \
+  else if (kout == kIgQuant) hipLaunchKernelGGL((k_packed_idwgemm<B, kIgQuant>), grid, dim3(256), 0, s, d); \
+  else hipLaunchKernelGGL((k_packed_idwgemm<B, kIgFloat>), grid, dim3(256), 0, s, d)
+  PACKED_BITS_SWITCH(meta->bits, ADMMQ_IDW_BITS)
+#undef ADMMQ_IDW_BITS
+  return ig_finish(a, pl, s);
 }
 
 }  // extern "C"

@@ -572,7 +572,30 @@ std::tuple<at::Tensor, at::Tensor> packed_igemm_meta(const at::Tensor& codes, co
 // packed_idwgemm: admmq_packed_idwgemm on the codes x [nb, K, H, W] -> [nb, M, Ho, Wo] (float or
 // codes). Both counters are int32 [1] device tensors (clamped is empty without a codes output,
 // mid_clamped without count_mid: a counter that is not asked for costs no memset).
-int64_t taps_kp(int64_t K) { return 64 * ((K + 63) / 64); }
+// Kp of the image [ntaps, Kp]: K rounded up to the integer GEMM's K step, which is the library's
+// image size for one tap and K = 1 (so an out-of-range K still gets its rounded-up figure in a message)
+int64_t taps_kp(int64_t K) {
+  const int64_t step = static_cast<int64_t>(admmq_packed_taps_i8_bytes(1, 1));
+  return step * ((K + step - 1) / step);
+}
+
+// The output shape [n, M, Ho, Wo] of a fused depthwise + 1x1 op `who` on x [n, K, H, W]; its
+// depthwise factor `taps_name` must be [kh kw, taps_cols].
+std::vector<int64_t> packed_dw_shape(const char* who, const char* taps_name, int64_t taps_cols, const at::Tensor& x,
+                                     const at::Tensor& taps, int64_t M, int64_t K, int64_t kh, int64_t kw, int64_t sh,
+                                     int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(M > 0 && K > 0, "admmq: ", who, ": M and K must be positive");
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == K, "admmq: ", who, ": x must be [n, ", K, ", H, W], got ", x.sizes());
+  TORCH_CHECK(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "admmq: ", who, ": kernel size must be 1..7 x 1..7");
+  TORCH_CHECK(sh >= 1 && sw >= 1, "admmq: ", who, ": stride must be at least 1");
+  TORCH_CHECK(ph >= 0 && ph < kh && pw >= 0 && pw < kw, "admmq: ", who, ": padding must be in [0, kernel size)");
+  TORCH_CHECK(taps.dim() == 2 && taps.size(0) == kh * kw && taps.size(1) == taps_cols, "admmq: ", who, ": ", taps_name,
+              " must be [", kh * kw, ", ", taps_cols, "], got ", taps.sizes());
+  const int64_t H = x.size(2), W = x.size(3);
+  TORCH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "admmq: ", who, ": the ", kh, " x ", kw,
+              " window does not fit the padded image of x ", x.sizes());
+  return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
+}
 
 at::Tensor packed_taps_i8_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t ntaps, int64_t K) {
   TORCH_CHECK(ntaps >= 1 && ntaps <= 49, "admmq: packed_taps_i8: ntaps must be 1..49, got ", ntaps);
@@ -594,17 +617,7 @@ at::Tensor packed_taps_i8_meta(const at::Tensor& codes, const at::Tensor& meta_w
 
 std::vector<int64_t> packed_idwgemm_shape(const at::Tensor& x, const at::Tensor& taps, int64_t M, int64_t K, int64_t kh,
                                           int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
-  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_idwgemm: M and K must be positive");
-  TORCH_CHECK(x.dim() == 4 && x.size(1) == K, "admmq: packed_idwgemm: x must be [n, ", K, ", H, W], got ", x.sizes());
-  TORCH_CHECK(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "admmq: packed_idwgemm: kernel size must be 1..7 x 1..7");
-  TORCH_CHECK(sh >= 1 && sw >= 1, "admmq: packed_idwgemm: stride must be at least 1");
-  TORCH_CHECK(ph >= 0 && ph < kh && pw >= 0 && pw < kw, "admmq: packed_idwgemm: padding must be in [0, kernel size)");
-  TORCH_CHECK(taps.dim() == 2 && taps.size(0) == kh * kw && taps.size(1) == taps_kp(K),
-              "admmq: packed_idwgemm: taps_i8 must be [", kh * kw, ", ", taps_kp(K), "], got ", taps.sizes());
-  const int64_t H = x.size(2), W = x.size(3);
-  TORCH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "admmq: packed_idwgemm: the ", kh, " x ", kw,
-              " window does not fit the padded image of x ", x.sizes());
-  return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
+  return packed_dw_shape("packed_idwgemm", "taps_i8", taps_kp(K), x, taps, M, K, kh, kw, sh, sw, ph, pw);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_cuda(
@@ -687,17 +700,7 @@ at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_word
 // in one kernel (admmq_packed_dwgemm): x [nb, K, H, W] -> [nb, M, Ho, Wo]. Inference only.
 std::vector<int64_t> packed_dwgemm_shape(const at::Tensor& x, const at::Tensor& taps, int64_t M, int64_t K, int64_t kh,
                                          int64_t kw, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
-  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_dwgemm: M and K must be positive");
-  TORCH_CHECK(x.dim() == 4 && x.size(1) == K, "admmq: packed_dwgemm: x must be [n, ", K, ", H, W], got ", x.sizes());
-  TORCH_CHECK(kh >= 1 && kh <= 7 && kw >= 1 && kw <= 7, "admmq: packed_dwgemm: kernel size must be 1..7 x 1..7");
-  TORCH_CHECK(sh >= 1 && sw >= 1, "admmq: packed_dwgemm: stride must be at least 1");
-  TORCH_CHECK(ph >= 0 && ph < kh && pw >= 0 && pw < kw, "admmq: packed_dwgemm: padding must be in [0, kernel size)");
-  TORCH_CHECK(taps.dim() == 2 && taps.size(0) == kh * kw && taps.size(1) == K, "admmq: packed_dwgemm: taps must be [",
-              kh * kw, ", ", K, "], got ", taps.sizes());
-  const int64_t H = x.size(2), W = x.size(3);
-  TORCH_CHECK(H + 2 * ph >= kh && W + 2 * pw >= kw, "admmq: packed_dwgemm: the ", kh, " x ", kw,
-              " window does not fit the padded image of x ", x.sizes());
-  return {x.size(0), M, (H + 2 * ph - kh) / sh + 1, (W + 2 * pw - kw) / sw + 1};
+  return packed_dw_shape("packed_dwgemm", "taps", K, x, taps, M, K, kh, kw, sh, sw, ph, pw);
 }
 
 at::Tensor packed_dwgemm_impl(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,

@@ -78,6 +78,49 @@ def test_workspace_size_is_a_function_of_its_arguments(lib):
         assert b % (s[0] * s[2] * s[3] * 4) == 0
 
 
+def _ws_formula(M, K, N, nb, integer):
+    """The documented plan, written out: K pieces of kp = max(64, BK ceil(K / (32 BK))) (BK = 32 float, 64 integer);
+    the pieces run in parallel, one 4-byte partial image of C M elements each, when there is more than one piece
+    and fewer than 256 tiles of 64 x 64; sizes out of range give 0."""
+    if min(M, K, N, nb) <= 0 or M > 1 << 22 or N > 1 << 30 or nb > 1 << 30 or nb * N > 1 << 30:
+        return 0
+    if K > (65536 if integer else 1 << 24) or (not integer and M * K >= 1 << 40):
+        return 0
+    bk = 64 if integer else 32
+    kp = max(64, bk * -(-K // (32 * bk)))
+    pieces = -(-K // kp)
+    tiles = -(-M // 64) * -(-(nb * N) // 64)
+    return pieces * (nb * N * M) * 4 if pieces > 1 and tiles < 256 else 0
+
+
+def test_workspace_sizes_match_the_closed_formula(lib):
+    ks = [1, 63, 64, 65, 2048, 2049, 65536, 65537]
+    # (M, N, nb): one tile; partial tiles; 255 and 256 tiles along m and along c; as a product 15 x 17 = 255,
+    # 15 x 18, 16 x 16 = 256 and 5 x 51 = 255; a batch
+    mnb = [(8, 4, 1), (65, 129, 1), (64 * 255, 64, 1), (64 * 255 + 1, 64, 1), (64, 64 * 255, 1), (64, 64 * 255 + 1, 1),
+           (960, 1088, 1), (960, 1089, 1), (1024, 1024, 1), (320, 3264, 1), (134, 65, 3), (512, 7, 2)]
+    grid = [(M, K, N, nb) for K in ks for (M, N, nb) in mnb]
+    # just inside and just beyond each limit
+    grid += [(1 << 22, 65, 1, 1), ((1 << 22) + 1, 65, 1, 1), (8, 1 << 24, 4, 1), (8, (1 << 24) + 1, 4, 1),
+             (8, 128, 1 << 30, 1), (8, 128, (1 << 30) + 1, 1), (8, 128, 1, 1 << 30), (8, 128, 1, (1 << 30) + 1),
+             (8, 128, 1 << 20, 1 << 10), (8, 128, 1 << 20, (1 << 10) + 1), (1 << 22, (1 << 18) - 1, 1, 1),
+             (1 << 22, 1 << 18, 1, 1), (0, 8, 8, 1), (8, 0, 8, 1), (8, 8, 0, 1), (8, 8, 8, 0), (8, 8, -1, 1)]
+    for M, K, N, nb in grid:
+        assert lib.admmq_packed_gemm_workspace_size(M, K, N, nb) == _ws_formula(M, K, N, nb, False), (M, K, N, nb)
+        assert lib.admmq_packed_igemm_workspace_size(M, K, N, nb) == _ws_formula(M, K, N, nb, True), (M, K, N, nb)
+        # the depthwise entry points: N = Ho Wo, in both factorisations
+        for Ho, Wo in ((N, 1), (1, N)) + (((N // 17, 17),) if N % 17 == 0 else ()):
+            for f, integer in ((lib.admmq_packed_dwgemm_workspace_size, False), (lib.admmq_packed_idwgemm_workspace_size, True)):
+                assert f(M, K, Ho, Wo, nb) == _ws_formula(M, K, Ho * Wo, nb, integer), (M, K, Ho, Wo, nb, integer)
+    # Ho and Wo each at most 2^30 and positive, and their product within N's limit
+    for Ho, Wo in [((1 << 30) + 1, 1), (1, (1 << 30) + 1), (1 << 16, 1 << 15), (0, 4), (4, -1)]:
+        assert lib.admmq_packed_dwgemm_workspace_size(512, 1141, Ho, Wo, 1) == 0
+        assert lib.admmq_packed_idwgemm_workspace_size(512, 1141, Ho, Wo, 1) == 0
+    # the parallel regime is in the grid: (8, 65, 4, 1) has two pieces and one tile
+    assert lib.admmq_packed_gemm_workspace_size(8, 65, 4, 1) == 2 * 4 * 8 * 4
+    assert lib.admmq_packed_idwgemm_workspace_size(64 * 255, 65, 8, 8, 1) == 2 * 64 * (64 * 255) * 4
+
+
 def test_meta_kernel_gives_the_shapes():
     from admmq import _lib
     ops = _lib.ops()
