@@ -295,18 +295,21 @@ int copy_sel_stats(unsigned long long* host, int reset);
 long long copy_shared_stage2(int reset);
 int check_thresholds(unsigned seed, int nsamp);
 int check_cells(int n, int bits, unsigned seed, int nsamp, unsigned* maxdev_out);
+// merged-threshold stage 1: whether (ncand, bits) has one (1..5 bits, the kernels' QMAX
+// instantiations; table size and LDS). The launchers return ADMMQ_OK, or refuse any other
+// width with ADMMQ_ERR_ARG (set_error) and launch nothing.
 bool merged_ok(int ncand, int bits);
-void launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int nchunks, int ncand, int bits, int slot,
-                      const unsigned short* rank0, const unsigned short* groups, int ngroups, int nv, bool fin, int iter,
-                      unsigned wait_polls, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+int launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int nchunks, int ncand, int bits, int slot,
+                     const unsigned short* rank0, const unsigned short* groups, int ngroups, int nv, bool fin, int iter,
+                     unsigned wait_polls, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // fused finalize: polls (s_sleep 2 each, ~10 ms in all) before a block gives up waiting for
 // its job's selection and reports an internal fault instead of finalizing
 constexpr unsigned kFinWaitPollsDefault = 1u << 17;
 int hist3_fin_capacity(int ncand, int bits, int nv);
 int small_admm_groups(long long maxtotal);
-void launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ngr, int ncand, int bits, int slot,
-                           int iter, const unsigned short* rank0, const unsigned short* groups, int ngroups,
-                           hipStream_t s);
+int launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ngr, int ncand, int bits, int slot,
+                          int iter, const unsigned short* rank0, const unsigned short* groups, int ngroups,
+                          hipStream_t s);
 void launch_mse_select_all(const ProbDesc* d, const QJob* q, int njobs, int ncand, int slot, hipStream_t s);
 void launch_mse_sse(const ProbDesc* d, const QJob* q, const Chunk* chunks, int nchunks, int ncand, int bits,
                     int slot, hipStream_t s);

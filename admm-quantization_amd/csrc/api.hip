@@ -400,8 +400,9 @@ static int run_quant(QPlan& pl, int n, int bits, int qscheme, int ncand, hipStre
     const SearchForm sf = search_form(ncand, bits, qscheme, sw.exhaustive, sw.legacy_stage1);
     if ((rc = upload_search_tables(sf, pl.d_rank0, pl.d_groups, s))) return rc;
     if (sf.merged) {
-      launch_mse_hist3(nullptr, pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), ncand, bits, 0, pl.d_rank0,
-                       pl.d_groups, sf.ngroups, 1, false, 0, 0u, s);
+      if ((rc = launch_mse_hist3(nullptr, pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), ncand, bits, 0, pl.d_rank0,
+                                 pl.d_groups, sf.ngroups, 1, false, 0, 0u, s)))
+        return rc;
     } else if (!sf.exhaustive) {
       launch_mse_hist(nullptr, pl.d_jobs, pl.d_hist, (int)pl.hist_chunks.size(), ncand, bits, 0, 1, s);
     } else {   // exhaustive: every candidate's canonical SSE over all chunks
@@ -743,10 +744,12 @@ struct RunArgs {
 };
 
 // One iteration's launches as the schedule lists them, one event pair per launch (classes:
-// include/admmq.h, admmq_profile_end)
-static void run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const SearchForm& sf, const RunArgs& a, int it,
-                          hipStream_t s) {
+// include/admmq.h, admmq_profile_end). ADMMQ_OK, or a search launcher's refusal (nothing
+// more is launched).
+static int run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const SearchForm& sf, const RunArgs& a, int it,
+                         hipStream_t s) {
   const int slot = it & 1;
+  int rc;
   if (rs.gemm) {
     hipEvent_t g0 = nullptr, g1 = nullptr;
     // the diagnostic fp32 kernels: event packets
@@ -768,8 +771,10 @@ static void run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const Searc
   if (rs.search == kSearchHist3 || rs.search == kSearchHist3Fin) {
     hipEvent_t h0, h1;
     prof_pair(ADMMQ_PROF_SEARCH, &h0, &h1);
-    launch_mse_hist3(pl.d_desc, nullptr, rs.search_multi ? pl.d_hist_multi : pl.d_hist, rs.nh, a.ncand, a.bits, slot,
-                     pl.d_rank0, pl.d_groups, sf.ngroups, pl.hist_nv, rs.search == kSearchHist3Fin, it, a.polls, s, h0, h1);
+    if ((rc = launch_mse_hist3(pl.d_desc, nullptr, rs.search_multi ? pl.d_hist_multi : pl.d_hist, rs.nh, a.ncand, a.bits,
+                               slot, pl.d_rank0, pl.d_groups, sf.ngroups, pl.hist_nv, rs.search == kSearchHist3Fin, it,
+                               a.polls, s, h0, h1)))
+      return rc;
   } else if (rs.search != kSearchNone) {
     prof_class(ADMMQ_PROF_SEARCH); prof_mark(s);
     if (rs.search == kSearchHist) {
@@ -782,8 +787,9 @@ static void run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const Searc
   }
   if (rs.fuse_small) {
     prof_class(ADMMQ_PROF_SMALL); prof_mark(s);
-    launch_mse_small_admm(pl.d_desc, pl.d_small, (int)pl.small.size(), pl.small_groups, a.ncand, a.bits, slot, it,
-                          pl.d_rank0, pl.d_groups, sf.ngroups, s);
+    if ((rc = launch_mse_small_admm(pl.d_desc, pl.d_small, (int)pl.small.size(), pl.small_groups, a.ncand, a.bits, slot,
+                                    it, pl.d_rank0, pl.d_groups, sf.ngroups, s)))
+      return rc;
     prof_mark(s);
   }
   if (rs.nf > 0) {
@@ -791,6 +797,7 @@ static void run_iteration(const AdmmPlan& pl, const RunSchedule& rs, const Searc
     launch_finalize_admm(pl.d_desc, pl.d_fin, rs.nf, pl.fin_groups, a.ncand, a.bits, a.qscheme, slot, it, s);
     prof_mark(s);
   }
+  return ADMMQ_OK;
 }
 
 int32_t admmq_admm_run_ex(const admmq_problem* probs, int32_t nprob, int32_t max_iter, float eps, int32_t bits,
@@ -844,7 +851,7 @@ int32_t admmq_admm_run_ex(const admmq_problem* probs, int32_t nprob, int32_t max
   }
   for (int it = 0; !loop_done && it < rs.iters; ++it) {
     g_prof.sampled = it % g_prof.every == 0;
-    run_iteration(pl, rs, sf, a, it, s);
+    if ((rc = run_iteration(pl, rs, sf, a, it, s))) return rc;
   }
   g_prof.sampled = true;
   if (max_iter > 1) launch_unpack(pl.d_desc, nprob, pl.maxI, pl.maxR, s);

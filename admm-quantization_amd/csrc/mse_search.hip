@@ -16,10 +16,12 @@
 //                       kernel exits at once); exhaustive when |S| > kMaxSel or forced.
 #include <algorithm>
 #include <mutex>
+#include <cstdio>
 #include <cstdlib>
 
 #include <hip/hip_ext.h>
 
+#include "../../include/admmq.h"
 #include "quant_device.h"
 #include "search_device.h"
 
@@ -1470,16 +1472,27 @@ __global__ __launch_bounds__(kSmallThreads) void k_mse_small_admm(const ProbDesc
   ADMMQ_SMALL_STAMP(7);
 }
 
+// The merged-threshold kernels (k_mse_hist3, k_mse_small_admm) read rank0 / groups as tables
+// of QMAX * ncand thresholds with QMAX = 2^(bits-1) a template argument, instantiated for
+// 1..5 bits: merged_ok admits no other width, and a launcher asked for one refuses (a kernel
+// of another QMAX would score another quantizer in stage 1, its selection no longer exact).
+static bool merged_width(int bits) { return bits >= 1 && bits <= 5; }
+static int merged_refused(const char* kernel) {
+  static thread_local char msg[96];
+  snprintf(msg, sizeof msg, "%s: no merged-threshold stage 1 for this bit width", kernel);
+  return set_error(ADMMQ_ERR_ARG, msg);
+}
+
 // maxtotal: the largest I * ld among the jobs (picks G); 0 when the path cannot run
 int small_admm_groups(long long maxtotal) {
   const long long g = (maxtotal + 4095) / 4096;
   return g <= 1 ? 1 : (g <= 2 ? 2 : (g <= 3 ? 3 : (g <= 4 ? 4 : (g <= 6 ? 6 : 0))));
 }
 
-void launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ngr, int ncand, int bits, int slot,
-                           int iter, const unsigned short* rank0, const unsigned short* groups, int ngroups,
-                           hipStream_t s) {
-  if (njobs <= 0) return;
+int launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ngr, int ncand, int bits, int slot,
+                          int iter, const unsigned short* rank0, const unsigned short* groups, int ngroups,
+                          hipStream_t s) {
+  if (njobs <= 0) return ADMMQ_OK;
   const size_t lds = hist3_lds_bytes(ncand, bits);
 #define ADMMQ_SMG(Q, GG) \
   hipLaunchKernelGGL((k_mse_small_admm<Q, GG>), dim3(njobs), dim3(kSmallThreads), lds, s, d, jobs, ncand, bits, slot, iter, \
@@ -1497,10 +1510,12 @@ void launch_mse_small_admm(const ProbDesc* d, const int* jobs, int njobs, int ng
     case 2: ADMMQ_SM(2); break;
     case 3: ADMMQ_SM(4); break;
     case 4: ADMMQ_SM(8); break;
-    default: ADMMQ_SM(16); break;
+    case 5: ADMMQ_SM(16); break;
+    default: return merged_refused("k_mse_small_admm");
   }
 #undef ADMMQ_SM
 #undef ADMMQ_SMG
+  return ADMMQ_OK;
 }
 
 size_t hist3_lds_bytes(int ncand, int bits) {
@@ -1606,12 +1621,13 @@ void launch_mse_hist(const ProbDesc* d, const QJob* q, const Chunk* chunks, int 
 #undef ADMMQ_H1
 }
 bool merged_ok(int ncand, int bits) {
-  return ncand >= 2 && ((size_t)ncand << (bits - 1)) <= (size_t)kMaxMerged && hist3_lds_bytes(ncand, bits) <= 150 * 1024;
+  return merged_width(bits) && ncand >= 2 && ((size_t)ncand << (bits - 1)) <= (size_t)kMaxMerged &&
+         hist3_lds_bytes(ncand, bits) <= 150 * 1024;
 }
-void launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int nchunks, int ncand, int bits, int slot,
-                      const unsigned short* rank0, const unsigned short* groups, int ngroups, int nv, bool fin, int iter,
-                      unsigned wait_polls, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  if (nchunks <= 0) return;
+int launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int nchunks, int ncand, int bits, int slot,
+                     const unsigned short* rank0, const unsigned short* groups, int ngroups, int nv, bool fin, int iter,
+                     unsigned wait_polls, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  if (nchunks <= 0) return ADMMQ_OK;
   const size_t lds = fin ? hist3_fin_lds_bytes(ncand, bits, nv) : hist3_lds_bytes(ncand, bits);
   // ev0 / ev1 (profiling, may be null): recorded by the dispatch itself at the kernel's start / end
 #define ADMMQ_H3(Q, V, F)                                                                                         \
@@ -1632,10 +1648,12 @@ void launch_mse_hist3(const ProbDesc* d, const QJob* q, const Chunk* chunks, int
     case 2: ADMMQ_H3N(2); break;
     case 3: ADMMQ_H3N(4); break;
     case 4: ADMMQ_H3N(8); break;
-    default: ADMMQ_H3N(16); break;
+    case 5: ADMMQ_H3N(16); break;
+    default: return merged_refused("k_mse_hist3");
   }
 #undef ADMMQ_H3N
 #undef ADMMQ_H3
+  return ADMMQ_OK;
 }
 
 // Resident blocks of the fused (FIN) search kernel on the CURRENT device (all of a
@@ -1668,7 +1686,8 @@ int hist3_fin_capacity(int ncand, int bits, int nv) {
     case 2: ADMMQ_OCC(2); break;
     case 3: ADMMQ_OCC(4); break;
     case 4: ADMMQ_OCC(8); break;
-    default: ADMMQ_OCC(16); break;
+    case 5: ADMMQ_OCC(16); break;
+    default: return 0;   // no such kernel: nothing is resident
   }
 #undef ADMMQ_OCC
   return e == hipSuccess ? per * cus[dev] : 0;

@@ -1,6 +1,8 @@
 // Device helpers of the two-stage MSE search shared by mse_search.hip (the per-launch
 // search kernels) and thin_loop.hip (the persistent loop of the thin factors).
 #pragma once
+#include <type_traits>
+
 #include "quant_device.h"
 
 namespace admmq {
@@ -97,7 +99,11 @@ __device__ __forceinline__ void hist_insert_elem(float x, const float* thr, int 
   const unsigned long long af = to_fixed(a, K1);
   full1 += af * (unsigned long long)kfull;
   full2 += (unsigned)(kfull * kfull);              // sum_{k<=kfull} (2k-1)
-  unsigned slow = 0u;
+  // bit k: level k takes the slow path (k = 1..QMAX, so QMAX = 32 needs bit 32: a 32-bit mask
+  // dropped that level's sums whenever its estimate missed)
+  typedef typename std::conditional<(QMAX < 32), unsigned, unsigned long long>::type slow_t;
+  static_assert(QMAX <= 32, "the slow-path mask holds bits 1..QMAX");
+  slow_t slow = 0;
   if constexpr (QMAX <= 8) {
     // every level's estimate and its two neighbouring thresholds first, so the 2 QMAX LDS
     // reads are in flight together (read at their compare, each was waited for on its
@@ -120,7 +126,7 @@ __device__ __forceinline__ void hist_insert_elem(float x, const float* thr, int 
     for (int k = 1; k <= QMAX; ++k) {
       const bool act = (k > kfull && k <= k0);
       const bool exact = (a >= tlo[k - 1]) && (a < thi[k - 1]);
-      slow |= (act && !exact) ? (1u << k) : 0u;
+      slow |= (act && !exact) ? (slow_t(1) << k) : slow_t(0);
       // only the lanes whose level k is active add (1-2 of the QMAX levels of an
       // element): the masked-off lanes cost no LDS atomic
       if (act && exact) {
@@ -138,7 +144,7 @@ __device__ __forceinline__ void hist_insert_elem(float x, const float* thr, int 
       b = max(min(b, n - 1), 1);
       const float* tk = thr + (k - 1) * n;
       const bool exact = (a >= tk[b - 1]) && (a < tk[b]);
-      slow |= (act && !exact) ? (1u << k) : 0u;
+      slow |= (act && !exact) ? (slow_t(1) << k) : slow_t(0);
       if (act && exact) {
         atomicAdd(&h1[b], af);
         atomicAdd(&h2[b], (unsigned)(2 * k - 1));
@@ -149,7 +155,7 @@ __device__ __forceinline__ void hist_insert_elem(float x, const float* thr, int 
   if (slow) {   // rare: exact breakpoint by binary search (largest b with thr[k][b-1] <= a)
 #pragma unroll 1
     for (int k = 1; k <= QMAX; ++k) {
-      if (!((slow >> k) & 1u)) continue;
+      if (!((slow >> k) & slow_t(1))) continue;
       const float* tk = thr + (k - 1) * n;
       int lo = 1, hi = n - 1;   // a >= tk[0] and a < tk[n-1]: answer in [1, n-1]
       while (lo < hi) {

@@ -888,7 +888,8 @@ int launch_thin_loop(const ProbDesc* d, const ThinLoopUnit* units, int nunits, T
     case 2: return run(k_thin_loop<NRV, 2, W>);     \
     case 3: return run(k_thin_loop<NRV, 4, W>);     \
     case 4: return run(k_thin_loop<NRV, 8, W>);     \
-    default: return run(k_thin_loop<NRV, 16, W>);   \
+    case 5: return run(k_thin_loop<NRV, 16, W>);    \
+    default: return -1;                             \
   }
 #define ADMMQ_TLW(W)             \
   if (NRv == 9) { ADMMQ_TL(9, W) } \

@@ -7,6 +7,8 @@ for the rest).
 from __future__ import annotations
 
 import hashlib
+import json
+import os
 
 import numpy as np
 
@@ -175,3 +177,46 @@ def f9_input(case) -> np.ndarray:
         x[1, 7] = np.inf
         x[4, 2] = -np.inf
     return x.astype(np.float32)
+
+
+# F13: the MSE-minmax search at every (bits, num_attempts) cell that fixes the device's
+# search form (csrc/admm_plan.hip: search_form): 1 candidate and a tie group above 4
+# (196, 201: n = 1 mod 5) take the per-level stage 1, 1100 exceeds the two-stage search,
+# 7 and 8 bits are exhaustive, 6 bits is per-level at every count. SHA-256 digests only.
+F13_BITS = [1, 2, 3, 5, 6, 7, 8]
+F13_ATTEMPTS = [1, 2, 50, 64, 128, 196, 200, 1100]
+F13_EXTRA = [(4, 196), (4, 201)]
+F13_INPUTS = [("tall", (40, 134)), ("thin", (9, 134)), ("outlier", (40, 134))]
+
+
+def f13_grid():
+    """The (bits, num_attempts) pairs of F13, in case order."""
+    return [(b, n) for b in F13_BITS for n in F13_ATTEMPTS] + list(F13_EXTRA)
+
+
+def f13_cases():
+    cases = []
+    for k, (kind, shape) in enumerate(F13_INPUTS):
+        for bits, na in f13_grid():
+            cases.append(dict(id=f"m_{kind}_b{bits}_n{na}", kind=kind, shape=list(shape), seed=13000 + k, scale=0.3,
+                              bits=bits, num_attempts=na))
+    return cases
+
+
+def f13_input(case) -> np.ndarray:
+    """Standard normal times the scale; "outlier": one element at 30 standard deviations
+    (about 8 times the largest of the rest, so the clipping candidates trade it against
+    them at every width). An outlier so large that every other element rounds to zero is
+    no KAT: the candidates' MSEs then differ by less than the float32 rounding of the
+    reference's own mean, which ties them, while the oracle's exact sums do not."""
+    rng = np.random.default_rng(case["seed"])
+    x = rng.standard_normal(tuple(case["shape"])) * case["scale"]
+    if case["kind"] == "outlier":
+        x.flat[1234] = -30.0 * case["scale"]
+    return x.astype(np.float32)
+
+
+def f13_reference():
+    """The cases of f13_forms.json: f13_cases() with the reference's SHA-256 and candidate."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "f13_forms.json")) as f:
+        return json.load(f)["cases"]

@@ -122,6 +122,24 @@ def test_f9_channel_kats():
         assert np.array_equal(np.isnan(y), np.isnan(ref)) and np.array_equal(y[~np.isnan(y)], ref[~np.isnan(ref)])
 
 
+def test_f13_search_form_matrix_kats():
+    """MSE-minmax over the (bits, num_attempts) matrix that fixes the device's search form
+    (bits 1..8; 1, 2, 50, 64, 128, 196, 200, 201 and 1100 candidates; a tall, a thin and an
+    outlier input): the fixture holds the cases of golden_cases.f13_cases() and the oracle
+    reproduces every reference output bit for bit, so it is a pinned reference at every
+    cell the GPU tests of the matrix compare the kernels with."""
+    meta = gc.f13_reference()
+    want = gc.f13_cases()
+    assert len(meta) == len(want) == 3 * (7 * 8 + 2)
+    mism = []
+    for case, w in zip(meta, want):
+        assert {k: case[k] for k in w} == w, case["id"]
+        y, info = qo.quantize_tensor_mse(gc.f13_input(case), case["bits"], case["num_attempts"], return_info=True)
+        if _sha(y) != case["sha"]:
+            mism.append((case["id"], f"reference candidate {case['index']}, oracle {info['index']}"))
+    assert mism == [], f"{len(mism)} of {len(meta)} KATs differ: {mism[:20]}"
+
+
 def test_f10_lowrank_fixture_consistent():
     """F10 (reference quant + low-rank loop, 30 outer iterations, five runs): the band holds
     the reference's own history, its runs agree to 1e-3 for 4 outer iterations, and every
