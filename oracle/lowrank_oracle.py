@@ -19,8 +19,27 @@ def project_rank(H: np.ndarray, rank: int) -> np.ndarray:
     return ((U[:, :rank] * S[:rank]) @ Vt[:rank]).astype(F32)
 
 
-def admm_iteration(H, U, W, H2, proj_func, rho=1.0, max_iter=50, eps=1e-8):
-    """Returns (H, U, iterations run). U is a new array (the reference mutates in place)."""
+def proj_quarter(X: np.ndarray) -> np.ndarray:
+    """round(4 X) / 4 in float32: a projection whose torch twin (``torch.round(X * 4) / 4``)
+    is bit-identical (both round half to even, both scalings are exact), so the oracle is
+    a bit-exact reference of the two stream kernels alone, the quantizer left out."""
+    return (np.rint(np.asarray(X, F32) * F32(4.0)) / F32(4.0)).astype(F32)
+
+
+def break_case(shape, seed=5):
+    """(W, H2, H0) of the break-at-iteration-k tests (W ~ N(0,1), H2 ~ 0.1 N(0,1),
+    H0 ~ N(0,1), drawn in that order from ``default_rng(seed)``); run with U = 0,
+    rho = 1, eps = 0.02, max_iter = 40 and ``proj_quarter``."""
+    g = np.random.default_rng(seed)
+    W = g.standard_normal(shape).astype(F32)
+    H2 = (0.1 * g.standard_normal(shape)).astype(F32)
+    H0 = g.standard_normal(shape).astype(F32)
+    return W, H2, H0
+
+
+def admm_iteration(H, U, W, H2, proj_func, rho=1.0, max_iter=50, eps=1e-8, history=None):
+    """Returns (H, U, iterations run). U is a new array (the reference mutates in place).
+    ``history``: an optional list that receives every iteration's ``(r, s)``."""
     H = np.asarray(H, F32).copy()
     U = np.asarray(U, F32).copy()
     W = np.asarray(W, F32)
@@ -36,8 +55,11 @@ def admm_iteration(H, U, W, H2, proj_func, rho=1.0, max_iter=50, eps=1e-8):
         it += 1
         d = (H - Hb).astype(np.float64)
         dp = (H - Hp).astype(np.float64)
-        r = np.sum(d * d) / np.sum(H.astype(np.float64) ** 2)
-        s = np.sum(dp * dp) / np.sum(U.astype(np.float64) ** 2)
+        with np.errstate(divide="ignore", invalid="ignore"):   # 0/0, x/0: NaN / inf compare as on the device
+            r = np.sum(d * d) / np.sum(H.astype(np.float64) ** 2)
+            s = np.sum(dp * dp) / np.sum(U.astype(np.float64) ** 2)
+        if history is not None:
+            history.append((float(r), float(s)))
         if r < eps and s < eps:
             break
     return H, U, it

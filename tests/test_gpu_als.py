@@ -6,8 +6,11 @@ Tolerances (fp32 MFMA products, different summation order than torch's CPU einsu
   * vs the reference's own G/F fixtures (tests/golden/f2_admm.npz): rel-Frob <= 1e-5;
   * vs a float64 restatement at full resnet18 / Llama shapes: rel-Frob <= 1e-5;
   * error vs the reference's recorded losses (tests/golden/f3_als.npz): rel <= 1e-5;
-  * batched == single and reruns: bit-identical (fixed-order split-K and block sums).
+  * batched == single and reruns: bit-identical (fixed-order split-K and block sums);
+  * error vs float64 at ragged shapes, both tile classes, NaN guard bands, aligned and not:
+    the derived worst-case fp32 bound of _rel_case (no measured constant).
 """
+import functools
 import os
 
 import numpy as np
@@ -175,6 +178,116 @@ def test_batched_equals_single_and_deterministic(torch_dev):
     e = rel_error_batched(layers)
     assert e == rel_error_batched(layers)
     assert e == [rel_error(W, fs) for W, fs in layers]
+
+
+# --------------------------------------------------------------------------------------
+# The fused error off the fixture shapes: k_als_error<32> (I <= 32), masked rows / columns,
+# partial K-steps, both BM classes in one batch, against a float64 restatement.
+#   (20,12,9; 7)    BM 32, 12 masked rows, N = 108 (44-column second tile), one partial K-step
+#   (9,64,64; 134)  BM 32, 64 column tiles, K tail of 6
+#   (33,10,5; 17)   BM 64 with 31 masked rows, N = 50 < 64, divmod by 5, R = 16 + 1
+#   (100,7,9; 40)   two row tiles (36 valid rows in the second), N = 63
+#   (1,1,1; 1)      the smallest case
+#   (65,65; 1)      2-way, ragged by one both ways
+#   (17,5; 3)       2-way, BM 32
+#   (32,64; 32), (64,64,9; 16)   exact tiles, no masks (the control)
+REL_CASES = [((20, 12, 9), 7), ((9, 64, 64), 134), ((33, 10, 5), 17), ((100, 7, 9), 40), ((1, 1, 1), 1),
+             ((65, 65), 1), ((17, 5), 3), ((32, 64), 32), ((64, 64, 9), 16)]
+MIXED = [((100, 7, 9), 40), ((20, 12, 9), 7), ((65, 65), 1), ((17, 5), 3), ((64, 64, 9), 16), ((9, 64, 64), 134)]
+
+
+def _outer64(fs):
+    fs = [np.asarray(f, np.float64) for f in fs]
+    return np.einsum('ir,jr,kr->ijk', *fs) if len(fs) == 3 else fs[0] @ fs[1].T
+
+
+@functools.lru_cache(maxsize=None)
+def _rel_case(dims, R, kind):
+    """(W, factors, want, bound) in numpy, computed once per case.
+    kind 'a': random W and factors (error ~ 1). kind 'b': W = float32(rec + noise), noise of
+    relative Frobenius size 1e-3 (error ~ 1e-3: a mis-masked row or column moves it by far
+    more than rounding does).
+    want = sqrt(sum (W - rec)^2 / sum W^2) in float64 from the float32 inputs.
+    bound = (R + 2) 2^-24 || |A| (|B| (.) |C|)^T ||_F / ||W||_F + 2^-23 want: the worst-case
+    fp32 accumulation error of rec (R products and sums plus the Khatri-Rao product) moves
+    ||W - rec||_F by at most its own Frobenius norm, and w - acc rounds once (the fp64 sums
+    are negligible). Derived, not measured."""
+    g = np.random.default_rng(1000 * len(dims) + 10 * sum(dims) + R)
+    fs = [g.standard_normal((n, R)).astype(np.float32) for n in dims]
+    rec = _outer64(fs)
+    if kind == "a":
+        W = g.standard_normal(dims).astype(np.float32)
+    else:
+        noise = g.standard_normal(dims)
+        noise *= 1e-3 * np.linalg.norm(rec) / np.linalg.norm(noise)
+        W = (rec + noise).astype(np.float32)
+    W64 = W.astype(np.float64)
+    nw = np.linalg.norm(W64)
+    want = float(np.linalg.norm(W64 - rec) / nw)
+    bound = float((R + 2) * 2.0 ** -24 * np.linalg.norm(_outer64([np.abs(f) for f in fs])) / nw + 2.0 ** -23 * want)
+    return W, fs, want, bound   # shared between tests: read only
+
+
+def _banded(torch, dev, a, band):
+    """`a` on the device as the middle of a flat buffer with `band` NaNs on both sides
+    (band 64: 16-byte aligned; band 65: 4-byte aligned only). Returns (view, buffer)."""
+    buf = torch.full((a.size + 2 * band,), float("nan"), dtype=torch.float32, device=dev)
+    v = buf[band:band + a.size].view(a.shape)
+    v.copy_(torch.from_numpy(a))
+    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * band) % 16
+    return v, buf
+
+
+@pytest.mark.parametrize("band", [64, 65])
+@pytest.mark.parametrize("dims,R", REL_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_rel_error_ragged_vs_float64_guarded(torch_dev, dims, R, band):
+    torch, dev = torch_dev
+    from admmq.als import gram_mttkrp, rel_error
+    for kind in "ab":
+        W, fs, want, bound = _rel_case(dims, R, kind)
+        views, bufs = zip(*[_banded(torch, dev, a, band) for a in [W] + list(fs)])
+        before = [b.clone() for b in bufs]
+        got = rel_error(views[0], list(views[1:]))
+        print(f"{dims} R={R} {kind} band={band}: got {got:.9e} want {want:.9e} diff {abs(got - want):.2e} "
+              f"bound {bound:.2e}")
+        assert np.isfinite(got), (kind, got)
+        assert abs(got - want) <= bound, (kind, got, want, bound)
+        outs = []
+        if band == 65 and kind == "a":   # misaligned W: the 9-tap shapes take the generic MTTKRP too
+            for m in range(len(dims)):
+                G, F = gram_mttkrp(views[0], list(views[1:]), m)
+                Gr, Fr = _ref64(torch, views[0], list(views[1:]), m)
+                outs.append((m, _rel(G.cpu().numpy(), Gr), _rel(F.cpu().numpy(), Fr)))
+        for b, b0 in zip(bufs, before):   # bands (and the operands) bit-unchanged
+            assert torch.equal(b.view(torch.int32), b0.view(torch.int32))
+        for m, eg, ef in outs:
+            assert eg < TOL and ef < TOL, (m, eg, ef)
+
+
+@pytest.mark.parametrize("kind", ["a", "b"])
+def test_rel_error_mixed_class_batch(torch_dev, kind, monkeypatch):
+    """One batch with both BM classes interleaved (per-class error partials and unit0),
+    2-way and 3-way, forwards and reversed: every entry bit-equal to its single call and
+    inside the derived bound; as_tensor and the ctypes route return the same doubles."""
+    torch, dev = torch_dev
+    from admmq import _lib
+    from admmq.als import rel_error, rel_error_batched
+    cases = [_rel_case(d, R, kind) for d, R in MIXED]
+    layers = [(_t(torch, dev, W), [_t(torch, dev, f) for f in fs]) for W, fs, _, _ in cases]
+    single = [rel_error(W, fs) for W, fs in layers]
+    for (_, _, want, bound), got in zip(cases, single):
+        assert np.isfinite(got) and abs(got - want) <= bound, (got, want, bound)
+    fwd = rel_error_batched(layers)
+    rev = rel_error_batched(layers[::-1])
+    assert fwd == single
+    assert rev == single[::-1]
+    ten = rel_error_batched(layers, as_tensor=True)
+    assert ten.dtype == torch.float64 and ten.device.type == "cuda"
+    assert ten.cpu().tolist() == single
+    monkeypatch.setattr(_lib, "use_ops", lambda: False)
+    assert rel_error_batched(layers) == single
+    assert rel_error_batched(layers[::-1]) == single[::-1]
+    assert rel_error_batched(layers, as_tensor=True).cpu().tolist() == single
 
 
 def test_bad_arguments_raise(torch_dev):

@@ -7,7 +7,10 @@ against the reference's outputs (tests/golden/f6_lowrank.npz) and the oracle.
     random 96 x 64 start has close 4th/5th singular values; measured 1.3e-5 after 2 steps);
   * SubspaceProjector vs exact truncation: 1e-4 rel-Frobenius (decaying spectra);
   * KrylovProjector vs exact float64 truncation: 1e-4 on the loop's own flat-spectrum iterates;
-  * three outer iterations: rel errors within 1e-3 of the reference's.
+  * three outer iterations: rel errors within 1e-3 of the reference's;
+  * the two stream kernels alone (scalar and float4 forms, ragged and empty blocks, the
+    device break at iteration k > 1, degenerate residual sums) with an exactly
+    reproducible projection: H, U and the iteration count bit-equal to the oracle.
 """
 import os
 from functools import partial
@@ -211,3 +214,110 @@ def test_f10_reference_band():
         w = hi[i] - lo[i]
         assert lo[i] - 0.5 * w - 0.01 <= r <= hi[i] + 0.5 * w + 0.01, (i, r, lo[i], hi[i])
     print("F10 device rel:", [round(r, 4) for r in rel])
+
+
+# --------------------------------------------------------------------------------------
+# The two stream kernels alone (k_lr_pre / k_lr_post, scalar and float4 forms) against the
+# oracle, bit for bit. The projection is round(4 X) / 4 (lo.proj_quarter and its torch twin:
+# both round half to even, the scalings are exact), so the quantizer is not involved and
+# oracle.lowrank_oracle.admm_iteration (pinned to F6) is an exact reference of H, U and the
+# iteration count.
+
+def _proj_quarter(X):
+    import torch
+    return torch.round(X * 4.0) / 4.0
+
+
+def _at_offset(torch, dev, a, off, fill=7.0):
+    """`a` on the device as a contiguous view `off` floats into a fresh buffer of `fill`
+    (off = 1: the view is 4-byte aligned only). Returns (view, buffer)."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    buf = torch.full((a.size + off + 3,), fill, dtype=torch.float32, device=dev)
+    v = buf[off:off + a.size].view(a.shape)
+    v.copy_(torch.from_numpy(a))
+    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * off) % 16
+    return v, buf
+
+
+def _same_bits(t, a):
+    return np.array_equal(t.cpu().numpy().view(np.uint32), np.asarray(a, np.float32).view(np.uint32))
+
+
+# (shape, float offset of W, float offset of U, max_iter)
+STREAM_CASES = [
+    ((1, 1), 0, 0, 6), ((1, 3), 0, 0, 6), ((7, 11), 0, 0, 6), ((33, 31), 0, 0, 6),   # n % 4 != 0: both scalar
+    ((96, 64), 1, 0, 6),      # only W misaligned: scalar pre, float4 post
+    ((96, 64), 0, 1, 6),      # U misaligned: both scalar, U updated through the view
+    ((1030, 1028), 0, 0, 4),  # float4, n/4 = 264710 > 1024 * 256: 259 per block, ragged block 1022, empty block 1023
+    ((1025, 1025), 0, 0, 4),  # scalar, 1027 per block: block 1023 holds 4 elements
+]
+
+
+@pytest.mark.parametrize("shape,woff,uoff,mi", STREAM_CASES, ids=lambda v: str(v).replace(" ", ""))
+def test_stream_kernels_match_oracle(env, shape, woff, uoff, mi):
+    torch, dev, _ = env
+    from admmq.lowrank import admm_iteration
+    from oracle import lowrank_oracle as lo
+    W, H2, H0 = lo.break_case(shape, seed=11)
+    U0 = (0.25 * np.random.default_rng(12).standard_normal(shape)).astype(np.float32)
+    Ho, Uo, ito = lo.admm_iteration(H0, U0, W, H2, lo.proj_quarter, 1.0, mi, 1e-8)
+    assert ito == mi - 1
+    Wd, Wbuf = _at_offset(torch, dev, W, woff)
+    Ud, Ubuf = _at_offset(torch, dev, U0, uoff)
+    Hd = _t(torch, dev, H0)
+    H, U2, it = admm_iteration(Hd, Ud, Wd, _t(torch, dev, H2), _proj_quarter, rho=1.0, max_iter=mi, eps=1e-8,
+                               return_iters=True)
+    assert it == ito
+    assert U2 is Ud                                   # in place, through the view
+    assert _same_bits(Hd, H0)                         # caller's H untouched
+    assert _same_bits(Wd, W)
+    assert _same_bits(H, Ho)
+    assert _same_bits(Ud, Uo)
+    for buf, off in ((Wbuf, woff), (Ubuf, uoff)):     # nothing written around the views
+        assert bool((buf[:off] == 7.0).all()) and bool((buf[off + W.size:] == 7.0).all())
+
+
+@pytest.mark.parametrize("poll", [1, 8])
+@pytest.mark.parametrize("shape,rho,eps,k", [((7, 11), 1.0, 0.02, 8), ((33, 31), 1.0, 0.02, 11),
+                                             ((96, 64), 1.0, 0.02, 12), ((33, 31), 2.0, 0.005, 11)])
+def test_device_break_at_iteration_k(env, shape, rho, eps, k, poll):
+    """The oracle breaks at iteration k > 1 (tests/test_lowrank_oracle.py shows that
+    max(r, s) stays 25 % off eps at every iteration, so the device's other summation order
+    cannot move a decision). The device reports the same count and the oracle's H and U: a
+    post that formed s from the wrong H (from the new H: s = 0, break at 1; from H_: the
+    rho = 2 case breaks at 13), missed the break or kept running after `done`
+    (max_iter = 40 queues up to 39 - k further iterations with poll = 8) would not."""
+    torch, dev, _ = env
+    from admmq.lowrank import admm_iteration
+    from oracle import lowrank_oracle as lo
+    W, H2, H0 = lo.break_case(shape)
+    Ho, Uo, ito = lo.admm_iteration(H0, np.zeros_like(H0), W, H2, lo.proj_quarter, rho, 40, eps)
+    assert ito == k
+    U = torch.zeros(shape, device=dev)
+    H, _, it = admm_iteration(_t(torch, dev, H0), U, _t(torch, dev, W), _t(torch, dev, H2), _proj_quarter,
+                              rho=rho, max_iter=40, eps=eps, poll=poll, return_iters=True)
+    assert it == k
+    assert _same_bits(H, Ho)
+    assert _same_bits(U, Uo)
+
+
+@pytest.mark.parametrize("zero_start", [False, True])
+@pytest.mark.parametrize("shape", [(7, 11), (96, 64)])
+def test_degenerate_residual_sums(env, shape, zero_start):
+    """W = H2 = 0, U = 0 and H0 on the projection's grid (or all zero): the iterates die
+    out and the residual ratios become x/0 and 0/0. inf and NaN compare false against eps
+    on both sides, so the device runs exactly as many iterations as the oracle."""
+    torch, dev, _ = env
+    from admmq.lowrank import admm_iteration
+    from oracle import lowrank_oracle as lo
+    Z = np.zeros(shape, np.float32)
+    H0 = Z if zero_start else lo.proj_quarter(np.random.default_rng(7).standard_normal(shape))
+    hist = []
+    Ho, Uo, ito = lo.admm_iteration(H0, Z, Z, Z, lo.proj_quarter, 1.0, 12, 0.02, history=hist)
+    assert any(not np.isfinite(r) or not np.isfinite(s) for r, s in hist)   # the case is degenerate
+    for p in (1, 8):
+        U = torch.zeros(shape, device=dev)
+        H, _, it = admm_iteration(_t(torch, dev, H0), U, _t(torch, dev, Z), _t(torch, dev, Z), _proj_quarter,
+                                  rho=1.0, max_iter=12, eps=0.02, poll=p, return_iters=True)
+        assert it == ito
+        assert _same_bits(H, Ho) and _same_bits(U, Uo)
