@@ -22,6 +22,7 @@ from .packed import packed_linear, packed_conv1x1, packed_depthwise_conv1x1  # n
 from .packed import QuantizedActivation, act_encode, act_decode, packed_rowsums  # noqa: F401
 from .packed import packed_linear_int, packed_conv1x1_int  # noqa: F401
 from .packed import packed_taps_int, packed_depthwise_conv1x1_int  # noqa: F401
+from .packed import PackedLowRank, packed_lowrank_linear, save_packed_lowrank, load_packed_lowrank  # noqa: F401
 from .utils import unfold  # noqa: F401
 
 __version__ = "0.1.0"

@@ -21,6 +21,8 @@ the CP builders accept them in place of float tensors: the 1x1 convs / linears t
 3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``).
 ``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
 activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
+``build_qlr_layer`` turns the ``PackedLowRank`` of ``admmq.lowrank`` (``W ~ W_q + L Rt``) into a
+``PackedLowRankLinear``: codes and thin factors, one GEMM (``k_packed_lrgemm``).
 ``integer=True`` of ``build_cp_layer`` returns an ``IntegerPackedCP``: ``conv1`` on ``k_packed_igemm`` and
 the fused depthwise + 1x1 stage on ``k_packed_idwgemm`` (an int8 stencil feeding the int8 MFMA).
 """
@@ -34,9 +36,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from .packed import (PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _meta_words, _pair, _weight_dims,
-                     _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm, packed_gemm, packed_rowsums,
-                     packed_taps_int, taps_kp)
+from .packed import (PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
+                     _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
+                     packed_gemm, packed_lrgemm, packed_rowsums, packed_taps_int, taps_kp)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -146,6 +148,63 @@ class PackedLinear(_PackedWeight):
 
     def forward(self, x):
         return self._gemm(x)
+
+
+class PackedLowRankLinear(_PackedWeight):
+    """``nn.Linear`` on the quant + low-rank form ``W = W_q + L Rt`` of ``admmq.lowrank``: ``x [..., in] -> [..., out]``
+    by ``k_lr_down`` + ``k_packed_lrgemm``. ``W_q`` stays packed in ``codes``; ``L [out, r]`` and
+    ``Rt [r, in]`` are float32 buffers. Neither ``W_q`` nor ``L Rt`` is ever formed. No activation quantizer yet."""
+
+    def __init__(self, p: PackedLowRank, bias: Optional[torch.Tensor] = None, act=None):
+        if act is not None:
+            raise NotImplementedError("PackedLowRankLinear: act= (an output quantizer on the fused quant + low-rank "
+                                      "layer) is not supported")
+        M, K, r = _lowrank_dims(p)
+        super().__init__(p.q, bias, transpose=False)
+        dev = self.codes.device
+        self.register_buffer("L", p.L.detach().clone().to(dev).contiguous())
+        self.register_buffer("Rt", p.Rt.detach().clone().to(dev).contiguous())
+
+    @property
+    def rank(self) -> int:
+        return int(self.L.shape[1])
+
+    def set_activation_quant(self, bits=None, min_val=None, max_val=None):
+        if bits is not None:
+            raise NotImplementedError("PackedLowRankLinear: an output quantizer on the fused quant + low-rank layer is "
+                                      "not supported")
+        self._act = None
+
+    def packed_lowrank(self) -> PackedLowRank:
+        """The layer's weight as a ``PackedLowRank`` sharing its buffers."""
+        return PackedLowRank(q=self.packed(), L=self.L, Rt=self.Rt)
+
+    def dequantize(self) -> torch.Tensor:
+        """``W_q + L Rt`` as a float32 ``[out, in]`` tensor (a new tensor; the layer does not keep it)."""
+        return self.packed().dequantize() + self.L @ self.Rt
+
+    def get_extra_state(self):
+        return dict(super().get_extra_state(), rank=self.rank)
+
+    def set_extra_state(self, state):
+        if int(state.get("rank", -1)) != self.rank:
+            raise ValueError(f"packed low-rank state of rank {state.get('rank')} does not fit this layer (rank {self.rank})")
+        if state.get("act"):
+            raise NotImplementedError("PackedLowRankLinear: a state with an output quantizer is not supported")
+        super().set_extra_state(state)
+
+    def forward(self, x):
+        return packed_lrgemm(self.codes, self._meta, self.out_features, self.in_features, self.L, self.Rt, x, self.bias)
+
+    def extra_repr(self):
+        return (f"{self.in_features}, {self.out_features}, rank={self.rank}, bits={self._q['bits']}, "
+                f"qscheme={self._q['qscheme']}, bias={self.bias is not None}")
+
+
+def build_qlr_layer(p: PackedLowRank, bias: Optional[torch.Tensor] = None) -> PackedLowRankLinear:
+    """The linear layer of a quant + low-rank factorization (``factorize_lowrank(..., return_packed=True)`` or
+    ``load_packed_lowrank``): ``y = (W_q + L Rt) x + bias`` straight from the codes and the factors."""
+    return PackedLowRankLinear(p, bias)
 
 
 class PackedConv1x1(_PackedWeight):

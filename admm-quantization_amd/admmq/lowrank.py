@@ -16,6 +16,10 @@ rho, max_iter, eps)`` (``:85-101``) with the other part held fixed.
   ``project_rank`` (exact truncated SVD through the library, the reference's semantics;
   ``projection="svd"``) or ``SubspaceProjector`` (warm-started subspace iteration:
   cheaper, but it stalls on flat spectra - kept for comparison).
+* ``return_packed=True`` / ``--save-packed`` keep the result in its deployable form, a
+  ``PackedLowRank``: ``W_q`` as the packed codes of the last quantizing projection and ``W_r`` as
+  the two thin factors the last rank projection multiplied out (every projector keeps them
+  as ``last_factors``); ``admmq.export.build_qlr_layer`` runs it.
 """
 from __future__ import annotations
 
@@ -38,6 +42,30 @@ def project_rank(H: torch.Tensor, rank: int) -> torch.Tensor:
     return U[:, :rank] @ torch.diag(S[:rank]) @ Vt[:rank]
 
 
+def _f32_factors(U: torch.Tensor, S: torch.Tensor, Vt: torch.Tensor):
+    """``(U S, Vt)`` rounded to float32: the thin pair whose product a projector returned."""
+    return (U * S).float().contiguous(), Vt.float().contiguous()
+
+
+class SvdProjector:
+    """``project_rank`` as an object that remembers the pair of its last call: ``last_factors`` is
+    ``(U[:, :rank] S[:rank], Vt[:rank])``, the factors it multiplied out."""
+
+    def __init__(self, rank: int):
+        self.rank = rank
+        self._last = None
+
+    def __call__(self, H: torch.Tensor) -> torch.Tensor:
+        U, S, Vt = torch.linalg.svd(H, full_matrices=False)
+        rank = self.rank
+        self._last = (U[:, :rank], S[:rank], Vt[:rank])
+        return U[:, :rank] @ torch.diag(S[:rank]) @ Vt[:rank]   # (project_rank's expression)
+
+    @property
+    def last_factors(self):
+        return None if self._last is None else _f32_factors(*self._last)
+
+
 class SubspaceProjector:
     """Rank-``rank`` truncation by block subspace iteration, warm-started from the previous
     call's subspace (consecutive ADMM iterates differ little). Each sweep runs
@@ -51,6 +79,7 @@ class SubspaceProjector:
         self.tol, self.max_sweeps, self.seed = tol, max_sweeps, seed
         self.Q: Optional[torch.Tensor] = None
         self.sweeps: List[int] = []
+        self._last = None
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         m, n = X.shape
@@ -73,7 +102,13 @@ class SubspaceProjector:
             Ur_prev = Ur
         self.Q = Q
         self.sweeps.append(sweeps)
+        self._last = (Ur, S[:r], Vt[:r])
         return Ur @ torch.diag(S[:r]) @ Vt[:r]
+
+    @property
+    def last_factors(self):
+        """``(U S, Vt)`` of the last call, float32."""
+        return None if self._last is None else _f32_factors(*self._last)
 
 
 def _chol_step(Z: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
@@ -128,6 +163,12 @@ class KrylovProjector:
         self.blocks: List[int] = []
         self.residuals: List[float] = []
         self.repairs = 0
+        self._last = None
+
+    @property
+    def last_factors(self):
+        """``(U S, V^T)`` of the last call (the float64 Ritz triplets), rounded to float32."""
+        return None if self._last is None else _f32_factors(*self._last)
 
     def __call__(self, X: torch.Tensor) -> torch.Tensor:
         m, n = X.shape
@@ -181,6 +222,7 @@ class KrylovProjector:
                 self.Q = orthonormalize(K @ Ub[:, :k])   # warm start: the leading Ritz vectors
                 self.blocks.append(nb)
                 self.residuals.append(res)
+                self._last = (U, S[:r], V.T)
                 if r <= 32:   # the panel kernel's register tile
                     out = panel.outer((U * S[:r]).contiguous(), V.contiguous())
                     return out if X.dtype == torch.float32 else out.to(X.dtype)
@@ -193,7 +235,8 @@ def _is_device_quantizer(f) -> bool:
 
 def admm_iteration(H: torch.Tensor, U: torch.Tensor, W: torch.Tensor, H2: torch.Tensor,
                    proj_func: Callable[[torch.Tensor], torch.Tensor], rho: float = 1.0, max_iter: int = 50,
-                   eps: float = 1e-8, poll: Optional[int] = None, return_iters: bool = False):
+                   eps: float = 1e-8, poll: Optional[int] = None, return_iters: bool = False,
+                   keep: Optional[dict] = None):
     """scripts/factorize_lowrank.py:85-101. Returns (H, U); U is updated in place and
     returned (as in the reference); the caller's H is not written.
 
@@ -201,7 +244,11 @@ def admm_iteration(H: torch.Tensor, U: torch.Tensor, W: torch.Tensor, H2: torch.
     iterations. Default: 8 for the HIP quantizer (queued without a host round trip;
     an iteration queued after the break is a device no-op), 1 for any other
     projection (an SVD synchronises anyway, and a projection of a stale iterate
-    after the break would cost a full SVD)."""
+    after the break would cost a full SVD).
+
+    ``keep``: a dict that receives ``keep["X"]``, the iterate of the last projection that was
+    taken into ``H`` (``None`` when no iteration ran). An iteration queued after the break
+    leaves ``X`` as it is (``k_lr_pre`` does nothing), so ``H = proj_func(keep["X"])`` either way."""
     if poll is None:
         poll = 8 if _is_device_quantizer(proj_func) else 1
     for t in (H, U, W, H2):
@@ -231,26 +278,41 @@ def admm_iteration(H: torch.Tensor, U: torch.Tensor, W: torch.Tensor, H2: torch.
                                           ctypes.c_float(eps), wsp, wsn, s), "lowrank_post")
     if Uc is not U:
         U.copy_(Uc)
+    if keep is not None:
+        keep["X"] = X if max_iter > 1 else None
     iters = int(ws[:12].view(torch.int32)[2])
     return (Hc, U, iters) if return_iters else (Hc, U)
 
 
 def factorize_lowrank(W: torch.Tensor, bits: int, rank: int, qscheme: str = "tensor_minmax", max_iter: int = 100,
                       inner_iter: int = 50, rho: float = 1.0, seed: int = 42, projection: str = "krylov",
-                      log_every: int = 10, logger=None):
+                      log_every: int = 10, logger=None, return_packed: bool = False):
     """The alternating loop of scripts/factorize_lowrank.py:156-170 (init 'random').
     Returns (W_q, W_r, rel_history). Random starts come from the CPU generator (seeded).
+
+    ``return_packed=True`` returns ``(W_q, W_r, rel_history, packed)`` with ``packed`` a
+    ``PackedLowRank``: ``packed.q`` holds the codes of the last quantizing projection
+    (``packed.q.dequantize()`` equals ``W_q`` bit for bit; tested on the device before returning,
+    ``RuntimeError`` otherwise), ``packed.L`` / ``packed.Rt`` the float32 pair ``U S`` / ``V^T`` that the
+    last rank projection multiplied out to make ``W_r``. Schemes as ``quantize_packed``: the
+    per-channel schemes and ``tensor_minmax`` at 1 bit are refused before the loop starts.
 
     ``projection`` picks the rank projection (``:80-82``): ``"krylov"`` (default) is the
     device block-Krylov projector on the hand-written fp64-MFMA panel kernels (DESIGN.md
     §2.18; pinned to the reference's own trajectory band F10); ``"svd"`` is the exact
     library SVD truncation (``project_rank``, the reference's arithmetic) for callers that
     want it explicitly; ``"subspace"`` the cheaper subspace iteration (comparison only)."""
+    if return_packed:   # (quantize_packed's refusals, before any device work)
+        from . import packed as _packed
+        _packed._validate(bits, qscheme)
+        if W.dim() != 2:
+            raise ValueError(f"factorize_lowrank: return_packed needs a 2-D weight, got shape {tuple(W.shape)}")
     _lib.require_device(W)
     dev = W.device
     g = torch.Generator().manual_seed(seed)
     quant = partial(quantize_tensor, qscheme=qscheme, bits=bits)
-    proj = (partial(project_rank, rank=rank) if projection == "svd" else
+    kept = {} if return_packed else None
+    proj = (SvdProjector(rank) if projection == "svd" else
             KrylovProjector(rank, seed=seed) if projection == "krylov" else SubspaceProjector(rank, seed=seed))
     W_q = torch.randn(*W.shape, generator=g).to(dev)
     U_q = torch.zeros_like(W_q)
@@ -259,7 +321,7 @@ def factorize_lowrank(W: torch.Tensor, bits: int, rank: int, qscheme: str = "ten
     hist = []
     nw = torch.linalg.norm(W)
     for i in range(max_iter):
-        W_q, U_q = admm_iteration(W_q, U_q, W, W_r, quant, rho=rho, max_iter=inner_iter)
+        W_q, U_q = admm_iteration(W_q, U_q, W, W_r, quant, rho=rho, max_iter=inner_iter, keep=kept)
         W_r, U_r = admm_iteration(W_r, U_r, W, W_q, proj, rho=rho, max_iter=inner_iter)
         rel = float(torch.linalg.norm(W - W_r - W_q) / nw)
         if logger and i % log_every == 0:
@@ -268,7 +330,24 @@ def factorize_lowrank(W: torch.Tensor, bits: int, rank: int, qscheme: str = "ten
             hist.append(rel)
             break
         hist.append(rel)
+    if return_packed:
+        return W_q, W_r, hist, _pack_result(W_q, kept.get("X"), proj, bits, qscheme)
     return W_q, W_r, hist
+
+
+def _pack_result(W_q: torch.Tensor, X: Optional[torch.Tensor], proj, bits: int, qscheme: str):
+    """The ``PackedLowRank`` of a finished run: the codes of ``quantize_packed`` on the last projected iterate
+    (bit-exact with the ``quantize_tensor`` that made ``W_q``; verified here) and the projector's last pair."""
+    from .packed import PackedLowRank, quantize_packed
+    if X is None:
+        raise RuntimeError("admmq.lowrank: no quantizing projection ran (max_iter / inner_iter too small): W_q has no grid")
+    q = quantize_packed([X], bits, qscheme)[0]
+    if not torch.equal(q.dequantize(), W_q):
+        raise RuntimeError("admmq.lowrank: the packed codes of the last quantizing projection do not decode to W_q")
+    pair = proj.last_factors
+    if pair is None:
+        raise RuntimeError("admmq.lowrank: the rank projection kept no factors")
+    return PackedLowRank(q=q, L=pair[0], Rt=pair[1])
 
 
 def main(argv=None):
@@ -290,6 +369,9 @@ def main(argv=None):
     ap.add_argument("--projection", choices=["svd", "krylov", "subspace"], default="krylov",
                     help="rank projection: device block-Krylov on the panel kernels (default) or the exact library "
                          "SVD truncation of the reference (svd)")
+    ap.add_argument("--save-packed", action="store_true",
+                    help="also write {layer}_{bits}_{rank}_{rel}_QR_packed.pt: W_q as packed codes and W_r as its two thin "
+                         "factors (admmq.load_packed_lowrank, admmq.export.build_qlr_layer)")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("admmq.lowrank needs a ROCm GPU")
@@ -304,13 +386,17 @@ def main(argv=None):
         W = torch.from_numpy(synthetic.layer_weight(spec, i))
     W = W.to(dev)
     t0 = time.time()
-    W_q, W_r, hist = factorize_lowrank(W, a.bits, a.rank, a.qscheme, a.max_iter, seed=a.seed,
-                                       projection=a.projection, logger=print)
+    res = factorize_lowrank(W, a.bits, a.rank, a.qscheme, a.max_iter, seed=a.seed, projection=a.projection, logger=print,
+                            return_packed=a.save_packed)
+    W_q, W_r, hist = res[:3]
     print(f"done in {time.time() - t0:.1f}s, rel {hist[-1]:.4f}")
     os.makedirs(a.output_dir, exist_ok=True)
     rel = hist[-1]
     torch.save(W_q.cpu(), os.path.join(a.output_dir, f'{a.layer}_{a.bits}_{a.rank}_{rel:.3f}_Q.pt'))
     torch.save(W_r.cpu(), os.path.join(a.output_dir, f'{a.layer}_{a.bits}_{a.rank}_{rel:.3f}_R.pt'))
+    if a.save_packed:
+        from .packed import save_packed_lowrank
+        save_packed_lowrank(os.path.join(a.output_dir, f'{a.layer}_{a.bits}_{a.rank}_{rel:.3f}_QR_packed.pt'), res[3])
     return W_q, W_r, hist
 
 

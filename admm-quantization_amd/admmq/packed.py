@@ -19,6 +19,10 @@ fixed-range quantizer's level clamped to ``0 .. 2^bits - 1``), and ``packed_line
 ``packed_depthwise_conv1x1_int`` is the fused depthwise + 1x1 stage on such codes (``k_packed_idwgemm``: an
 int8 stencil over the codes feeds the int8 MFMA).
 
+``PackedLowRank`` is the deployable form of ``admmq.lowrank``'s ``W ~ W_q + W_r``: ``W_q`` as packed
+codes, ``W_r`` as its thin factors ``L [M, r]``, ``Rt [r, K]``; ``packed_lowrank_linear`` evaluates
+``x (W_q + L Rt)^T (+ bias)`` from the three in one GEMM (``k_lr_down`` + ``k_packed_lrgemm``).
+
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
 """
@@ -35,10 +39,13 @@ from . import _lib
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
            "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
-           "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int"]
+           "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
+           "packed_lrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
+FORMAT_LOWRANK = "admmq.packed_lowrank.v1"
+RANK_MAX = 256   # of the fused quant + low-rank GEMM
 
 
 def packed_bytes(numel: int, bits: int) -> int:
@@ -876,3 +883,133 @@ def load_packed(path: str, device=None):
                                 zero_point=int(it["zero_point"]), mn=float(it["mn"]), rng=float(it["rng"]),
                                 index=int(it["index"])))
     return out if d["many"] else out[0]
+
+
+# --- quant + low-rank -----------------------------------------------------------
+@dataclass
+class PackedLowRank:
+    """``W ~ W_q + W_r`` of ``admmq.lowrank`` in its deployable form: ``q`` the packed codes of ``W_q [M, K]``,
+    ``L [M, r]`` and ``Rt [r, K]`` the float32 factors of ``W_r = L Rt`` (``K`` contiguous in ``Rt``: the
+    down-projection streams along it)."""
+    q: PackedTensor
+    L: torch.Tensor
+    Rt: torch.Tensor
+
+    @property
+    def rank(self) -> int:
+        return int(self.L.shape[1])
+
+    @property
+    def nbytes(self) -> int:
+        """Resident bytes of the weights: the code stream and the two factors."""
+        return self.q.nbytes + 4 * (int(self.L.numel()) + int(self.Rt.numel()))
+
+    def dequantize(self) -> torch.Tensor:
+        """``W_q + L Rt`` as a float32 ``[M, K]`` tensor (the library product; for comparisons)."""
+        return self.q.dequantize() + self.L @ self.Rt
+
+
+def _lowrank_dims(p: "PackedLowRank") -> Tuple[int, int, int]:
+    """``(M, K, r)`` of ``p``, checked on the host."""
+    if not isinstance(p, PackedLowRank):
+        raise TypeError("expected a PackedLowRank")
+    M, K = _weight_dims(p.q, False)
+    L, Rt = p.L, p.Rt
+    if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
+        raise ValueError(f"PackedLowRank: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
+    if L.dtype != torch.float32 or Rt.dtype != torch.float32:
+        raise TypeError(f"PackedLowRank: L and Rt must be float32, got {L.dtype} and {Rt.dtype}")
+    r = int(L.shape[1])
+    if not 1 <= r <= RANK_MAX:
+        raise ValueError(f"PackedLowRank: rank must be 1..{RANK_MAX}, got {r}")
+    return M, K, r
+
+
+def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
+                  x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``y = x (D + L Rt)^T (+ bias)`` with ``D`` the ``[M, K]`` de-quantization of ``codes``, ``L [M, r]`` and
+    ``Rt [r, K]`` float32 (``admmq_packed_lrgemm``): ``x [..., K] -> [..., M]``. Neither ``D`` nor ``L Rt`` is
+    written to memory. Inference only: an ``x`` that requires grad is refused while grad mode is on."""
+    if not isinstance(x, torch.Tensor) or any(t.device.type != "cuda" for t in (x, codes, L, Rt)):
+        raise RuntimeError("admmq: packed_lrgemm needs its codes, factors and activations on a ROCm GPU (device 'cuda'); "
+                           "the MI355X path has no CPU implementation")
+    _lib.require_device(x)
+    if x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: packed_lrgemm is inference only (no backward through packed weights): call it "
+                           "under torch.no_grad() or detach x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_lrgemm(codes, meta_words, M, K, L, Rt, x, bias)
+    M, K = int(M), int(K)
+    L, Rt = L.detach(), Rt.detach()
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_lrgemm (csrc/torch_ops.cpp) -> admmq_packed_lrgemm
+        return _lib.ops().packed_lrgemm(codes, meta_words, M, K, L, Rt, x, bias)
+    lib = _lib.load()
+    _lib.require_device(L)
+    _lib.require_device(Rt)
+    if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
+        raise ValueError(f"packed_lrgemm: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
+    if x.dim() < 1 or x.shape[-1] != K:
+        raise ValueError(f"packed_lrgemm: x must be [..., {K}], got {tuple(x.shape)}")
+    xc, Lc, Rc = x.contiguous(), L.contiguous(), Rt.contiguous()
+    if xc.numel() == 0:
+        raise ValueError("packed_lrgemm: empty x")
+    N, r = xc.numel() // K, int(Lc.shape[1])
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    bc = None
+    if bias is not None:
+        _lib.require_device(bias)
+        if tuple(bias.shape) != (M,):
+            raise ValueError(f"packed_lrgemm: bias must be [{M}], got {tuple(bias.shape)}")
+        bc = bias.contiguous()
+    y = torch.empty(tuple(x.shape[:-1]) + (M,), dtype=torch.float32, device=x.device)
+    nbytes = lib.admmq_packed_lrgemm_workspace_size(M, K, N, r)
+    ws = _lib.workspace(nbytes, x.device)
+    rc = lib.admmq_packed_lrgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), r, _lib.ptr(xc), N,
+                                 _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_lrgemm")
+    return y
+
+
+_opaque_packed_lrgemm = torch.compiler.disable(packed_lrgemm)
+
+
+def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``F.linear(x, W_q + L Rt, bias)`` computed from ``p``'s codes and factors in one GEMM: ``x [..., K] ->
+    [..., M]``. Inference only."""
+    M, K, _ = _lowrank_dims(p)
+    return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias)
+
+
+def save_packed_lowrank(path: str, p: "PackedLowRank") -> None:
+    """Write a ``PackedLowRank`` as a plain dict of tensors and Python scalars; ``load_packed_lowrank`` reads it
+    back with ``weights_only=True``."""
+    _lowrank_dims(p)
+    q = p.q
+    torch.save({"format": FORMAT_LOWRANK,
+                "q": {"codes": q.codes.detach().cpu(), "shape": [int(s) for s in q.shape], "bits": int(q.bits),
+                      "qscheme": q.qscheme, "scale": float(q.scale), "zero_point": int(q.zero_point), "mn": float(q.mn),
+                      "rng": float(q.rng), "index": int(q.index)},
+                "L": p.L.detach().cpu().contiguous(), "Rt": p.Rt.detach().cpu().contiguous()}, path)
+
+
+def load_packed_lowrank(path: str, device=None) -> "PackedLowRank":
+    """The ``PackedLowRank`` that ``save_packed_lowrank`` wrote, with its tensors on ``device``."""
+    d = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(d, dict) or d.get("format") != FORMAT_LOWRANK:
+        raise ValueError(f"{path}: not a packed quant + low-rank file ({FORMAT_LOWRANK})")
+    it = d["q"]
+    c = it["codes"]
+    if c.dtype != torch.uint8:
+        raise TypeError(f"{path}: codes must be uint8, got {c.dtype}")
+    to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
+    p = PackedLowRank(q=PackedTensor(codes=to(c), shape=tuple(it["shape"]), bits=int(it["bits"]), qscheme=it["qscheme"],
+                                     scale=float(it["scale"]), zero_point=int(it["zero_point"]), mn=float(it["mn"]),
+                                     rng=float(it["rng"]), index=int(it["index"])),
+                      L=to(d["L"]), Rt=to(d["Rt"]))
+    _lowrank_dims(p)
+    return p

@@ -9,6 +9,7 @@
 //   admmq::quantize_packed / dequantize_packed: the packed integer codes of the tensor schemes
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::packed_gemm             a packed weight times float32 activations
+//   admmq::packed_lrgemm           packed codes + low-rank factors times float32 activations, one GEMM
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
@@ -695,6 +696,74 @@ at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_word
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
 }
 
+// --- packed_lrgemm --------------------------------------------------------------------------
+// y = x (D + L Rt)^T (+ bias): D the [M, K] de-quantization of `codes`, L [M, r], Rt [r, K]
+// (admmq_packed_lrgemm). x [..., K] -> [..., M]. Inference only.
+std::vector<int64_t> packed_lrgemm_shape(const at::Tensor& x, const at::Tensor& L, const at::Tensor& Rt, int64_t M, int64_t K) {
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_lrgemm: M and K must be positive");
+  TORCH_CHECK(L.dim() == 2 && Rt.dim() == 2 && L.size(0) == M && Rt.size(1) == K && L.size(1) == Rt.size(0),
+              "admmq: packed_lrgemm: L must be [", M, ", r] and Rt [r, ", K, "], got ", L.sizes(), " and ", Rt.sizes());
+  TORCH_CHECK(L.size(1) >= 1 && L.size(1) <= 256, "admmq: packed_lrgemm: rank r must be 1..256, got ", L.size(1));
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "admmq: packed_lrgemm: x must be [..., ", K, "], got ", x.sizes());
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  shape.back() = M;
+  return shape;
+}
+
+at::Tensor packed_lrgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                              const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& x,
+                              const std::optional<at::Tensor>& bias) {
+  check_f32_device(x, "x");
+  check_f32_device(L, "L");
+  check_f32_device(Rt, "Rt");
+  TORCH_CHECK(!((x.requires_grad() || L.requires_grad() || Rt.requires_grad()) && at::GradMode::is_enabled()),
+              "admmq: packed_lrgemm is inference only (no backward through packed weights): call it under "
+              "torch.no_grad() or detach x");
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
+              "admmq: packed_lrgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_same_device(codes, x, "codes");
+  check_same_device(L, x, "L");
+  check_same_device(Rt, x, "Rt");
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
+              "admmq: packed_lrgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  const std::vector<int64_t> oshape = packed_lrgemm_shape(x, L, Rt, M, K);
+  admmq_qmeta meta;
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_lrgemm: bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_lrgemm: a ", M,
+              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
+              " code bytes, got ", codes.numel());
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous(), Lc = L.contiguous(), Rc = Rt.contiguous();
+  at::Tensor cc = codes.contiguous();
+  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_lrgemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int64_t N = xc.numel() / K;
+  TORCH_CHECK(N > 0, "admmq: packed_lrgemm: empty x");
+  const int32_t r = static_cast<int32_t>(Lc.size(1));
+  at::Tensor y = at::empty(oshape, xc.options());
+  const size_t nbytes = admmq_packed_lrgemm_workspace_size(M, K, N, r);
+  at::Tensor ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_lrgemm(cc.data_ptr<uint8_t>(), &meta, M, K, Lc.data_ptr<float>(), Rc.data_ptr<float>(), r,
+                               xc.data_ptr<float>(), N, bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(),
+                               ws.data_ptr(), ws.numel(), stream_of(xc)),
+           "packed_lrgemm");
+  return y;
+}
+
+at::Tensor packed_lrgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                              const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& x,
+                              const std::optional<at::Tensor>& bias) {
+  return at::empty(packed_lrgemm_shape(x, L, Rt, M, K), x.options().dtype(at::kFloat));
+}
+
 // --- packed_dwgemm --------------------------------------------------------------------------
 // The depthwise kh x kw stage (taps [kh kw, K]) and the 1x1 stage by the packed [M, K] weight
 // in one kernel (admmq_packed_dwgemm): x [nb, K, H, W] -> [nb, M, Ho, Wo]. Inference only.
@@ -938,6 +1007,8 @@ TORCH_LIBRARY(admmq, m) {
   m.def("dequantize_packed(Tensor[] codes, Tensor meta, int[] numel) -> Tensor[]");
   m.def("packed_gemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
         "Tensor? bias=None) -> Tensor");
+  m.def("packed_lrgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor x, Tensor? bias=None) "
+        "-> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
         "int sw, int ph, int pw, Tensor? bias=None) -> Tensor");
   m.def("packed_gemm_act(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
@@ -969,6 +1040,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("quantize_packed", &quantize_packed_cuda);
   m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("packed_gemm", &packed_gemm_cuda);
+  m.impl("packed_lrgemm", &packed_lrgemm_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_cuda);
@@ -990,6 +1062,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("quantize_packed", &quantize_packed_meta);
   m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("packed_gemm", &packed_gemm_meta);
+  m.impl("packed_lrgemm", &packed_lrgemm_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_meta);

@@ -402,6 +402,34 @@ int32_t admmq_packed_idwgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
                              const admmq_actq* mid_q, const admmq_actq* out_q, int32_t* mid_clamped, int32_t* clamped,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Packed quant + low-rank GEMM: the deployable form of W ~ W_q + W_r
+ * (admmq.lowrank): W_q as packed codes, W_r as its thin factors, one call
+ *   y[N, M] = x[N, K] . (D + L Rt)^T (+ bias[M])
+ * with D [M, K] the table de-quantization of `codes` (as for admmq_packed_gemm, trans_w = 0),
+ * L [M, r] and Rt [r, K] row-major float32, 1 <= r <= 256. Linear layout only: x and y
+ * row-major, one row per token. Neither D nor L Rt is written to memory.
+ * Arithmetic, with kp = max(64, 32 ceil(K/1024)) and np = ceil(K/kp) (admmq_packed_gemm's K
+ * pieces, a function of K alone), every sum an fp32 MFMA chain in increasing index from zero:
+ *   t[j, c] = ((s_0 + s_1) + ...) + s_{np-1},  s_p = sum over piece p of Rt[j, k] x[c, k]
+ *   y[c, m] = ((((p_0 + p_1) + ...) + p_{np-1}) + q) + bias[m]
+ * with p_i the pieces of admmq_packed_gemm on D and q = sum_j L[m, j] t[j, c] (j zero-padded
+ * to a multiple of 32). An output depends on its own column of x, on K and on r only: the
+ * same bits for every N and on every call; with L = 0 or Rt = 0 the values of
+ * admmq_packed_gemm. Launches: k_lr_down (t), k_packed_lrgemm (the pieces and the tail), and
+ * k_lr_reduce where the pieces run as separate workgroups - one more than admmq_packed_gemm.
+ * codes: device, 16-byte aligned; L, Rt, x, y, bias (may be NULL): device, float aligned.
+ * `meta` is a HOST record. stream: a hipStream_t. Limits: admmq_packed_gemm's on M, K, N
+ * (nb = 1) and M*K. ADMMQ_ERR_ARG for NULL codes / meta / L / Rt / x / y, non-positive sizes,
+ * r outside 1..256, what admmq_packed_gemm refuses of a meta record, misaligned pointers,
+ * sizes past the limits; ADMMQ_ERR_WORKSPACE for a NULL or short workspace - all before any
+ * launch. admmq_packed_lrgemm_workspace_size depends on its arguments only: 0 for arguments
+ * out of range, else positive (t always lives there: at least
+ * admmq_packed_gemm_workspace_size(M, K, N, 1) + 4 r N bytes). */
+size_t admmq_packed_lrgemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t r);
+int32_t admmq_packed_lrgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const float* L,
+                            const float* Rt, int32_t r, const float* x, int64_t N, const float* bias, float* y,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

@@ -173,6 +173,49 @@ int main(void) {
     fails += admmq_packed_gemm(c, &q2, 0, 8, 8, x, 0, 4, 1, NULL, y, ws, 1 << 20, NULL) != ADMMQ_ERR_ARG;
     fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, ws, 16, NULL) != ADMMQ_ERR_WORKSPACE;
     fails += admmq_packed_gemm(c, &qm, 0, 512, 1141, x, 0, 4, 1, NULL, y, NULL, 0, NULL) != ADMMQ_ERR_WORKSPACE;
+    /* the quant + low-rank GEMM: the workspace always holds t (at least the GEMM's images and
+     * 4 r N bytes), and every refusal before any launch */
+    {
+      const float* lf = (const float*)0x30000;
+      const float* rt = (const float*)0x40000;
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, 6000), K = rnd(1, 6000), N = rnd(1, t % 3 ? 70 : 4000);
+        const int32_t r = rnd(1, 256);
+        const size_t w = admmq_packed_lrgemm_workspace_size(M, K, N, r);
+        fails += w != admmq_packed_lrgemm_workspace_size(M, K, N, r);
+        fails += w < admmq_packed_gemm_workspace_size(M, K, N, 1) + (size_t)4 * r * N;
+      }
+      fails += admmq_packed_lrgemm_workspace_size(0, 8, 8, 4) != 0;
+      fails += admmq_packed_lrgemm_workspace_size(8, 8, -1, 4) != 0;
+      fails += admmq_packed_lrgemm_workspace_size(8, 8, 8, 0) != 0;
+      fails += admmq_packed_lrgemm_workspace_size(8, 8, 8, 257) != 0;
+      fails += admmq_packed_lrgemm_workspace_size((int64_t)1 << 40, 8, 8, 4) != 0;
+      fails += admmq_packed_lrgemm_workspace_size(8, 8, 4, 4) != 64;
+#define LR(cc, mm, M, K, ll, rr, r, xx, N, yy, ws, wsb) admmq_packed_lrgemm(cc, mm, M, K, ll, rr, r, xx, N, NULL, yy, ws, wsb, NULL)
+      fails += LR(NULL, &qm, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, NULL, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, NULL, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, NULL, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, rt, 4, NULL, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, rt, 4, x, 4, NULL, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 0, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, rt, 4, x, -4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, rt, 0, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, lf, rt, 257, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c + 4, &qm, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 8, 8, (const float*)0x30002, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bits = 9;
+      fails += LR(c, &q2, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX; q2.bits = 1;
+      fails += LR(c, &q2, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 3;
+      fails += LR(c, &q2, 8, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, (int64_t)1 << 30, 8, lf, rt, 4, x, 4, y, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LR(c, &qm, 512, 1141, lf, rt, 8, x, 4, y, ws, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += LR(c, &qm, 8, 8, lf, rt, 4, x, 4, y, ws, 63) != ADMMQ_ERR_WORKSPACE;
+      fails += LR(c, &qm, 1024, 134, lf, rt, 8, x, 1024, y, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+#undef LR
+    }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
     const float* tp = (const float*)0x18000;
