@@ -142,6 +142,8 @@ def load() -> ctypes.CDLL:
         "admmq_dequantize_packed": (I32, [P, P, P, P, I32, P]),
         "admmq_packed_gemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_gemm": (I32, [P, P, I32, I64, I64, P, I32, I64, I32, P, P, P, S, P]),
+        "admmq_packed_hgemm_workspace_size": (S, [P, I64, I64, I64, I32]),
+        "admmq_packed_hgemm": (I32, [P, P, I32, I64, I64, P, I32, I32, I64, I32, P, P, I32, P, S, P]),
         "admmq_packed_lrgemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_lrgemm": (I32, [P, P, I64, I64, P, P, I32, P, I64, P, P, P, S, P]),
         "admmq_packed_dwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),

@@ -64,7 +64,10 @@ class _PackedWeight(nn.Module):
     transpose ``[in, out]``). ``codes`` is a uint8 buffer; the scale / zero-point / shape travel
     in the extra state; ``bias`` is an optional parameter (``requires_grad=False``: the layer is
     inference only). There is no ``weight`` attribute: ``dequantize()`` returns the float32
-    weight for callers that want the library GEMM instead."""
+    weight for callers that want the library GEMM instead. A bfloat16 / float16 input runs on the
+    16-bit MFMA and gives an output of its dtype; ``module.half()`` leaves the codes
+    and the quantization record untouched and turns only the bias into half (it is read as float32,
+    exactly). The output quantizer needs float32 activations."""
     _layout = 1
 
     def __init__(self, p: PackedTensor, bias: Optional[torch.Tensor] = None, transpose: bool = False):
@@ -153,7 +156,9 @@ class PackedLinear(_PackedWeight):
 class PackedLowRankLinear(_PackedWeight):
     """``nn.Linear`` on the quant + low-rank form ``W = W_q + L Rt`` of ``admmq.lowrank``: ``x [..., in] -> [..., out]``
     by ``k_lr_down`` + ``k_packed_lrgemm``. ``W_q`` stays packed in ``codes``; ``L [out, r]`` and
-    ``Rt [r, in]`` are float32 buffers. Neither ``W_q`` nor ``L Rt`` is ever formed. No activation quantizer yet."""
+    ``Rt [r, in]`` are float32 buffers. Neither ``W_q`` nor ``L Rt`` is ever formed. No activation quantizer yet.
+    A bfloat16 / float16 input is a composition, not the fused kernel: the half packed GEMM with a float32
+    result plus ``(x.float() @ Rt.float().T) @ L.float().T`` and the bias, converted once to the input's dtype."""
 
     def __init__(self, p: PackedLowRank, bias: Optional[torch.Tensor] = None, act=None):
         if act is not None:

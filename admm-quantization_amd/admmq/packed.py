@@ -223,19 +223,28 @@ def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
     return [y.view(p.shape) for y, p in zip(ys, packed)]
 
 
+HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}   # ADMMQ_DT_F16 / ADMMQ_DT_BF16 (include/admmq.h)
+
+
 def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int, x: torch.Tensor,
-                x_layout: int, bias: Optional[torch.Tensor] = None, act=None) -> torch.Tensor:
+                x_layout: int, bias: Optional[torch.Tensor] = None, act=None, out_dtype=None) -> torch.Tensor:
     """``Y = W X (+ bias)`` with ``W`` the ``[M, K]`` de-quantization of ``codes`` (``transpose``: of the
     ``[K, M]`` packed tensor's transpose). ``meta_words``: the 8 int32 words of the meta record on
     the CPU. ``x_layout`` 0: ``x [n, K, ...] -> [n, M, ...]``; 1: ``x [..., K] -> [..., M]``.
     ``act = (bits, min_val, max_val)``: the fixed-range activation quantizer of ``min_max_quantize``
     applied to the output inside the kernel (``admmq_packed_gemm_act``): the bits of quantizing the
-    result in a launch of its own. Inference only: an ``x`` that requires grad is refused while grad
-    mode is on."""
+    result in a launch of its own. A ``torch.bfloat16`` / ``torch.float16`` ``x`` runs on the 16-bit MFMA
+    (``admmq_packed_hgemm``): the result has ``x``'s dtype, or float32 with
+    ``out_dtype=torch.float32``; ``bias`` may be float32 or of ``x``'s dtype; ``act`` is not available
+    there. Inference only: an ``x`` that requires grad is refused while grad mode is on."""
     if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda":
         raise RuntimeError("admmq: packed_gemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
                            "the MI355X path has no CPU implementation")
+    if x.dtype in HALF_DTYPES:
+        return _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, out_dtype)
     _lib.require_device(x)
+    if out_dtype is not None and out_dtype != torch.float32:
+        raise ValueError(f"packed_gemm: a float32 x gives a float32 result, not out_dtype={out_dtype}")
     if x.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
                            "under torch.no_grad() or detach x")
@@ -307,6 +316,71 @@ def _act_record(act):
 _opaque_packed_gemm = torch.compiler.disable(packed_gemm)
 
 
+def _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, out_dtype):
+    """``packed_gemm`` on a bfloat16 / float16 ``x`` already known to be on the GPU (``admmq_packed_hgemm``)."""
+    if act is not None:
+        raise ValueError(f"packed_gemm: act= (an output quantizer) is not available for a {x.dtype} x; it needs "
+                         "float32 activations")
+    if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+        raise ValueError(f"packed_gemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
+                           "under torch.no_grad() or detach x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like the float32 call
+        return _opaque_packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, out_dtype)
+    M, K, x_layout = int(M), int(K), int(x_layout)
+    out_f32 = out_dtype == torch.float32
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor):
+            raise TypeError(f"admmq: expected a torch.Tensor, got {type(bias).__name__}")
+        if bias.device.type != "cuda":
+            raise RuntimeError("admmq: tensors must live on a ROCm GPU (device 'cuda'); the MI355X path has "
+                               "no CPU implementation")
+        if bias.dtype != torch.float32 and bias.dtype != x.dtype:
+            raise TypeError(f"admmq: packed_gemm: bias must be float32 or x's dtype {x.dtype}, got {bias.dtype}")
+        bias = bias.detach().float()   # (exact)
+    if _lib.use_ops():   # torch.ops.admmq.packed_hgemm (csrc/torch_ops.cpp) -> admmq_packed_hgemm
+        return _lib.ops().packed_hgemm(codes, meta_words, bool(transpose), M, K, x, x_layout, bias, out_f32)
+    lib = _lib.load()
+    if x_layout == 0:
+        if x.dim() < 3 or x.shape[1] != K:
+            raise ValueError(f"packed_gemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
+        oshape = (x.shape[0], M) + tuple(x.shape[2:])
+        nb = int(x.shape[0])
+    elif x_layout == 1:
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError(f"packed_gemm: x must be [..., {K}], got {tuple(x.shape)}")
+        oshape = tuple(x.shape[:-1]) + (M,)
+        nb = 1
+    else:
+        raise ValueError("packed_gemm: x_layout must be 0 or 1")
+    xc = x.detach().contiguous()
+    if xc.numel() == 0:
+        raise ValueError("packed_gemm: empty x")
+    N = xc.numel() // (nb * K)
+    cc = codes.contiguous()
+    if cc.data_ptr() % 16:
+        cc = cc.clone()
+    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    bc = None
+    if bias is not None:
+        if tuple(bias.shape) != (M,):
+            raise ValueError(f"packed_gemm: bias must be [{M}], got {tuple(bias.shape)}")
+        bc = bias.contiguous()
+    xdt = HALF_DTYPES[x.dtype]
+    y = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    nbytes = lib.admmq_packed_hgemm_workspace_size(ctypes.byref(meta), M, K, N, nb)
+    ws = _lib.workspace(nbytes, x.device)
+    rc = lib.admmq_packed_hgemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc), xdt,
+                                x_layout, N, nb, _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws),
+                                ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_hgemm")
+    return y
+
+
+_opaque_packed_hgemm = torch.compiler.disable(_packed_hgemm)
+
+
 def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
     _validate(p.bits, p.qscheme)
     if len(p.shape) != 2:
@@ -321,25 +395,27 @@ def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
 
 
 def packed_linear(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
-                  transpose: bool = False, act=None) -> torch.Tensor:
+                  transpose: bool = False, act=None, out_dtype=None) -> torch.Tensor:
     """``F.linear(x, W, bias)`` with ``W = p.dequantize()`` (``transpose``: its transpose) computed
-    from the codes: ``x [..., K] -> [..., M]``. Inference only."""
+    from the codes: ``x [..., K] -> [..., M]``. A bfloat16 / float16 ``x`` gives a result of its dtype
+    (float32 with ``out_dtype=torch.float32``), as ``packed_gemm``. Inference only."""
     M, K = _weight_dims(p, transpose)
-    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias, act)
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias, act, out_dtype)
 
 
 def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None, transpose: bool = False,
-                   stride=1, act=None) -> torch.Tensor:
+                   stride=1, act=None, out_dtype=None) -> torch.Tensor:
     """``F.conv2d(x, W[:, :, None, None], bias, stride=stride)`` with ``W = p.dequantize()``
     (``transpose``: its transpose) computed from the codes: ``x [n, K, H, W] -> [n, M, H', W']``.
-    The stride sub-samples ``x`` (a 1x1 kernel without padding commutes with it). Inference only."""
+    The stride sub-samples ``x`` (a 1x1 kernel without padding commutes with it). A bfloat16 / float16 ``x``
+    gives a result of its dtype (float32 with ``out_dtype=torch.float32``), as ``packed_gemm``. Inference only."""
     M, K = _weight_dims(p, transpose)
     if isinstance(x, torch.Tensor) and x.dim() != 4:
         raise ValueError(f"packed_conv1x1: x must be [n, {K}, H, W], got {tuple(x.shape)}")
     sh, sw = (stride, stride) if isinstance(stride, int) else tuple(stride)
     if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
         x = x[:, :, ::sh, ::sw]
-    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias, act)
+    return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias, act, out_dtype)
 
 
 # --- integer route (DESIGN.md 2.25) -------------------------------------------------------------
@@ -926,13 +1002,26 @@ def _lowrank_dims(p: "PackedLowRank") -> Tuple[int, int, int]:
 
 
 def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
-                  x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  x: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
     """``y = x (D + L Rt)^T (+ bias)`` with ``D`` the ``[M, K]`` de-quantization of ``codes``, ``L [M, r]`` and
     ``Rt [r, K]`` float32 (``admmq_packed_lrgemm``): ``x [..., K] -> [..., M]``. Neither ``D`` nor ``L Rt`` is
-    written to memory. Inference only: an ``x`` that requires grad is refused while grad mode is on."""
+    written to memory. A bfloat16 / float16 ``x`` is a composition, not a fused kernel:
+    ``(packed_gemm(x, out float32) + (x.float() @ Rt.float().T) @ L.float().T + bias)`` converted once to ``x``'s
+    dtype (or kept float32 with ``out_dtype=torch.float32``); ``L`` / ``Rt`` / ``bias`` may then be of ``x``'s dtype
+    (a module after ``.half()``). Inference only: an ``x`` that requires grad is refused while grad mode is on."""
     if not isinstance(x, torch.Tensor) or any(t.device.type != "cuda" for t in (x, codes, L, Rt)):
         raise RuntimeError("admmq: packed_lrgemm needs its codes, factors and activations on a ROCm GPU (device 'cuda'); "
                            "the MI355X path has no CPU implementation")
+    if x.dtype in HALF_DTYPES:
+        if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+            raise ValueError(f"packed_lrgemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+        y = packed_gemm(codes, meta_words, False, M, K, x, 1, None, None, torch.float32)
+        y = y + (x.detach().float() @ Rt.detach().float().T) @ L.detach().float().T
+        if bias is not None:
+            y = y + bias.detach().float()
+        return y if out_dtype == torch.float32 else y.to(x.dtype)
+    if out_dtype is not None and out_dtype != torch.float32:
+        raise ValueError(f"packed_lrgemm: a float32 x gives a float32 result, not out_dtype={out_dtype}")
     _lib.require_device(x)
     if x.requires_grad and torch.is_grad_enabled():
         raise RuntimeError("admmq: packed_lrgemm is inference only (no backward through packed weights): call it "
@@ -978,11 +1067,13 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
 _opaque_packed_lrgemm = torch.compiler.disable(packed_lrgemm)
 
 
-def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[torch.Tensor] = None,
+                          out_dtype=None) -> torch.Tensor:
     """``F.linear(x, W_q + L Rt, bias)`` computed from ``p``'s codes and factors in one GEMM: ``x [..., K] ->
-    [..., M]``. Inference only."""
+    [..., M]``. A bfloat16 / float16 ``x`` runs ``packed_lrgemm``'s composition (the half packed GEMM plus two
+    library products in float32; not a fused kernel). Inference only."""
     M, K, _ = _lowrank_dims(p)
-    return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias)
+    return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
 
 
 def save_packed_lowrank(path: str, p: "PackedLowRank") -> None:

@@ -9,6 +9,7 @@
 //   admmq::quantize_packed / dequantize_packed: the packed integer codes of the tensor schemes
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::packed_gemm             a packed weight times float32 activations
+//   admmq::packed_hgemm            a packed weight times bfloat16 / float16 activations
 //   admmq::packed_lrgemm           packed codes + low-rank factors times float32 activations, one GEMM
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
@@ -696,6 +697,63 @@ at::Tensor packed_gemm_meta(const at::Tensor& codes, const at::Tensor& meta_word
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
 }
 
+// --- packed_hgemm ---------------------------------------------------------------------------
+// packed_gemm on bfloat16 / float16 activations (admmq_packed_hgemm): the result
+// has x's dtype, or float32 with out_f32. bias: float32. Inference only.
+at::Tensor packed_hgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                             const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias, bool out_f32) {
+  TORCH_CHECK(x.is_cuda(), "admmq: x must live on a ROCm GPU (the MI355X path has no CPU implementation)");
+  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16,
+              "admmq: packed_hgemm: x must be float16 or bfloat16, got ", x.scalar_type());
+  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
+              "admmq: packed_gemm is inference only (no backward through packed weights): call it under "
+              "torch.no_grad() or detach x");
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
+              "admmq: packed_hgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_same_device(codes, x, "codes");
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
+              "admmq: packed_hgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
+  admmq_qmeta meta;
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_hgemm: bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_hgemm: a ", M,
+              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
+              " code bytes, got ", codes.numel());
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  at::Tensor cc = codes.contiguous();
+  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
+  at::Tensor bc;
+  if (bias.has_value() && bias->defined()) {
+    check_f32_device(*bias, "bias");
+    check_same_device(*bias, x, "bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_hgemm: bias must be [", M, "], got ", bias->sizes());
+    bc = bias->contiguous();
+  }
+  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
+  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
+  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_hgemm: empty x");
+  const int32_t xdt = x.scalar_type() == at::kHalf ? ADMMQ_DT_F16 : ADMMQ_DT_BF16;
+  at::Tensor y = at::empty(oshape, out_f32 ? xc.options().dtype(at::kFloat) : xc.options());
+  const size_t nbytes = admmq_packed_hgemm_workspace_size(&meta, M, K, N, static_cast<int32_t>(nb));
+  at::Tensor ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_hgemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr(), xdt,
+                              static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
+                              bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr(), out_f32 ? ADMMQ_DT_F32 : xdt,
+                              ws.data_ptr(), ws.numel(), stream_of(xc)),
+           "packed_hgemm");
+  return y;
+}
+
+at::Tensor packed_hgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                             const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias, bool out_f32) {
+  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16,
+              "admmq: packed_hgemm: x must be float16 or bfloat16, got ", x.scalar_type());
+  return at::empty(packed_gemm_shape(x, M, K, x_layout), out_f32 ? x.options().dtype(at::kFloat) : x.options());
+}
+
 // --- packed_lrgemm --------------------------------------------------------------------------
 // y = x (D + L Rt)^T (+ bias): D the [M, K] de-quantization of `codes`, L [M, r], Rt [r, K]
 // (admmq_packed_lrgemm). x [..., K] -> [..., M]. Inference only.
@@ -1007,6 +1065,8 @@ TORCH_LIBRARY(admmq, m) {
   m.def("dequantize_packed(Tensor[] codes, Tensor meta, int[] numel) -> Tensor[]");
   m.def("packed_gemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
         "Tensor? bias=None) -> Tensor");
+  m.def("packed_hgemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
+        "Tensor? bias=None, bool out_f32=False) -> Tensor");
   m.def("packed_lrgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor x, Tensor? bias=None) "
         "-> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
@@ -1040,6 +1100,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("quantize_packed", &quantize_packed_cuda);
   m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("packed_gemm", &packed_gemm_cuda);
+  m.impl("packed_hgemm", &packed_hgemm_cuda);
   m.impl("packed_lrgemm", &packed_lrgemm_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
@@ -1062,6 +1123,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("quantize_packed", &quantize_packed_meta);
   m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("packed_gemm", &packed_gemm_meta);
+  m.impl("packed_hgemm", &packed_hgemm_meta);
   m.impl("packed_lrgemm", &packed_lrgemm_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);

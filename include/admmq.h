@@ -430,6 +430,43 @@ int32_t admmq_packed_lrgemm(const uint8_t* codes, const admmq_qmeta* meta, int64
                             const float* Rt, int32_t r, const float* x, int64_t N, const float* bias, float* y,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* Half-precision packed GEMM: admmq_packed_gemm's product on bfloat16 or
+ * float16 activations, on v_mfma_f32_32x32x16_{bf16,f16}. Shapes, trans_w, the two x layouts,
+ * the code stream and the HOST meta record are admmq_packed_gemm's. x_dtype is ADMMQ_DT_F16 or
+ * ADMMQ_DT_BF16; y_dtype is ADMMQ_DT_F32 or x_dtype; bias (may be NULL) is float32.
+ * Arithmetic, with kp = max(64, 32 ceil(K/1024)) and np = ceil(K/kp) (admmq_packed_gemm's K
+ * pieces): the weight enters the MFMA as an exact integer half value and its scale is applied
+ * in float32 behind the sum.
+ *   mse-minmax, symmetric, affine: a = (u - q) - zero_point (q = 2^(bits-1); zero_point 0
+ *   unless affine)
+ *     S = ((s_0 + s_1) + ...) + s_{np-1},  s_p = the MFMA accumulator chain of piece p from zero
+ *     over a[m, k] x[k, c];  y32 = (S * scale) + bias[m]
+ *   tensor_minmax (bits >= 2): the operand is u (0 .. 255)
+ *     y32 = ((S_u * rng) / n + mn * S_x) + bias[m],  n = float(2^bits - 1)
+ *     with S_x the column's sum of x formed like S_u, against an operand of ones.
+ * Every operation above is a separately rounded float32 one. y is y32, or y32 rounded once to
+ * nearest even to x_dtype. An output depends on its own column of x, on K and on the weight
+ * only: the same bits for every N and nb and on every call; no atomics. Half subnormal inputs
+ * are outside the contract.
+ * codes: device, 16-byte aligned; x and y: device, aligned to their element (2 or 4 bytes) - no
+ * wider alignment is needed; bias: float aligned. Limits: admmq_packed_gemm's. ADMMQ_ERR_ARG
+ * for NULL codes / meta / x / y, non-positive sizes or sizes past the limits, what
+ * admmq_packed_gemm refuses of a meta record, an affine record whose -q - zero_point or
+ * q - 1 - zero_point is not an integer exact in x_dtype (magnitude above 256 for bfloat16, 2048
+ * for float16), x_layout 1 with nb != 1, a dtype pair other than the above, misaligned
+ * pointers; ADMMQ_ERR_WORKSPACE for a short workspace - all before any launch.
+ * admmq_packed_hgemm_workspace_size depends on its arguments only (of meta: the scheme): 0 for
+ * a NULL meta or sizes out of range, else admmq_packed_gemm_workspace_size(M, K, N, nb), plus,
+ * for tensor_minmax where that size is positive, 4 np nb N bytes (the pieces' sums of x). */
+#define ADMMQ_DT_F32 0
+#define ADMMQ_DT_F16 1
+#define ADMMQ_DT_BF16 2
+size_t admmq_packed_hgemm_workspace_size(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int32_t nb);
+int32_t admmq_packed_hgemm(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                           const void* x, int32_t x_dtype, int32_t x_layout, int64_t N, int32_t nb,
+                           const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

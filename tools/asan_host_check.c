@@ -216,6 +216,62 @@ int main(void) {
       fails += LR(c, &qm, 1024, 134, lf, rt, 8, x, 1024, y, NULL, 0) != ADMMQ_ERR_WORKSPACE;
 #undef LR
     }
+    /* the half-precision GEMM: the float GEMM's workspace, plus 4 np nb N bytes for tensor_minmax where
+     * that is positive, and every refusal before any launch */
+    {
+      admmq_qmeta qx = qm;
+      qx.scheme = ADMMQ_TENSOR_MINMAX;
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, 6000), K = rnd(1, 6000), N = rnd(1, t % 3 ? 70 : 4000);
+        const int32_t nb = rnd(1, 4);
+        const size_t w = admmq_packed_gemm_workspace_size(M, K, N, nb);
+        const int64_t kp = K > 2048 ? 32 * ((K + 1023) / 1024) : 64;
+        fails += admmq_packed_hgemm_workspace_size(&qm, M, K, N, nb) != w;
+        fails += admmq_packed_hgemm_workspace_size(&qx, M, K, N, nb) != (w ? w + (size_t)4 * ((K + kp - 1) / kp) * nb * N : 0);
+      }
+      fails += admmq_packed_hgemm_workspace_size(NULL, 8, 65, 4, 1) != 0;
+      fails += admmq_packed_hgemm_workspace_size(&qm, 0, 8, 8, 1) != 0;
+      fails += admmq_packed_hgemm_workspace_size(&qm, 8, 8, -1, 1) != 0;
+      fails += admmq_packed_hgemm_workspace_size(&qm, (int64_t)1 << 40, 8, 8, 1) != 0;
+      fails += admmq_packed_hgemm_workspace_size(&qx, 8, 65, 4, 1) != 2 * 4 * 8 * 4 + 2 * 4 * 4;
+#define HG(cc, mm, tr, M, K, xx, xd, xl, N, nb, bb, yy, yd, wsp, wsb) \
+  admmq_packed_hgemm(cc, mm, tr, M, K, xx, xd, xl, N, nb, bb, yy, yd, wsp, wsb, NULL)
+      const void* hx = (const void*)0x10000;
+      void* hy = (void*)0x20000;
+      const int32_t BF = ADMMQ_DT_BF16, HF = ADMMQ_DT_F16, F32 = ADMMQ_DT_F32;
+      fails += HG(NULL, &qm, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, NULL, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, NULL, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 0, 4, 1, NULL, NULL, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 0, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 0, -4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 2, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 2, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 1, 4, 2, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, F32, 0, 4, 1, NULL, hy, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, 3, 0, 4, 1, NULL, hy, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, HF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c + 4, &qm, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, (const void*)0x10001, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 0, 4, 1, NULL, (void*)0x20001, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 0, 4, 1, NULL, (void*)0x20002, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 8, 8, hx, BF, 0, 4, 1, (const float*)0x30002, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bits = 9;
+      fails += HG(c, &q2, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_MINMAX; q2.bits = 1;
+      fails += HG(c, &q2, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 3;
+      fails += HG(c, &q2, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 200;
+      fails += HG(c, &q2, 0, 8, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2.zero_point = -3000;
+      fails += HG(c, &q2, 0, 8, 8, hx, HF, 0, 4, 1, NULL, hy, HF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, (int64_t)1 << 30, 8, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HG(c, &qm, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += HG(c, &qm, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+      fails += HG(c, &qx, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 18 * 512 * 4 * 4) != ADMMQ_ERR_WORKSPACE;
+#undef HG
+    }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
     const float* tp = (const float*)0x18000;
