@@ -226,6 +226,97 @@ def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
 HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}   # ADMMQ_DT_F16 / ADMMQ_DT_BF16 (include/admmq.h)
 
 
+# --- the call frame of the packed GEMM wrappers ---------------------------------
+# Plain functions on tensor metadata, shared by the ctypes route of the six wrappers below. None of
+# them looks at the device, and each raises what the wrapper it was cut from raised, in that
+# wrapper's order.
+def _require_gpu(who: str, names: str, x, *others) -> None:
+    """The device refusal of wrapper ``who``: ``x`` (which need not be a tensor) and ``others`` on the GPU."""
+    ok = isinstance(x, torch.Tensor) and x.device.type == "cuda"
+    for t in others:
+        ok = ok and t.device.type == "cuda"
+    if not ok:
+        raise RuntimeError(f"admmq: {who} needs its {names} on a ROCm GPU (device 'cuda'); "
+                           "the MI355X path has no CPU implementation")
+
+
+def _inference_only(who: str, t: torch.Tensor, name: str) -> None:
+    """The refusal of a ``t`` (called ``name``) that requires grad while grad mode is on."""
+    if t.requires_grad and torch.is_grad_enabled():
+        raise RuntimeError(f"admmq: {who} is inference only (no backward through packed weights): call it "
+                           f"under torch.no_grad() or detach {name}")
+
+
+def _gemm_geometry(who: str, x: torch.Tensor, M: int, K: int, x_layout: int):
+    """``(oshape, nb, N, xc)`` of a GEMM on ``x``: layout 0 ``[nb, K, ...] -> [nb, M, ...]``, layout 1
+    ``[..., K] -> [..., M]`` (``nb`` 1); ``N`` columns per batch entry, ``xc`` the contiguous ``x``."""
+    if x_layout == 0:
+        if x.dim() < 3 or x.shape[1] != K:
+            raise ValueError(f"{who}: x must be [n, {K}, ...], got {tuple(x.shape)}")
+        oshape = (x.shape[0], M) + tuple(x.shape[2:])
+        nb = int(x.shape[0])
+    elif x_layout == 1:
+        if x.dim() < 1 or x.shape[-1] != K:
+            raise ValueError(f"{who}: x must be [..., {K}], got {tuple(x.shape)}")
+        oshape = tuple(x.shape[:-1]) + (M,)
+        nb = 1
+    else:
+        raise ValueError(f"{who}: x_layout must be 0 or 1")
+    xc = x.contiguous()
+    if xc.numel() == 0:
+        raise ValueError(f"{who}: empty x")
+    return oshape, nb, xc.numel() // (nb * K), xc
+
+
+def _dw_x_shape(who: str, x: torch.Tensor, K: int) -> None:
+    """The shape refusal of a fused depthwise + 1x1 call's ``x``. Apart from ``_dw_geometry``: both
+    depthwise wrappers check their tap tensor between this and the empty-x refusal."""
+    if x.dim() != 4 or x.shape[1] != K:
+        raise ValueError(f"{who}: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+
+
+def _dw_geometry(who: str, x: torch.Tensor, ks, st, pd):
+    """``(nb, H, W, Ho, Wo, xc)`` of a fused depthwise + 1x1 call on a checked ``x [nb, K, H, W]``. A
+    geometry outside the limits leaves ``Ho`` / ``Wo`` meaningless: the C call refuses it before any launch."""
+    xc = x.contiguous()
+    if xc.numel() == 0:
+        raise ValueError(f"{who}: empty x")
+    nb, H, W = int(xc.shape[0]), int(xc.shape[2]), int(xc.shape[3])
+    Ho = max((H + 2 * pd[0] - ks[0]) // max(st[0], 1) + 1, 1)
+    Wo = max((W + 2 * pd[1] - ks[1]) // max(st[1], 1) + 1, 1)
+    return nb, H, W, Ho, Wo, xc
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """``t`` contiguous at a 16-byte aligned address (a view into a larger buffer is cloned)."""
+    tc = t.contiguous()
+    return tc.clone() if tc.data_ptr() % 16 else tc
+
+
+def _weight_arg(codes: torch.Tensor, meta_words: torch.Tensor):
+    """The aligned code stream and the C meta record of a packed weight."""
+    return _aligned(codes), _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+
+
+def _bias_arg(who: str, bias: Optional[torch.Tensor], M: int) -> Optional[torch.Tensor]:
+    """``None`` or the contiguous float32 ``bias [M]`` on the GPU."""
+    if bias is None:
+        return None
+    _lib.require_device(bias)
+    if tuple(bias.shape) != (M,):
+        raise ValueError(f"{who}: bias must be [{M}], got {tuple(bias.shape)}")
+    return bias.contiguous()
+
+
+def _actq(t3) -> Optional["_lib.ActQ"]:
+    """The C record of a checked quantizer ``(bits, mn, rng)``; bits 0 (none): ``None``."""
+    return _lib.ActQ(t3[0], 1, t3[1], t3[2]) if t3[0] else None
+
+
+def _byref(rec):
+    return ctypes.byref(rec) if rec is not None else None
+
+
 def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int, x: torch.Tensor,
                 x_layout: int, bias: Optional[torch.Tensor] = None, act=None, out_dtype=None) -> torch.Tensor:
     """``Y = W X (+ bias)`` with ``W`` the ``[M, K]`` de-quantization of ``codes`` (``transpose``: of the
@@ -237,17 +328,13 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
     (``admmq_packed_hgemm``): the result has ``x``'s dtype, or float32 with
     ``out_dtype=torch.float32``; ``bias`` may be float32 or of ``x``'s dtype; ``act`` is not available
     there. Inference only: an ``x`` that requires grad is refused while grad mode is on."""
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda":
-        raise RuntimeError("admmq: packed_gemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
-                           "the MI355X path has no CPU implementation")
+    _require_gpu("packed_gemm", "codes and activations", x, codes)
     if x.dtype in HALF_DTYPES:
         return _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, out_dtype)
     _lib.require_device(x)
     if out_dtype is not None and out_dtype != torch.float32:
         raise ValueError(f"packed_gemm: a float32 x gives a float32 result, not out_dtype={out_dtype}")
-    if x.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
-                           "under torch.no_grad() or detach x")
+    _inference_only("packed_gemm", x, "x")
     if torch.compiler.is_compiling():   # (see _opaque_packed_gemm below)
         return _opaque_packed_gemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act)
     M, K, x_layout = int(M), int(K), int(x_layout)
@@ -259,35 +346,10 @@ def packed_gemm(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, 
     if _lib.use_ops():   # torch.ops.admmq.packed_gemm (csrc/torch_ops.cpp) -> admmq_packed_gemm
         return _lib.ops().packed_gemm(codes, meta_words, bool(transpose), M, K, x, x_layout, bias)
     lib = _lib.load()
-    if x_layout == 0:
-        if x.dim() < 3 or x.shape[1] != K:
-            raise ValueError(f"packed_gemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
-        oshape = (x.shape[0], M) + tuple(x.shape[2:])
-        nb = int(x.shape[0])
-    elif x_layout == 1:
-        if x.dim() < 1 or x.shape[-1] != K:
-            raise ValueError(f"packed_gemm: x must be [..., {K}], got {tuple(x.shape)}")
-        oshape = tuple(x.shape[:-1]) + (M,)
-        nb = 1
-    else:
-        raise ValueError("packed_gemm: x_layout must be 0 or 1")
-    xc = x.contiguous()
-    if xc.numel() == 0:
-        raise ValueError("packed_gemm: empty x")
-    N = xc.numel() // (nb * K)
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-    bc = None
-    if bias is not None:
-        _lib.require_device(bias)
-        if tuple(bias.shape) != (M,):
-            raise ValueError(f"packed_gemm: bias must be [{M}], got {tuple(bias.shape)}")
-        bc = bias.contiguous()
+    oshape, nb, N, xc = _gemm_geometry("packed_gemm", x, M, K, x_layout)
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_gemm", bias, M)
     y = torch.empty(oshape, dtype=torch.float32, device=x.device)
-    nbytes = lib.admmq_packed_gemm_workspace_size(M, K, N, nb)
-    ws = _lib.workspace(nbytes, x.device)
+    ws = _lib.workspace(lib.admmq_packed_gemm_workspace_size(M, K, N, nb), x.device)
     if oq is not None:
         rc = lib.admmq_packed_gemm_act(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc),
                                        x_layout, N, nb, _lib.ptr(bc), _lib.ptr(y), ctypes.byref(oq), _lib.ptr(ws),
@@ -323,9 +385,7 @@ def _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, ou
                          "float32 activations")
     if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
         raise ValueError(f"packed_gemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
-    if x.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("admmq: packed_gemm is inference only (no backward through packed weights): call it "
-                           "under torch.no_grad() or detach x")
+    _inference_only("packed_gemm", x, "x")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like the float32 call
         return _opaque_packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, out_dtype)
     M, K, x_layout = int(M), int(K), int(x_layout)
@@ -342,35 +402,11 @@ def _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, ou
     if _lib.use_ops():   # torch.ops.admmq.packed_hgemm (csrc/torch_ops.cpp) -> admmq_packed_hgemm
         return _lib.ops().packed_hgemm(codes, meta_words, bool(transpose), M, K, x, x_layout, bias, out_f32)
     lib = _lib.load()
-    if x_layout == 0:
-        if x.dim() < 3 or x.shape[1] != K:
-            raise ValueError(f"packed_gemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
-        oshape = (x.shape[0], M) + tuple(x.shape[2:])
-        nb = int(x.shape[0])
-    elif x_layout == 1:
-        if x.dim() < 1 or x.shape[-1] != K:
-            raise ValueError(f"packed_gemm: x must be [..., {K}], got {tuple(x.shape)}")
-        oshape = tuple(x.shape[:-1]) + (M,)
-        nb = 1
-    else:
-        raise ValueError("packed_gemm: x_layout must be 0 or 1")
-    xc = x.detach().contiguous()
-    if xc.numel() == 0:
-        raise ValueError("packed_gemm: empty x")
-    N = xc.numel() // (nb * K)
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-    bc = None
-    if bias is not None:
-        if tuple(bias.shape) != (M,):
-            raise ValueError(f"packed_gemm: bias must be [{M}], got {tuple(bias.shape)}")
-        bc = bias.contiguous()
+    oshape, nb, N, xc = _gemm_geometry("packed_gemm", x, M, K, x_layout)
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_gemm", bias, M)
     xdt = HALF_DTYPES[x.dtype]
     y = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
-    nbytes = lib.admmq_packed_hgemm_workspace_size(ctypes.byref(meta), M, K, N, nb)
-    ws = _lib.workspace(nbytes, x.device)
+    ws = _lib.workspace(lib.admmq_packed_hgemm_workspace_size(ctypes.byref(meta), M, K, N, nb), x.device)
     rc = lib.admmq_packed_hgemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc), xdt,
                                 x_layout, N, nb, _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws),
                                 ws.numel(), _lib.stream_handle(x.device))
@@ -548,10 +584,7 @@ def packed_rowsums(p: "PackedTensor", transpose: bool = False) -> torch.Tensor:
 def _rowsums(codes, meta_words, transpose, M, K):
     if _lib.use_ops():
         return _lib.ops().packed_rowsums(codes, meta_words, transpose, M, K)
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    cc, meta = _weight_arg(codes, meta_words)
     A = torch.empty(M, dtype=torch.int32, device=cc.device)
     _lib.check(_lib.load().admmq_packed_rowsums(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(A),
                                                 _lib.stream_handle(cc.device)), "packed_rowsums")
@@ -600,9 +633,7 @@ def _igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o
     """The call behind ``packed_igemm`` on checked quantizers ``x3`` / ``o3 = (bits, mn, rng)``."""
     if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
         raise TypeError("packed_igemm: xq.codes must be a uint8 tensor")
-    if x.device.type != "cuda" or codes.device.type != "cuda":
-        raise RuntimeError("admmq: packed_igemm needs its codes and activations on a ROCm GPU (device 'cuda'); "
-                           "the MI355X path has no CPU implementation")
+    _require_gpu("packed_igemm", "codes and activations", x, codes)
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
         return _opaque_igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o3, out_codes)
     if bias is not None:
@@ -612,45 +643,18 @@ def _igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o
                                              x_layout, bias, o3[0], o3[1], o3[2], out_codes)
     else:
         lib = _lib.load()
-        if x_layout == 0:
-            if x.dim() < 3 or x.shape[1] != K:
-                raise ValueError(f"packed_igemm: x must be [n, {K}, ...], got {tuple(x.shape)}")
-            oshape = (x.shape[0], M) + tuple(x.shape[2:])
-            nb = int(x.shape[0])
-        elif x_layout == 1:
-            if x.dim() < 1 or x.shape[-1] != K:
-                raise ValueError(f"packed_igemm: x must be [..., {K}], got {tuple(x.shape)}")
-            oshape = tuple(x.shape[:-1]) + (M,)
-            nb = 1
-        else:
-            raise ValueError("packed_igemm: x_layout must be 0 or 1")
-        xc = x.contiguous()
-        if xc.numel() == 0:
-            raise ValueError("packed_igemm: empty x")
-        N = xc.numel() // (nb * K)
-        cc = codes.contiguous()
-        if cc.data_ptr() % 16:
-            cc = cc.clone()
-        meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-        bc = None
-        if bias is not None:
-            _lib.require_device(bias)
-            if tuple(bias.shape) != (M,):
-                raise ValueError(f"packed_igemm: bias must be [{M}], got {tuple(bias.shape)}")
-            bc = bias.contiguous()
+        oshape, nb, N, xc = _gemm_geometry("packed_igemm", x, M, K, x_layout)
+        (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_igemm", bias, M)
         if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
             raise ValueError(f"packed_igemm: rowsums must be int32 [{M}]")
-        xr = _lib.ActQ(x3[0], 1, x3[1], x3[2])
-        oq = _lib.ActQ(o3[0], 1, o3[1], o3[2]) if o3[0] else None
+        xr, oq = _actq(x3), _actq(o3)
         y = torch.empty(oshape, dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
         clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
-        nbytes = lib.admmq_packed_igemm_workspace_size(M, K, N, nb)
-        ws = _lib.workspace(nbytes, x.device)
+        ws = _lib.workspace(lib.admmq_packed_igemm_workspace_size(M, K, N, nb), x.device)
         rc = lib.admmq_packed_igemm(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc),
                                     ctypes.byref(xr), _lib.ptr(rowsums.contiguous()), x_layout, N, nb, _lib.ptr(bc),
                                     _lib.ptr(None if out_codes else y), _lib.ptr(y if out_codes else None),
-                                    ctypes.byref(oq) if oq is not None else None,
-                                    _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), ws.numel(),
+                                    _byref(oq), _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), ws.numel(),
                                     _lib.stream_handle(x.device))
         _lib.check(rc, "packed_igemm")
     if out_codes:
@@ -733,10 +737,7 @@ def packed_taps_int(C: "PackedTensor") -> torch.Tensor:
 def _taps_i8(codes, meta_words, ntaps, K):
     if _lib.use_ops():   # torch.ops.admmq.packed_taps_i8 (csrc/torch_ops.cpp) -> admmq_packed_taps_i8
         return _lib.ops().packed_taps_i8(codes, meta_words, ntaps, K)
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
+    cc, meta = _weight_arg(codes, meta_words)
     image = torch.empty((ntaps, taps_kp(K)), dtype=torch.int8, device=cc.device)
     _lib.check(_lib.load().admmq_packed_taps_i8(_lib.ptr(cc), ctypes.byref(meta), ntaps, K, _lib.ptr(image),
                                                 _lib.stream_handle(cc.device)), "packed_taps_i8")
@@ -749,12 +750,9 @@ def _idwgemm(codes, meta_words, M, K, x, x3, image, s_c, ks, st, pd, rowsums, bi
     empty without ``count_mid``: the count then costs nothing, not even its memset)."""
     if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
         raise TypeError("packed_idwgemm: xq.codes must be a uint8 tensor")
-    if bias is not None and bias.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("admmq: packed_idwgemm is inference only (no backward through packed weights): call it "
-                           "under torch.no_grad() or detach bias")
-    if x.device.type != "cuda" or codes.device.type != "cuda" or image.device.type != "cuda":
-        raise RuntimeError("admmq: packed_idwgemm needs its codes, tap image and activations on a ROCm GPU (device "
-                           "'cuda'); the MI355X path has no CPU implementation")
+    if bias is not None:
+        _inference_only("packed_idwgemm", bias, "bias")
+    _require_gpu("packed_idwgemm", "codes, tap image and activations", x, codes, image)
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_igemm
         return _opaque_idwgemm(codes, meta_words, M, K, x, x3, image, s_c, ks, st, pd, rowsums, bias, m3, o3, out_codes,
                                count_mid)
@@ -766,44 +764,24 @@ def _idwgemm(codes, meta_words, M, K, x, x3, image, s_c, ks, st, pd, rowsums, bi
                                          pw, rowsums, bias, m3[0], m3[1], m3[2], o3[0], o3[1], o3[2], out_codes,
                                          bool(count_mid))
     lib = _lib.load()
-    if x.dim() != 4 or x.shape[1] != K:
-        raise ValueError(f"packed_idwgemm: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    _dw_x_shape("packed_idwgemm", x, K)
     if image.dtype != torch.int8 or tuple(image.shape) != (kh * kw, taps_kp(K)):
         raise ValueError(f"packed_idwgemm: the tap image must be int8 [{kh * kw}, {taps_kp(K)}], got {image.dtype} "
                          f"{tuple(image.shape)}")
     if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
         raise ValueError(f"packed_idwgemm: rowsums must be int32 [{M}]")
-    xc, ic = x.contiguous(), image.contiguous()
-    if xc.numel() == 0:
-        raise ValueError("packed_idwgemm: empty x")
-    if ic.data_ptr() % 16:
-        ic = ic.clone()
-    nb, H, W = int(xc.shape[0]), int(xc.shape[2]), int(xc.shape[3])
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-    bc = None
-    if bias is not None:
-        _lib.require_device(bias)
-        if tuple(bias.shape) != (M,):
-            raise ValueError(f"packed_idwgemm: bias must be [{M}], got {tuple(bias.shape)}")
-        bc = bias.contiguous()
-    # (a geometry outside the limits leaves Ho / Wo meaningless: the call below refuses it before any launch)
-    Ho = max((H + 2 * ph - kh) // max(sh, 1) + 1, 1)
-    Wo = max((W + 2 * pw - kw) // max(sw, 1) + 1, 1)
-    xr, mr = _lib.ActQ(x3[0], 1, x3[1], x3[2]), _lib.ActQ(m3[0], 1, m3[1], m3[2])
-    oq = _lib.ActQ(o3[0], 1, o3[1], o3[2]) if o3[0] else None
+    nb, H, W, Ho, Wo, xc = _dw_geometry("packed_idwgemm", x, ks, st, pd)
+    ic = _aligned(image)
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_idwgemm", bias, M)
+    xr, mr, oq = _actq(x3), _actq(m3), _actq(o3)
     y = torch.empty((nb, M, Ho, Wo), dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
     mid_clamped = torch.empty(1 if count_mid else 0, dtype=torch.int32, device=x.device)
     clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
-    nbytes = lib.admmq_packed_idwgemm_workspace_size(M, K, Ho, Wo, nb)
-    ws = _lib.workspace(nbytes, x.device)
+    ws = _lib.workspace(lib.admmq_packed_idwgemm_workspace_size(M, K, Ho, Wo, nb), x.device)
     rc = lib.admmq_packed_idwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), ctypes.byref(xr), nb, H, W,
                                   _lib.ptr(ic), s_c, kh, kw, sh, sw, ph, pw, _lib.ptr(rowsums.contiguous()), _lib.ptr(bc),
                                   _lib.ptr(None if out_codes else y), _lib.ptr(y if out_codes else None),
-                                  ctypes.byref(mr), ctypes.byref(oq) if oq is not None else None,
-                                  _lib.ptr(mid_clamped if count_mid else None),
+                                  ctypes.byref(mr), _byref(oq), _lib.ptr(mid_clamped if count_mid else None),
                                   _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), ws.numel(),
                                   _lib.stream_handle(x.device))
     _lib.check(rc, "packed_idwgemm")
@@ -856,19 +834,15 @@ def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     ``mid_act`` / ``act = (bits, min_val, max_val)``: fixed-range quantizers of the depthwise stage's
     output (applied as it is staged; padding stays 0) and of the result (``admmq_packed_dwgemm_act``).
     Inference only: an ``x`` that requires grad is refused while grad mode is on."""
-    if not isinstance(x, torch.Tensor) or x.device.type != "cuda" or codes.device.type != "cuda" or \
-            taps.device.type != "cuda":
-        raise RuntimeError("admmq: packed_dwgemm needs its codes, taps and activations on a ROCm GPU (device 'cuda'); "
-                           "the MI355X path has no CPU implementation")
+    _require_gpu("packed_dwgemm", "codes, taps and activations", x, codes, taps)
     _lib.require_device(x)
     _lib.require_device(taps)
-    if x.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("admmq: packed_dwgemm is inference only (no backward through packed weights): call it "
-                           "under torch.no_grad() or detach x")
+    _inference_only("packed_dwgemm", x, "x")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
         return _opaque_packed_dwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act)
     M, K = int(M), int(K)
-    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
+    ks, st, pd = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
+    (kh, kw), (sh, sw), (ph, pw) = ks, st, pd
     taps = taps.detach()
     if bias is not None:
         bias = bias.detach()
@@ -880,36 +854,18 @@ def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     if _lib.use_ops():   # torch.ops.admmq.packed_dwgemm (csrc/torch_ops.cpp) -> admmq_packed_dwgemm
         return _lib.ops().packed_dwgemm(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias)
     lib = _lib.load()
-    if x.dim() != 4 or x.shape[1] != K:
-        raise ValueError(f"packed_dwgemm: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    _dw_x_shape("packed_dwgemm", x, K)
     if tuple(taps.shape) != (kh * kw, K):
         raise ValueError(f"packed_dwgemm: taps must be [{kh * kw}, {K}], got {tuple(taps.shape)}")
-    xc, tc = x.contiguous(), taps.contiguous()
-    if xc.numel() == 0:
-        raise ValueError("packed_dwgemm: empty x")
-    nb, H, W = int(xc.shape[0]), int(xc.shape[2]), int(xc.shape[3])
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-    bc = None
-    if bias is not None:
-        _lib.require_device(bias)
-        if tuple(bias.shape) != (M,):
-            raise ValueError(f"packed_dwgemm: bias must be [{M}], got {tuple(bias.shape)}")
-        bc = bias.contiguous()
-    # (a geometry outside the limits leaves Ho / Wo meaningless: the call below refuses it before any launch)
-    Ho = max((H + 2 * ph - kh) // max(sh, 1) + 1, 1)
-    Wo = max((W + 2 * pw - kw) // max(sw, 1) + 1, 1)
+    nb, H, W, Ho, Wo, xc = _dw_geometry("packed_dwgemm", x, ks, st, pd)
+    tc = taps.contiguous()
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_dwgemm", bias, M)
     y = torch.empty((nb, M, Ho, Wo), dtype=torch.float32, device=x.device)
-    nbytes = lib.admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb)
-    ws = _lib.workspace(nbytes, x.device)
+    ws = _lib.workspace(lib.admmq_packed_dwgemm_workspace_size(M, K, Ho, Wo, nb), x.device)
     if oq is not None or mq is not None:
         rc = lib.admmq_packed_dwgemm_act(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), nb, H, W, _lib.ptr(tc), kh,
-                                         kw, sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y),
-                                         ctypes.byref(mq) if mq is not None else None,
-                                         ctypes.byref(oq) if oq is not None else None, _lib.ptr(ws), ws.numel(),
-                                         _lib.stream_handle(x.device))
+                                         kw, sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y), _byref(mq), _byref(oq),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
         _lib.check(rc, "packed_dwgemm_act")
         return y
     rc = lib.admmq_packed_dwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), nb, H, W, _lib.ptr(tc), kh, kw,
@@ -1009,9 +965,7 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     ``(packed_gemm(x, out float32) + (x.float() @ Rt.float().T) @ L.float().T + bias)`` converted once to ``x``'s
     dtype (or kept float32 with ``out_dtype=torch.float32``); ``L`` / ``Rt`` / ``bias`` may then be of ``x``'s dtype
     (a module after ``.half()``). Inference only: an ``x`` that requires grad is refused while grad mode is on."""
-    if not isinstance(x, torch.Tensor) or any(t.device.type != "cuda" for t in (x, codes, L, Rt)):
-        raise RuntimeError("admmq: packed_lrgemm needs its codes, factors and activations on a ROCm GPU (device 'cuda'); "
-                           "the MI355X path has no CPU implementation")
+    _require_gpu("packed_lrgemm", "codes, factors and activations", x, codes, L, Rt)
     if x.dtype in HALF_DTYPES:
         if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
             raise ValueError(f"packed_lrgemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
@@ -1023,9 +977,7 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     if out_dtype is not None and out_dtype != torch.float32:
         raise ValueError(f"packed_lrgemm: a float32 x gives a float32 result, not out_dtype={out_dtype}")
     _lib.require_device(x)
-    if x.requires_grad and torch.is_grad_enabled():
-        raise RuntimeError("admmq: packed_lrgemm is inference only (no backward through packed weights): call it "
-                           "under torch.no_grad() or detach x")
+    _inference_only("packed_lrgemm", x, "x")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
         return _opaque_packed_lrgemm(codes, meta_words, M, K, L, Rt, x, bias)
     M, K = int(M), int(K)
@@ -1039,25 +991,11 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
     _lib.require_device(Rt)
     if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
         raise ValueError(f"packed_lrgemm: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
-    if x.dim() < 1 or x.shape[-1] != K:
-        raise ValueError(f"packed_lrgemm: x must be [..., {K}], got {tuple(x.shape)}")
-    xc, Lc, Rc = x.contiguous(), L.contiguous(), Rt.contiguous()
-    if xc.numel() == 0:
-        raise ValueError("packed_lrgemm: empty x")
-    N, r = xc.numel() // K, int(Lc.shape[1])
-    cc = codes.contiguous()
-    if cc.data_ptr() % 16:
-        cc = cc.clone()
-    meta = _lib.QMeta.from_buffer_copy(meta_words.contiguous().numpy().tobytes())
-    bc = None
-    if bias is not None:
-        _lib.require_device(bias)
-        if tuple(bias.shape) != (M,):
-            raise ValueError(f"packed_lrgemm: bias must be [{M}], got {tuple(bias.shape)}")
-        bc = bias.contiguous()
-    y = torch.empty(tuple(x.shape[:-1]) + (M,), dtype=torch.float32, device=x.device)
-    nbytes = lib.admmq_packed_lrgemm_workspace_size(M, K, N, r)
-    ws = _lib.workspace(nbytes, x.device)
+    oshape, _, N, xc = _gemm_geometry("packed_lrgemm", x, M, K, 1)
+    Lc, Rc, r = L.contiguous(), Rt.contiguous(), int(L.shape[1])
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_lrgemm", bias, M)
+    y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+    ws = _lib.workspace(lib.admmq_packed_lrgemm_workspace_size(M, K, N, r), x.device)
     rc = lib.admmq_packed_lrgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), r, _lib.ptr(xc), N,
                                  _lib.ptr(bc), _lib.ptr(y), _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
     _lib.check(rc, "packed_lrgemm")

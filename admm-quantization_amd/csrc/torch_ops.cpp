@@ -334,55 +334,91 @@ admmq_actq actq_of(int64_t bits, double mn, double rng, const char* what) {
   return q;
 }
 
+// --- the call frame of the packed GEMM ops -------------------------------------
+// The checks and the setup that the six packed GEMM ops share. Each piece raises under the name `who`
+// of the op that calls it; the pieces are apart where the ops order them differently.
+void check_inference_only(bool requires_grad, const char* who, const char* name) {
+  TORCH_CHECK(!(requires_grad && at::GradMode::is_enabled()), "admmq: ", who,
+              " is inference only (no backward through packed weights): call it under torch.no_grad() or detach ", name);
+}
+
+void check_codes(const at::Tensor& codes, const char* who) {
+  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1, "admmq: ", who,
+              ": codes must be a 1-D uint8 tensor on the GPU");
+}
+
+void check_meta_words(const at::Tensor& meta_words, const char* who) {
+  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8, "admmq: ",
+              who, ": meta_words must be the 8 int32 words of the meta record on the CPU");
+}
+
+// t contiguous at a 16-byte aligned address (a view into a larger buffer is cloned)
+at::Tensor aligned16(const at::Tensor& t) {
+  at::Tensor tc = t.contiguous();
+  if ((reinterpret_cast<uintptr_t>(tc.data_ptr()) & 15) != 0) tc = tc.clone();
+  return tc;
+}
+
+// the host meta record and the 16-byte aligned code stream of a checked [M, K] packed weight
+at::Tensor packed_weight_of(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const char* who,
+                            admmq_qmeta& meta) {
+  static_assert(sizeof(admmq_qmeta) == 32, "meta is int32 [8]");
+  const at::Tensor mw = meta_words.contiguous();
+  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
+  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: ", who, ": bits must be 1..8");
+  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: ", who, ": a ", M, " x ",
+              K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits), " code bytes, got ",
+              codes.numel());
+  return aligned16(codes);
+}
+
+// the contiguous float32 bias [M] on x's device, or an undefined tensor; refuse_grad: the integer
+// ops' inference-only refusal, which they make on the bias
+at::Tensor bias_of(const std::optional<at::Tensor>& bias, const at::Tensor& x, int64_t M, const char* who, bool refuse_grad) {
+  if (!bias.has_value() || !bias->defined()) return at::Tensor();
+  check_f32_device(*bias, "bias");
+  check_same_device(*bias, x, "bias");
+  if (refuse_grad) check_inference_only(bias->requires_grad(), who, "bias");
+  TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: ", who, ": bias must be [", M, "], got ", bias->sizes());
+  return bias->contiguous();
+}
+
+const float* f32_or_null(const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; }
+
+// batch entries nb (x_layout 1: one) and columns N per entry of a GEMM on the contiguous xc
+std::pair<int32_t, int64_t> gemm_extent(const at::Tensor& xc, int64_t K, int64_t x_layout, const char* who) {
+  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
+  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
+  TORCH_CHECK(nb > 0 && N > 0, "admmq: ", who, ": empty x");
+  return {static_cast<int32_t>(nb), N};
+}
+
 at::Tensor packed_gemm_impl(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
                             const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
                             const admmq_actq* out_q) {
-  static_assert(sizeof(admmq_qmeta) == 32, "meta is int32 [8]");
   check_f32_device(x, "x");
-  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
-              "admmq: packed_gemm is inference only (no backward through packed weights): call it under "
-              "torch.no_grad() or detach x");
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
-              "admmq: packed_gemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_inference_only(x.requires_grad(), "packed_gemm", "x");
+  check_codes(codes, "packed_gemm");
   check_same_device(codes, x, "codes");
-  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
-              "admmq: packed_gemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  check_meta_words(meta_words, "packed_gemm");
   const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
   admmq_qmeta meta;
-  const at::Tensor mw = meta_words.contiguous();
-  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
-  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_gemm: bits must be 1..8");
-  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_gemm: a ", M,
-              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
-              " code bytes, got ", codes.numel());
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_gemm", meta);
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous();
-  at::Tensor cc = codes.contiguous();
-  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_gemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
-  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
-  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
-  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_gemm: empty x");
+  const at::Tensor bc = bias_of(bias, x, M, "packed_gemm", false);
+  const auto [nb, N] = gemm_extent(xc, K, x_layout, "packed_gemm");
   at::Tensor y = at::empty(oshape, xc.options());
-  const size_t nbytes = admmq_packed_gemm_workspace_size(M, K, N, static_cast<int32_t>(nb));
-  at::Tensor ws = workspace(nbytes, xc);
+  at::Tensor ws = workspace(admmq_packed_gemm_workspace_size(M, K, N, nb), xc);
   if (out_q) {
     check_rc(admmq_packed_gemm_act(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<float>(),
-                                   static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
-                                   bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(), out_q,
+                                   static_cast<int32_t>(x_layout), N, nb, f32_or_null(bc), y.data_ptr<float>(), out_q,
                                    ws.data_ptr(), ws.numel(), stream_of(xc)),
              "packed_gemm_act");
     return y;
   }
   check_rc(admmq_packed_gemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<float>(),
-                             static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
-                             bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(), ws.data_ptr(),
+                             static_cast<int32_t>(x_layout), N, nb, f32_or_null(bc), y.data_ptr<float>(), ws.data_ptr(),
                              ws.numel(), stream_of(xc)),
            "packed_gemm");
   return y;
@@ -477,28 +513,30 @@ at::Tensor act_decode_meta(const at::Tensor& codes, int64_t bits, double mn, dou
   return at::empty(codes.sizes(), codes.options().dtype(at::kFloat));
 }
 
-// the host meta record and the 16-byte aligned code stream of a packed weight
-at::Tensor packed_weight_of(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const char* what,
-                            admmq_qmeta& meta) {
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1, "admmq: ", what,
-              ": codes must be a 1-D uint8 tensor on the GPU");
-  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8, "admmq: ",
-              what, ": meta_words must be the 8 int32 words of the meta record on the CPU");
-  TORCH_CHECK(M > 0 && K > 0, "admmq: ", what, ": M and K must be positive");
-  const at::Tensor mw = meta_words.contiguous();
-  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
-  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: ", what, ": bits must be 1..8");
-  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: ", what, ": a ", M, " x ",
-              K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits), " code bytes, got ",
-              codes.numel());
-  at::Tensor cc = codes.contiguous();
-  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();
-  return cc;
+// packed_weight_of behind the integer ops' checks of its arguments (the float ops make theirs around
+// their device and shape checks)
+at::Tensor int_weight_of(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const char* who,
+                         admmq_qmeta& meta) {
+  check_codes(codes, who);
+  check_meta_words(meta_words, who);
+  TORCH_CHECK(M > 0 && K > 0, "admmq: ", who, ": M and K must be positive");
+  return packed_weight_of(codes, meta_words, M, K, who, meta);
+}
+
+// the output quantizer of an integer op: a code quantizer when the output is codes
+admmq_actq outq_of(bool out_codes, int64_t bits, double mn, double rng, const char* who) {
+  return out_codes ? codeq_of(bits, mn, rng, who) : actq_of(bits, mn, rng, who);
+}
+
+void check_rowsums(const at::Tensor& rowsums, const at::Tensor& x, int64_t M, const char* who) {
+  TORCH_CHECK(rowsums.is_cuda() && rowsums.scalar_type() == at::kInt && rowsums.dim() == 1 && rowsums.size(0) == M,
+              "admmq: ", who, ": rowsums must be an int32 [", M, "] tensor on the GPU");
+  check_same_device(rowsums, x, "rowsums");
 }
 
 at::Tensor packed_rowsums_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K) {
   admmq_qmeta meta;
-  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_rowsums", meta);
+  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, "packed_rowsums", meta);
   const c10::DeviceGuard guard(cc.device());
   at::Tensor A = at::empty({M}, cc.options().dtype(at::kInt));
   check_rc(admmq_packed_rowsums(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, A.data_ptr<int32_t>(), stream_of(cc)),
@@ -518,39 +556,25 @@ std::tuple<at::Tensor, at::Tensor> packed_igemm_cuda(const at::Tensor& codes, co
                                                      double out_rng, bool out_codes) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte, "admmq: packed_igemm: x must be a uint8 code tensor on the GPU");
   const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_igemm");
-  const admmq_actq oq = out_codes ? codeq_of(out_bits, out_mn, out_rng, "packed_igemm") : actq_of(out_bits, out_mn, out_rng, "packed_igemm");
+  const admmq_actq oq = outq_of(out_codes, out_bits, out_mn, out_rng, "packed_igemm");
   admmq_qmeta meta;
-  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_igemm", meta);
+  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, "packed_igemm", meta);
   check_same_device(codes, x, "codes");
-  TORCH_CHECK(rowsums.is_cuda() && rowsums.scalar_type() == at::kInt && rowsums.dim() == 1 && rowsums.size(0) == M,
-              "admmq: packed_igemm: rowsums must be an int32 [", M, "] tensor on the GPU");
-  check_same_device(rowsums, x, "rowsums");
+  check_rowsums(rowsums, x, M, "packed_igemm");
   const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous();
   const at::Tensor rc = rowsums.contiguous();
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(!(bias->requires_grad() && at::GradMode::is_enabled()),
-                "admmq: packed_igemm is inference only (no backward through packed weights): call it under "
-                "torch.no_grad() or detach bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_igemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
-  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
-  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
-  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_igemm: empty x");
+  const at::Tensor bc = bias_of(bias, x, M, "packed_igemm", true);
+  const auto [nb, N] = gemm_extent(xc, K, x_layout, "packed_igemm");
   at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
   at::Tensor clamped = at::empty({out_codes ? 1 : 0}, xc.options().dtype(at::kInt));
-  const size_t nbytes = admmq_packed_igemm_workspace_size(M, K, N, static_cast<int32_t>(nb));
+  const size_t nbytes = admmq_packed_igemm_workspace_size(M, K, N, nb);
   at::Tensor ws;   // (the serial regime needs none: no allocation)
   if (nbytes > 0) ws = workspace(nbytes, xc);
   check_rc(admmq_packed_igemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<uint8_t>(), &xq,
-                              rc.data_ptr<int32_t>(), static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
-                              bc.defined() ? bc.data_ptr<float>() : nullptr, out_codes ? nullptr : y.data_ptr<float>(),
-                              out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq,
+                              rc.data_ptr<int32_t>(), static_cast<int32_t>(x_layout), N, nb, f32_or_null(bc),
+                              out_codes ? nullptr : y.data_ptr<float>(), out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq,
                               out_codes ? clamped.data_ptr<int32_t>() : nullptr, nbytes > 0 ? ws.data_ptr() : nullptr,
                               nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
            "packed_igemm");
@@ -563,8 +587,7 @@ std::tuple<at::Tensor, at::Tensor> packed_igemm_meta(const at::Tensor& codes, co
                                                      const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
                                                      double out_rng, bool out_codes) {
   (void)codeq_of(x_bits, x_mn, x_rng, "packed_igemm");
-  if (out_codes) (void)codeq_of(out_bits, out_mn, out_rng, "packed_igemm");
-  else (void)actq_of(out_bits, out_mn, out_rng, "packed_igemm");
+  (void)outq_of(out_codes, out_bits, out_mn, out_rng, "packed_igemm");
   return {at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(out_codes ? at::kByte : at::kFloat)),
           at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
 }
@@ -602,7 +625,7 @@ std::vector<int64_t> packed_dw_shape(const char* who, const char* taps_name, int
 at::Tensor packed_taps_i8_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t ntaps, int64_t K) {
   TORCH_CHECK(ntaps >= 1 && ntaps <= 49, "admmq: packed_taps_i8: ntaps must be 1..49, got ", ntaps);
   admmq_qmeta meta;
-  const at::Tensor cc = packed_weight_of(codes, meta_words, ntaps, K, "packed_taps_i8", meta);
+  const at::Tensor cc = int_weight_of(codes, meta_words, ntaps, K, "packed_taps_i8", meta);
   const c10::DeviceGuard guard(cc.device());
   at::Tensor image = at::empty({ntaps, taps_kp(K)}, cc.options().dtype(at::kChar));
   check_rc(admmq_packed_taps_i8(cc.data_ptr<uint8_t>(), &meta, static_cast<int32_t>(ntaps), K, image.data_ptr<int8_t>(),
@@ -632,32 +655,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_cuda(
               "admmq: packed_idwgemm: taps_i8 must be an int8 tensor on the GPU (packed_taps_i8 makes it)");
   const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_idwgemm");
   const admmq_actq mq = codeq_of(mid_bits, mid_mn, mid_rng, "packed_idwgemm");
-  const admmq_actq oq = out_codes ? codeq_of(out_bits, out_mn, out_rng, "packed_idwgemm") : actq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
+  const admmq_actq oq = outq_of(out_codes, out_bits, out_mn, out_rng, "packed_idwgemm");
   admmq_qmeta meta;
-  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_idwgemm", meta);
+  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, "packed_idwgemm", meta);
   check_same_device(codes, x, "codes");
   check_same_device(taps_i8, x, "taps_i8");
-  TORCH_CHECK(rowsums.is_cuda() && rowsums.scalar_type() == at::kInt && rowsums.dim() == 1 && rowsums.size(0) == M,
-              "admmq: packed_idwgemm: rowsums must be an int32 [", M, "] tensor on the GPU");
-  check_same_device(rowsums, x, "rowsums");
+  check_rowsums(rowsums, x, M, "packed_idwgemm");
   const std::vector<int64_t> oshape = packed_idwgemm_shape(x, taps_i8, M, K, kh, kw, sh, sw, ph, pw);
   TORCH_CHECK(std::max(sh, sw) <= INT32_MAX && x.size(0) <= INT32_MAX, "admmq: packed_idwgemm: sizes out of range");
   TORCH_CHECK(x.numel() > 0, "admmq: packed_idwgemm: empty x");
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous();
   const at::Tensor rc = rowsums.contiguous();
-  at::Tensor tc = taps_i8.contiguous();
-  if ((reinterpret_cast<uintptr_t>(tc.data_ptr()) & 15) != 0) tc = tc.clone();   // (a view into a larger buffer)
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(!(bias->requires_grad() && at::GradMode::is_enabled()),
-                "admmq: packed_idwgemm is inference only (no backward through packed weights): call it under "
-                "torch.no_grad() or detach bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_idwgemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
+  const at::Tensor tc = aligned16(taps_i8);
+  const at::Tensor bc = bias_of(bias, x, M, "packed_idwgemm", true);
   const int32_t nb = static_cast<int32_t>(xc.size(0));
   at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
   at::Tensor mid_clamped = at::empty({count_mid ? 1 : 0}, xc.options().dtype(at::kInt));   // (not counted: no memset)
@@ -669,7 +680,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_cuda(
                                 tc.data_ptr<int8_t>(), static_cast<float>(s_c), static_cast<int32_t>(kh),
                                 static_cast<int32_t>(kw), static_cast<int32_t>(sh), static_cast<int32_t>(sw),
                                 static_cast<int32_t>(ph), static_cast<int32_t>(pw), rc.data_ptr<int32_t>(),
-                                bc.defined() ? bc.data_ptr<float>() : nullptr, out_codes ? nullptr : y.data_ptr<float>(),
+                                f32_or_null(bc), out_codes ? nullptr : y.data_ptr<float>(),
                                 out_codes ? y.data_ptr<uint8_t>() : nullptr, &mq, &oq, count_mid ? mid_clamped.data_ptr<int32_t>() : nullptr,
                                 out_codes ? clamped.data_ptr<int32_t>() : nullptr, nbytes > 0 ? ws.data_ptr() : nullptr,
                                 nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
@@ -684,8 +695,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> packed_idwgemm_meta(
     double mid_mn, double mid_rng, int64_t out_bits, double out_mn, double out_rng, bool out_codes, bool count_mid) {
   (void)codeq_of(x_bits, x_mn, x_rng, "packed_idwgemm");
   (void)codeq_of(mid_bits, mid_mn, mid_rng, "packed_idwgemm");
-  if (out_codes) (void)codeq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
-  else (void)actq_of(out_bits, out_mn, out_rng, "packed_idwgemm");
+  (void)outq_of(out_codes, out_bits, out_mn, out_rng, "packed_idwgemm");
   return {at::empty(packed_idwgemm_shape(x, taps_i8, M, K, kh, kw, sh, sw, ph, pw),
                     x.options().dtype(out_codes ? at::kByte : at::kFloat)),
           at::empty({count_mid ? 1 : 0}, x.options().dtype(at::kInt)),
@@ -705,44 +715,23 @@ at::Tensor packed_hgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_wor
   TORCH_CHECK(x.is_cuda(), "admmq: x must live on a ROCm GPU (the MI355X path has no CPU implementation)");
   TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16,
               "admmq: packed_hgemm: x must be float16 or bfloat16, got ", x.scalar_type());
-  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
-              "admmq: packed_gemm is inference only (no backward through packed weights): call it under "
-              "torch.no_grad() or detach x");
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
-              "admmq: packed_hgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_inference_only(x.requires_grad(), "packed_gemm", "x");
+  check_codes(codes, "packed_hgemm");
   check_same_device(codes, x, "codes");
-  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
-              "admmq: packed_hgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  check_meta_words(meta_words, "packed_hgemm");
   const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
   admmq_qmeta meta;
-  const at::Tensor mw = meta_words.contiguous();
-  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
-  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_hgemm: bits must be 1..8");
-  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_hgemm: a ", M,
-              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
-              " code bytes, got ", codes.numel());
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_hgemm", meta);
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous();
-  at::Tensor cc = codes.contiguous();
-  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_hgemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
-  const int64_t nb = x_layout == 0 ? xc.size(0) : 1;
-  const int64_t N = x_layout == 0 ? xc.numel() / std::max<int64_t>(nb * K, 1) : xc.numel() / K;
-  TORCH_CHECK(nb > 0 && N > 0, "admmq: packed_hgemm: empty x");
+  const at::Tensor bc = bias_of(bias, x, M, "packed_hgemm", false);
+  const auto [nb, N] = gemm_extent(xc, K, x_layout, "packed_hgemm");
   const int32_t xdt = x.scalar_type() == at::kHalf ? ADMMQ_DT_F16 : ADMMQ_DT_BF16;
   at::Tensor y = at::empty(oshape, out_f32 ? xc.options().dtype(at::kFloat) : xc.options());
-  const size_t nbytes = admmq_packed_hgemm_workspace_size(&meta, M, K, N, static_cast<int32_t>(nb));
-  at::Tensor ws = workspace(nbytes, xc);
+  at::Tensor ws = workspace(admmq_packed_hgemm_workspace_size(&meta, M, K, N, nb), xc);
   check_rc(admmq_packed_hgemm(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr(), xdt,
-                              static_cast<int32_t>(x_layout), N, static_cast<int32_t>(nb),
-                              bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr(), out_f32 ? ADMMQ_DT_F32 : xdt,
-                              ws.data_ptr(), ws.numel(), stream_of(xc)),
+                              static_cast<int32_t>(x_layout), N, nb, f32_or_null(bc), y.data_ptr(),
+                              out_f32 ? ADMMQ_DT_F32 : xdt, ws.data_ptr(), ws.numel(), stream_of(xc)),
            "packed_hgemm");
   return y;
 }
@@ -774,44 +763,25 @@ at::Tensor packed_lrgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_wo
   check_f32_device(x, "x");
   check_f32_device(L, "L");
   check_f32_device(Rt, "Rt");
-  TORCH_CHECK(!((x.requires_grad() || L.requires_grad() || Rt.requires_grad()) && at::GradMode::is_enabled()),
-              "admmq: packed_lrgemm is inference only (no backward through packed weights): call it under "
-              "torch.no_grad() or detach x");
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
-              "admmq: packed_lrgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_inference_only(x.requires_grad() || L.requires_grad() || Rt.requires_grad(), "packed_lrgemm", "x");
+  check_codes(codes, "packed_lrgemm");
   check_same_device(codes, x, "codes");
   check_same_device(L, x, "L");
   check_same_device(Rt, x, "Rt");
-  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
-              "admmq: packed_lrgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  check_meta_words(meta_words, "packed_lrgemm");
   const std::vector<int64_t> oshape = packed_lrgemm_shape(x, L, Rt, M, K);
   admmq_qmeta meta;
-  const at::Tensor mw = meta_words.contiguous();
-  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
-  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_lrgemm: bits must be 1..8");
-  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_lrgemm: a ", M,
-              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
-              " code bytes, got ", codes.numel());
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_lrgemm", meta);
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous(), Lc = L.contiguous(), Rc = Rt.contiguous();
-  at::Tensor cc = codes.contiguous();
-  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_lrgemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
-  const int64_t N = xc.numel() / K;
-  TORCH_CHECK(N > 0, "admmq: packed_lrgemm: empty x");
+  const at::Tensor bc = bias_of(bias, x, M, "packed_lrgemm", false);
+  const int64_t N = gemm_extent(xc, K, 1, "packed_lrgemm").second;
   const int32_t r = static_cast<int32_t>(Lc.size(1));
   at::Tensor y = at::empty(oshape, xc.options());
-  const size_t nbytes = admmq_packed_lrgemm_workspace_size(M, K, N, r);
-  at::Tensor ws = workspace(nbytes, xc);
+  at::Tensor ws = workspace(admmq_packed_lrgemm_workspace_size(M, K, N, r), xc);
   check_rc(admmq_packed_lrgemm(cc.data_ptr<uint8_t>(), &meta, M, K, Lc.data_ptr<float>(), Rc.data_ptr<float>(), r,
-                               xc.data_ptr<float>(), N, bc.defined() ? bc.data_ptr<float>() : nullptr, y.data_ptr<float>(),
-                               ws.data_ptr(), ws.numel(), stream_of(xc)),
+                               xc.data_ptr<float>(), N, f32_or_null(bc), y.data_ptr<float>(), ws.data_ptr(), ws.numel(),
+                               stream_of(xc)),
            "packed_lrgemm");
   return y;
 }
@@ -835,56 +805,38 @@ at::Tensor packed_dwgemm_impl(const at::Tensor& codes, const at::Tensor& meta_wo
                               int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias,
                               const admmq_actq* mid_q, const admmq_actq* out_q) {
   check_f32_device(x, "x");
-  TORCH_CHECK(!(x.requires_grad() && at::GradMode::is_enabled()),
-              "admmq: packed_dwgemm is inference only (no backward through packed weights): call it under "
-              "torch.no_grad() or detach x");
+  check_inference_only(x.requires_grad(), "packed_dwgemm", "x");
   check_f32_device(taps, "taps");
   check_same_device(taps, x, "taps");
-  TORCH_CHECK(codes.is_cuda() && codes.scalar_type() == at::kByte && codes.dim() == 1,
-              "admmq: packed_dwgemm: codes must be a 1-D uint8 tensor on the GPU");
+  check_codes(codes, "packed_dwgemm");
   check_same_device(codes, x, "codes");
-  TORCH_CHECK(meta_words.device().is_cpu() && meta_words.scalar_type() == at::kInt && meta_words.numel() == 8,
-              "admmq: packed_dwgemm: meta_words must be the 8 int32 words of the meta record on the CPU");
+  check_meta_words(meta_words, "packed_dwgemm");
   const std::vector<int64_t> oshape = packed_dwgemm_shape(x, taps, M, K, kh, kw, sh, sw, ph, pw);
   TORCH_CHECK(std::max(sh, sw) <= INT32_MAX && x.size(0) <= INT32_MAX, "admmq: packed_dwgemm: sizes out of range");
   admmq_qmeta meta;
-  const at::Tensor mw = meta_words.contiguous();
-  std::memcpy(&meta, mw.data_ptr<int32_t>(), sizeof(meta));
-  TORCH_CHECK(meta.bits >= 1 && meta.bits <= 8, "admmq: packed_dwgemm: bits must be 1..8");
-  TORCH_CHECK(codes.numel() == static_cast<int64_t>(admmq_packed_bytes(M * K, meta.bits)), "admmq: packed_dwgemm: a ", M,
-              " x ", K, " weight with ", meta.bits, " bits needs ", admmq_packed_bytes(M * K, meta.bits),
-              " code bytes, got ", codes.numel());
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_dwgemm", meta);
   TORCH_CHECK(x.numel() > 0, "admmq: packed_dwgemm: empty x");
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous();
   const at::Tensor tc = taps.detach().contiguous();
-  at::Tensor cc = codes.contiguous();
-  if ((reinterpret_cast<uintptr_t>(cc.data_ptr()) & 15) != 0) cc = cc.clone();   // (a view into a larger buffer)
-  at::Tensor bc;
-  if (bias.has_value() && bias->defined()) {
-    check_f32_device(*bias, "bias");
-    check_same_device(*bias, x, "bias");
-    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == M, "admmq: packed_dwgemm: bias must be [", M, "], got ", bias->sizes());
-    bc = bias->contiguous();
-  }
+  const at::Tensor bc = bias_of(bias, x, M, "packed_dwgemm", false);
   const int32_t nb = static_cast<int32_t>(xc.size(0));
   at::Tensor y = at::empty(oshape, xc.options());
-  const size_t nbytes = admmq_packed_dwgemm_workspace_size(M, K, oshape[2], oshape[3], nb);
-  at::Tensor ws = workspace(nbytes, xc);
+  at::Tensor ws = workspace(admmq_packed_dwgemm_workspace_size(M, K, oshape[2], oshape[3], nb), xc);
   if (mid_q || out_q) {
     check_rc(admmq_packed_dwgemm_act(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<float>(), nb, xc.size(2), xc.size(3),
                                      tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
                                      static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
-                                     static_cast<int32_t>(pw), bc.defined() ? bc.data_ptr<float>() : nullptr,
-                                     y.data_ptr<float>(), mid_q, out_q, ws.data_ptr(), ws.numel(), stream_of(xc)),
+                                     static_cast<int32_t>(pw), f32_or_null(bc), y.data_ptr<float>(), mid_q, out_q,
+                                     ws.data_ptr(), ws.numel(), stream_of(xc)),
              "packed_dwgemm_act");
     return y;
   }
   check_rc(admmq_packed_dwgemm(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr<float>(), nb, xc.size(2), xc.size(3),
                                tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
                                static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
-                               static_cast<int32_t>(pw), bc.defined() ? bc.data_ptr<float>() : nullptr,
-                               y.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(xc)),
+                               static_cast<int32_t>(pw), f32_or_null(bc), y.data_ptr<float>(), ws.data_ptr(), ws.numel(),
+                               stream_of(xc)),
            "packed_dwgemm");
   return y;
 }

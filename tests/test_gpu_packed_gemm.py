@@ -182,6 +182,27 @@ def test_linear_calls_repeat():
     assert torch.equal(_gemm(p, False, x[2:3].contiguous(), 1)[0], _gemm(p, False, x, 1)[2])
 
 
+@pytest.mark.parametrize("scheme", [MSE, MINMAX])
+@pytest.mark.parametrize("trans", [False, True])
+def test_ops_route_and_ctypes_route_give_the_same_bits(scheme, trans, monkeypatch):
+    """The plain call (no ``act``) through torch.ops.admmq and, with ``use_ops`` off, through ctypes (DESIGN.md
+    2.30): a 3-bit 70 x 100 weight, whose code runs straddle dwords, on a linear and a channel-first ``x``."""
+    from admmq import _lib, packed_linear
+    p, _ = _packed((100, 70) if trans else (70, 100), 3, scheme)
+    bias = _randn((70,), 38)
+    calls = [lambda: packed_linear(_randn((3, 100), 36), p, None, trans),
+             lambda: packed_linear(_randn((3, 100), 36), p, bias, trans),
+             lambda: _gemm(p, trans, _randn((2, 100, 5), 37), 0),
+             lambda: _gemm(p, trans, _randn((2, 100, 5), 37), 0, bias)]
+    for i, call in enumerate(calls):
+        assert _lib.use_ops()
+        a = call()
+        with monkeypatch.context() as mp:
+            mp.setattr(_lib, "use_ops", lambda: False)
+            b = call()
+        assert tuple(a.shape) == ((3, 70), (3, 70), (2, 70, 5), (2, 70, 5))[i] and torch.equal(a, b), i
+
+
 # ----------------------------------------------------------------------------- bounds
 @pytest.mark.parametrize("shape,bits,N,nb", [((33, 65), 3, 70, 1), ((134, 9), 5, 3, 2), ((510, 1141), 3, 4, 1)])
 def test_nothing_outside_the_stream_the_output_or_the_workspace_is_touched(shape, bits, N, nb):

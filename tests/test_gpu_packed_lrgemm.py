@@ -179,6 +179,24 @@ def test_calls_repeat_rows_stand_alone_and_the_ctypes_route_agrees(M, K, r, N):
     assert torch.equal(y, y1)
 
 
+def test_ops_route_and_ctypes_route_give_the_same_bits(monkeypatch):
+    """packed_lowrank_linear through torch.ops.admmq and, with ``use_ops`` off, through ctypes:
+    3-bit codes, 5 rows, r = 3, in two regimes of the down-projection."""
+    from admmq import _lib, packed_lowrank_linear
+    M, N, r = 70, 5, 3
+    assert _regimes(M, 100, N, r) != _regimes(M, 40, N, r)
+    for K in (100, 40):
+        p, _ = _lowrank(M, K, r, 3)
+        x = _randn((N, K), 27)
+        for bias in (None, _randn((M,), 28)):
+            assert _lib.use_ops()
+            a = packed_lowrank_linear(x, p, bias)
+            with monkeypatch.context() as mp:
+                mp.setattr(_lib, "use_ops", lambda: False)
+                b = packed_lowrank_linear(x, p, bias)
+            assert torch.equal(a, b), (K, bias is None)
+
+
 # ----------------------------------------------------------------- 5. alignment and bounds
 def _off4(t):
     """A copy of ``t`` that starts 4 bytes past a 16-byte boundary."""
