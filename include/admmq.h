@@ -85,7 +85,11 @@ int32_t admmq_admm_prepare(const admmq_problem* probs, int32_t nprob, int32_t nu
  * dual update, residual test} per problem, with the per-problem early exit when
  * r < eps and s < eps. Writes H_out and U. info (device int32[nprob*4], may be
  * NULL) receives {iterations run, converged, spd_error, internal fault} per problem
- * (internal fault: see admmq_admm_run_ex). With info == NULL the run never takes the
+ * (internal fault: see admmq_admm_run_ex). "converged" is the break itself: it is 1 only
+ * when a later iteration was skipped, so a problem that first meets the rule in iteration
+ * max_iter - 1, the last one run, reports {max_iter - 1, 0} - nothing tests after the last
+ * finalize, and H_out / U are those of the same call with eps = 0 either way.
+ * With info == NULL the run never takes the
  * fused paths that can report an internal fault (as fused_finalize = 0), so a NULL-info
  * call always returns finalized results. Uses the solve mode its prepare recorded;
  * ADMMQ_ERR_ARG for a workspace no prepare has set up, or whose prepare planned other

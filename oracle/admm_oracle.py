@@ -51,10 +51,11 @@ def shifted_gram(G: np.ndarray, rho: np.float32) -> np.ndarray:
 
 
 def admm_iteration(H, U, F, G, max_iter, eps, bits, qscheme, num_attempts=200, solver="cholesky",
-                   return_info=False):
+                   return_info=False, history=None):
     """source/admm.py:51-67. Returns (H, U) with U a NEW array (callers that need the
     reference's in-place update copy it back). ``solver='inverse'`` uses the
-    explicit fp64 inverse rounded to fp32 (the formulation the HIP path uses)."""
+    explicit fp64 inverse rounded to fp32 (the formulation the HIP path uses).
+    ``history``: a list that receives the stop test's (r, s) of every iteration run."""
     H = np.asarray(H, dtype=F32)
     U = np.array(U, dtype=F32, copy=True)
     F = np.asarray(F, dtype=F32)
@@ -81,6 +82,8 @@ def admm_iteration(H, U, F, G, max_iter, eps, bits, qscheme, num_attempts=200, s
         iters += 1
         r = np.sum(((H - HT).astype(F32).astype(np.float64)) ** 2) / np.sum(H.astype(np.float64) ** 2)
         s = np.sum(((H - H_prev).astype(F32).astype(np.float64)) ** 2) / np.sum(U.astype(np.float64) ** 2)
+        if history is not None:
+            history.append((float(r), float(s)))
         if r < eps and s < eps:
             break
     if return_info:
