@@ -524,25 +524,27 @@ int32_t admmq_debug_set_fin_wait_polls(uint32_t polls) {
   return ADMMQ_OK;
 }
 
-// diagnostics (not in include/admmq.h): persistent fp32 solve on/off and its tile rule
-// (f32_tile_rows; changes the bits of the factors whose tile rows change between 64 and 32)
+// diagnostics (not in include/admmq.h): waves per fp32 64 x 64 solve tile: 1 = four waves of
+// 32 x 32 (default), 2 = eight, each pair splitting a sub-tile's K-step (other bits)
 int32_t admmq_debug_set_gemm_ks(int32_t ks) {
   if (ks != 1 && ks != 2) return fail(ADMMQ_ERR_ARG, "ks must be 1 or 2");
   g_gemm_ks_f32 = ks;
   return ADMMQ_OK;
 }
 
-// diagnostics (not in include/admmq.h): staging form of the fp32 64 x 64 tiles (same bits):
-// 0 = k_gemm's global_load_lds with per-lane 64-bit addresses, 1 = k_gemm_f32b (buffer
-// loads with a scalar K offset, U prefetched), 2 = k_gemm_f32b with a 2-deep
-// ring, 3 = k_gemm_f32b without the U prefetch (the default: C3 mode 0 0.655 -> 0.597 us per
-// 64x64 K-step per CU against 0), 4 = 3 with the waves' MFMA bursts at raised issue
-// priority (s_setprio). ADMMQ_GEMM_F32_STAGE sets it at load time.
+// diagnostics (not in include/admmq.h): 1 (default) = the big jobs' stage-1 units sized to fill
+// the resident round evenly, 0 = kHistElems x nv units
 int32_t admmq_debug_set_even_units(int32_t on) {
   g_even_units = on != 0;
   return ADMMQ_OK;
 }
 
+// diagnostics (not in include/admmq.h): kernel of the fp32 64 x 64 tiles (same bits):
+// 0 = k_gemm<2, 1, 3, false> (buffer loads to LDS from two descriptors chosen per piece,
+// U prefetched), 1 = k_gemm_f32b (one wave-uniform descriptor per wave, U prefetched),
+// 2 = k_gemm_f32b with a 2-deep ring, 3 = k_gemm_f32b without the U prefetch (the default:
+// C3 mode 0 0.655 -> 0.597 us per 64x64 K-step per CU against 0), 4 = 3 with the waves'
+// MFMA bursts at raised issue priority (s_setprio). ADMMQ_GEMM_F32_STAGE sets it at load time.
 int32_t admmq_debug_set_gemm_stage(int32_t v) {
   if (v < 0 || v > 4) return fail(ADMMQ_ERR_ARG, "stage must be 0..4");
   g_gemm_f32_stage = v;
@@ -609,6 +611,8 @@ int32_t admmq_debug_ksplit_pieces(int32_t I, int32_t R) {
   return ksplit_pieces(I, R);
 }
 
+// diagnostics (not in include/admmq.h): persistent fp32 solve on/off and its tile rule
+// (f32_tile_rows; changes the bits of the factors whose tile rows change between 64 and 32)
 int32_t admmq_debug_set_f32_persistent(int32_t kernel, int32_t rule) {
   if (rule < 0 || rule > 3) return fail(ADMMQ_ERR_ARG, "rule must be 0..3");
   if (kernel < 0 || kernel > 2) return fail(ADMMQ_ERR_ARG, "kernel must be 0..2");

@@ -20,13 +20,20 @@
 // for factors with I > 32, WM = 1 (32 x 64) for 17..32-row factors.
 //
 // Staging: K-step 32 (128 B per operand row in both forms: 32 floats, or 32 hi + 32 lo
-// halfs). Both operands go global -> LDS by global_load_lds_dwordx4 (no VGPR round trip)
-// into an NS-deep ring of stages, NS-1 K-steps in flight; each wave waits with a counted
-// vmcnt for its own pieces of the stage it is about to read and a raw s_barrier publishes
-// the stage (a __syncthreads would drain every in-flight load). A stage image is
+// halfs). Both operands go global -> LDS 16 B per lane with no VGPR round trip, into an
+// NS-deep ring of stages, NS-1 K-steps in flight. The kernels differ in the load:
+//   k_gemm       buffer_load_dwordx4 ... lds (blds16) from two descriptors rebased to the
+//                tile (P at its first row, M at its first column's row), a per-lane offset
+//                fixed for the tile, the K-step's byte offset in an SGPR;
+//   k_gemm_f32b  the same from one descriptor per wave (waves 0, 1 stage P, 2, 3 stage M);
+//   f32_tile     (k_gemm_f32p, k_gemm_f32t) global_load_lds_dwordx4 (glds16) with per-lane
+//                64-bit addresses.
+// Each wave waits with a counted vmcnt for its own pieces of the stage it is about to read
+// and a raw s_barrier publishes the stage (a __syncthreads would drain every in-flight
+// load). A stage image is
 // row-major, 128 B per row, with the 16-B chunk c of row r stored at chunk position
-// c ^ ((r >> 1) & 7) - applied on the global source address, since an LDS-DMA writes
-// lane-linear - so the fragment reads (ds_read_b128) are bank-conflict free.
+// c ^ ((r >> 1) & 7) - applied on the global source offset or address, since an LDS-DMA
+// writes lane-linear - so the fragment reads (ds_read_b128) are bank-conflict free.
 // fp32: the k-order inside a K-step is k = 16 h + m (lane half h, MFMA m); split: chunk
 // 2 kc + h holds hi halfs k = 16 kc + 8 h .. +7 (the f16 MFMA's lane-half k group), chunk
 // 4 + 2 kc + h the matching lo halfs. A and B use the same order in either form.
@@ -260,6 +267,202 @@ int copy_gemm_trace(unsigned long long* host, int n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_trace), (size_t)n * 4 * sizeof(unsigned long long)) == hipSuccess
              ? n : -1;
 }
+// The record of a finished tile; `extra` = 1 << 63 marks a K-split piece that did not complete its tile
+__device__ __forceinline__ void gemm_trace_store(unsigned long long T0, unsigned long long C0, int nk,
+                                                 unsigned long long extra) {
+  const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
+  const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID
+  g_gemm_trace[blockIdx.x][0] = T0;
+  g_gemm_trace[blockIdx.x][3] = __builtin_amdgcn_s_memtime() - C0;
+  g_gemm_trace[blockIdx.x][1] = ADMMQ_NOW();
+  g_gemm_trace[blockIdx.x][2] = extra | ((unsigned long long)blockIdx.x << 48) | ((unsigned long long)(nk & 0xFF) << 40) |
+                                ((unsigned long long)(xcc & 0xFF) << 32) | hw;
+}
+
+// ---------------------------------------------------------------------------
+// The pieces every tile kernel below (k_gemm, f32_tile, k_gemm_f32b) runs around its own
+// staging (ADMMQ_ISSUE) and MFMA step (ADMMQ_STEP), in the order a tile takes them.
+// Functions where the kernels' code comes out as before; macros, expanded in the kernel,
+// for the rest: the compiler optimises a function on its own before it inlines it, and for
+// these pieces that moved every kernel's registers, spills and waits (the stop decision,
+// the K-slice reduction) or sank the U prefetch out of its place (the epilogue); DESIGN.md
+// §2.31. A macro names the kernel's variables of the same name in all three kernels.
+//
+// Stop head. The first NS-1 stages go out before the stop test; a stopped problem drains
+// them unused. Launch-head bit 0 (the tile carries the stop test's inputs): stop_begin
+// sends their loads ahead of the stages, one dependent level after the tile record like
+// the stages themselves; the kernel issues its stages; ADMMQ_STOP_DECIDE(WAIT) waits for
+// the first stage (the first K-step's own wait, WAIT = GPW (NS - 2)) and tests. Without
+// the bit the test reads the descriptor after the stages (converged_before). The problem's
+// first tile sets the sticky "break" flag (source/admm.py:64-65). A stopped problem's tile
+// returns from the kernel (f32_tile: to the tile loop) once its speculative stage loads
+// have landed: before the wave ends or the stages are reused.
+// (ADMMQ_STOP_DECIDE contains that return, and names early, si, tl, p, slot, iter, eps, tid)
+__device__ __forceinline__ bool stop_begin(const GemmTile& tl, int slot, int iter, StopIn& si) {
+  const bool early = tl.flags != nullptr;
+  if (early) stop_load(tl, slot ^ 1, iter, si);
+  return early;
+}
+#define ADMMQ_STOP_DECIDE(WAIT)                                                      \
+  do {                                                                               \
+    bool skip;                                                                       \
+    if (early) {                                                                     \
+      wait_vmcnt<WAIT>();                                                            \
+      stop_hold(si, iter);                                                           \
+      const int st = stop_test(si, iter, eps);                                       \
+      if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;                           \
+      skip = st != 0;                                                                \
+    } else {                                                                         \
+      skip = p.flags[0] != 0;                                                        \
+      if (!skip && converged_before(p, slot ^ 1, iter, eps)) {                       \
+        if (tl.first && tid == 0) p.flags[0] = 1;                                    \
+        skip = true;                                                                 \
+      }                                                                              \
+    }                                                                                \
+    if (skip) {                                                                      \
+      wait_vmcnt<0>();                                                               \
+      return;                                                                        \
+    }                                                                                \
+  } while (0)
+
+// This iteration's quantizer-search accumulators start at zero (the problem's first tile,
+// NT threads)
+template <int NT>
+__device__ __forceinline__ void reset_search(const ProbDesc& p, int slot, int ncand, int tid) {
+  unsigned long long* sse = p.mv.sse + (size_t)slot * ncand;
+  unsigned long long* h1 = p.mv.h1 + (size_t)slot * kHistRep * (ncand + 1);
+  unsigned long long* h2 = p.mv.h2 + (size_t)slot * kHistRep * (ncand + 1);
+  for (int c = tid; c < ncand; c += NT) sse[c] = 0ull;
+  for (int c = tid; c < kHistRep * (ncand + 1); c += NT) { h1[c] = 0ull; h2[c] = 0ull; }
+  if (tid == 0) { p.mv.s2[slot] = 0.0; p.mv.ticket[slot] = 0u; }
+}
+
+// Ring driver over the kernel's own ADMMQ_STEP(s, kt). Per K-step kt on stage s = kt % NS:
+// wait for it (counted vmcnt: the NS-2 later stages stay in flight), publish it (barrier),
+// refill the stage consumed one step ago with K-step kt + NS - 1, multiply. Every step
+// issues exactly GPW loads (past the end the last K-step is re-read into a stage nobody
+// reads), so the wait count is one constant and the compiler's own wait tracking stays
+// exact. The main loop runs whole groups of NS steps (stage static, no branches around the
+// MFMAs, which would move the accumulators out of AGPRs); the last < NS steps run guarded.
+// (a macro: the step bodies name one __shared__ object per stage through a static s)
+#define ADMMQ_RING(NS, nk)                                                    \
+  do {                                                                        \
+    const int nfull = (nk) / (NS) * (NS);                                     \
+    for (int kt0 = 0; kt0 < nfull; kt0 += (NS)) {                             \
+      _Pragma("unroll") for (int s = 0; s < (NS); ++s) ADMMQ_STEP(s, kt0 + s); \
+    }                                                                         \
+    _Pragma("unroll") for (int s = 0; s < (NS) - 1; ++s)                      \
+      if (nfull + s < (nk)) ADMMQ_STEP(s, nfull + s);                         \
+  } while (0)
+
+// Fixed-order (deterministic) reduction of the KS partial accumulators of a sub-tile into
+// the K-slice 0 wave, through stage 0: behind the first barrier nothing is in flight any
+// more and the stages may be reused. (names ks, sub, lane)
+#define ADMMQ_KSLICE_REDUCE(KS, NSUB, acc, stage0)                                       \
+  do {                                                                                   \
+    __syncthreads();                                                                     \
+    if (KS > 1) {                                                                        \
+      if (ks > 0) {                                                                      \
+        float* dst = (stage0) + ((ks - 1) * NSUB + sub) * 1024;                          \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) dst[r * 64 + lane] = (acc)[r];    \
+      }                                                                                  \
+      __syncthreads();                                                                   \
+      if (ks == 0) {                                                                     \
+        _Pragma("unroll") for (int j = 1; j < KS; ++j) {                                 \
+          const float* s2 = (stage0) + ((j - 1) * NSUB + sub) * 1024;                    \
+          _Pragma("unroll") for (int r = 0; r < 16; ++r) (acc)[r] += s2[r * 64 + lane];  \
+        }                                                                                \
+      }                                                                                  \
+    }                                                                                    \
+  } while (0)
+
+// Serial K-split of the fp32 64 x 64 tiles (tl.ser pieces in one workgroup): at the first
+// K-step of piece pf, fold the finished piece into the running sum ((p0 + p1) + ...:
+// ksplit_combine's order) and restart the accumulator (step); last adds the last piece.
+// The order psum + acc is part of the tile's bits (-ffp-contract=off).
+struct SerialFold {
+  f32x16 psum;
+  int ser, pf, kb;
+  __device__ __forceinline__ SerialFold(int ser_, int nk) : ser(ser_), pf(1), kb(ser_ > 1 ? nk / ser_ : nk) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) psum[r] = 0.f;
+  }
+  __device__ __forceinline__ void step(f32x16& acc, int kt, int nk) {
+    if (kt == kb && kt > 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        psum[r] = pf == 1 ? acc[r] : psum[r] + acc[r];
+        acc[r] = 0.f;
+      }
+      ++pf;
+      kb = pf * nk / ser;
+    }
+  }
+  __device__ __forceinline__ void last(f32x16& acc) const {
+    if (ser > 1)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = psum[r] + acc[r];
+  }
+};
+
+// Epilogue of one wave (C/D map col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)):
+// store H_T (split form: scaled back by the row and column exponents EROW / ECOL), the
+// debug X = H_T - U, and fold max|X|, min X, max X over the valid I x R region into
+// red[0..2][SUB]. ACC[c] / U[c]: accumulator and U entries of sub-tile c < CW. HT_STORE:
+// 0 plain stores, 1 write-through (sc1) buffer stores, 2 nontemporal stores (k_gemm_f32b's
+// ADMMQ_SC1_STORES / ADMMQ_NT_STORES bit 2). Names the kernel's p, row0, col0, ld, wm, wn,
+// i, h, lane and red. (a macro: a function is optimised on its own before it is inlined,
+// which moved the U prefetch and the register counts of every kernel)
+constexpr const int* kNoExp = nullptr;   // EROW / ECOL of the fp32 kernels
+#define ADMMQ_EPILOGUE(CW, SPLIT, HT_STORE, ACC, U, EROW, ECOL, SUB)                                     \
+  do {                                                                                                   \
+    unsigned amax = 0u, mn = 0xFFFFFFFFu, mxo = 0u;                                                      \
+    /* descriptor fields once into registers (the stores below may alias the descriptor) */             \
+    typedef __attribute__((address_space(1))) float gf32;                                                \
+    [[maybe_unused]] gf32* const HTg = (gf32*)p.HT;                                                      \
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t htrs =                                                 \
+        __builtin_amdgcn_make_buffer_rsrc(p.HT, 0, 0x7FFFFFFF, 0x00020000);                              \
+    gf32* const Xg = p.X_dbg ? (gf32*)p.X : nullptr; /* X is re-formed by its readers; debug output */   \
+    const int pI = p.I, pR = p.R;                                                                        \
+    _Pragma("unroll") for (int c = 0; c < CW; ++c) {                                                     \
+      const int col = col0 + 32 * (CW * wn + c) + i;                                                     \
+      if (col < ld) {                                                                                    \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                 \
+          const int row = row0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * h;                               \
+          const size_t off = (size_t)row * ld + col;                                                     \
+          float ht = (ACC)[c][r];                                                                        \
+          if constexpr (SPLIT) ht = __builtin_ldexpf(ht, -((EROW)[r] + (ECOL)[c]));                      \
+          const float x = ht - (U)[c][r];                                                                \
+          if constexpr (HT_STORE == 1)                                                                   \
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ht), htrs, (int)(off * 4), 0, 16);     \
+          else if constexpr (HT_STORE == 2) __builtin_nontemporal_store(ht, HTg + off);                  \
+          else HTg[off] = ht;                                                                            \
+          if (Xg) Xg[off] = x;                                                                           \
+          if (row < pI && col < pR) {                                                                    \
+            amax = max(amax, __float_as_uint(x) & 0x7FFFFFFFu);                                          \
+            const unsigned e = enc_ord(x);                                                               \
+            mn = min(mn, e);                                                                             \
+            mxo = max(mxo, e);                                                                           \
+          }                                                                                              \
+        }                                                                                                \
+      }                                                                                                  \
+    }                                                                                                    \
+    amax = wave_max_u32(amax); mn = wave_min_u32(mn); mxo = wave_max_u32(mxo);                           \
+    if (lane == 0) { red[0][SUB] = amax; red[1][SUB] = mn; red[2][SUB] = mxo; }                          \
+  } while (0)
+// ... and of the workgroup (one thread, behind a barrier): the NSUB waves' values into the
+// problem's per-iteration stat slot
+template <int NSUB, int RW>
+__device__ __forceinline__ void stat_reduce(const ProbDesc& p, int slot, const unsigned (*red)[RW]) {
+  static_assert(NSUB <= RW, "red rows hold NSUB waves");
+  unsigned a0 = red[0][0], a1 = red[1][0], a2 = red[2][0];
+#pragma unroll
+  for (int w = 1; w < NSUB; ++w) { a0 = max(a0, red[0][w]); a1 = min(a1, red[1][w]); a2 = max(a2, red[2][w]); }
+  unsigned* st = p.mv.stat + 4 * slot;
+  atomicMax(&st[0], a0);
+  atomicMin(&st[1], a1);
+  atomicMax(&st[2], a2);
+}
 
 // One workgroup per tile (the grid is the tile list, longest K first, CU-balanced by the
 // planner). SPLIT selects the operand form (see the file header).
@@ -360,73 +563,30 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
 #define ADMMQ_ISSUE(s, kt)                                                                                      \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                                                              \
     blds16(8 * (wave * GPW + j) < BM ? rsA : rsB, stp[s] + (wave * GPW + j) * 256, voff[j], (kt) * (BK * 4))
-  // the first NS-1 stages go out before the stop test; a stopped problem drains them unused
-  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
-  // of the stages, one dependent level after the tile record like the stages themselves,
-  // and the test waits for the first stage first (the first K-step's own wait)
-  const bool early = tl.flags != nullptr;
   StopIn si;
-  if (early) stop_load(tl, slot ^ 1, iter, si);
+  const bool early = stop_begin(tl, slot, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip;
-  if (early) {
-    wait_vmcnt<GPW * (NS - 2)>();
-    stop_hold(si, iter);
-    const int st = stop_test(si, iter, eps);
-    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = st != 0;
-  } else {
-    skip = p.flags[0] != 0;
-    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-      skip = true;
-    }
-  }
-  if (skip) {
-    wait_vmcnt<0>();   // the speculative stage loads land before the wave ends
-    return;
-  }
-  if (tl.first) {   // this iteration's quantizer-search accumulators start at zero
-    unsigned long long* sse = p.mv.sse + (size_t)slot * ncand;
-    unsigned long long* h1 = p.mv.h1 + (size_t)slot * kHistRep * (ncand + 1);
-    unsigned long long* h2 = p.mv.h2 + (size_t)slot * kHistRep * (ncand + 1);
-    for (int c = tid; c < ncand; c += NT) sse[c] = 0ull;
-    for (int c = tid; c < kHistRep * (ncand + 1); c += NT) { h1[c] = 0ull; h2[c] = 0ull; }
-    if (tid == 0) { p.mv.s2[slot] = 0.0; p.mv.ticket[slot] = 0u; }
-  }
+  ADMMQ_STOP_DECIDE(GPW * (NS - 2));   // returns from here when the problem has stopped
+  if (tl.first) reset_search<NT>(p, slot, ncand, tid);
 
-  f32x16 acc[CW], psum;
+  f32x16 acc[CW];
 #pragma unroll
   for (int c = 0; c < CW; ++c)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = psum[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
   // serial K-split (fp32 64 x 64 tiles only: k_gemm_f32b's fold, the same order)
   constexpr bool FOLD = !SPLIT && WM == 2 && KS == 1 && CW == 1;
-  const int ser = FOLD ? tl.ser : 1;
-  int pf = 1, kb = ser > 1 ? nk / ser : nk;
+  SerialFold fold(FOLD ? tl.ser : 1, nk);
 
-  // Per K-step kt on stage s = kt % NS: wait for it (counted vmcnt: the NS-2 later
-  // stages stay in flight), publish it (barrier), refill the stage consumed one step
-  // ago with K-step kt + NS - 1, multiply. Every step issues exactly GPW loads (past
-  // the end the last K-step is re-read into a stage nobody reads), so the wait count
-  // is one constant and the compiler's own wait tracking stays exact. The main loop
-  // runs whole groups of NS steps (stage static, no branches around the MFMAs, which
-  // would move the accumulators out of AGPRs); the last < NS steps run guarded.
+  // one K-step (ADMMQ_RING drives it)
 #define ADMMQ_STEP(s, kt)                                                                     \
   do {                                                                                        \
     wait_vmcnt<GPW * (NS - 2)>();                                                             \
     __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): reads of the refilled stage done */    \
     raw_barrier();                                                                            \
     if (ADMMQ_GEMM_DIAG != 2 || SPLIT) ADMMQ_ISSUE(((s) + NS - 1) % NS, min((kt) + NS - 1, nk - 1)); \
-    if (FOLD && (kt) == kb && (kt) > 0) {                                                     \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                        \
-        psum[r] = pf == 1 ? acc[0][r] : psum[r] + acc[0][r];                                  \
-        acc[0][r] = 0.f;                                                                      \
-      }                                                                                       \
-      ++pf;                                                                                   \
-      kb = pf * nk / ser;                                                                     \
-    }                                                                                         \
+    if (FOLD) fold.step(acc[0], (kt), nk);                                                    \
     const float* st = stp[s];                                                                 \
     if constexpr (SPLIT) {                                                                    \
       _Pragma("unroll") for (int q = 0; q < KCW; ++q) {                                       \
@@ -474,37 +634,12 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
       }                                                                                       \
     }                                                                                         \
   } while (0)
-  const int nfull = nk / NS * NS;
-  for (int kt0 = 0; kt0 < nfull; kt0 += NS) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) ADMMQ_STEP(s, kt0 + s);
-  }
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (nfull + s < nk) ADMMQ_STEP(s, nfull + s);
+  ADMMQ_RING(NS, nk);
 #undef ADMMQ_STEP
 #undef ADMMQ_ISSUE
-  __syncthreads();   // nothing in flight any more; the stages may be reused
-  if (KS > 1) {      // fixed-order reduction of the KS partial accumulators (deterministic)
-    if (ks > 0) {
-      float* dst = st0 + ((ks - 1) * NSUB + sub) * 1024;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64 + lane] = acc[0][r];
-    }
-    __syncthreads();
-    if (ks == 0) {
-#pragma unroll
-      for (int j = 1; j < KS; ++j) {
-        const float* s2 = st0 + ((j - 1) * NSUB + sub) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][r] += s2[r * 64 + lane];
-      }
-    }
-  }
+  ADMMQ_KSLICE_REDUCE(KS, NSUB, acc[0], st0);
   if constexpr (FOLD) {   // K-split: the serial form's last piece, or a parallel piece (k_gemm_f32b's combine)
-    if (ser > 1)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[0][r] = psum[r] + acc[0][r];
+    fold.last(acc[0]);
     if (tl.np > 1) {
       __shared__ int klast;
       if (!ksplit_combine(tl, acc[0], &klast)) return;
@@ -514,54 +649,12 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
   // epilogue (waves ks == 0): C/D map col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5)
   if (ks == 0) {
     if constexpr (!PRE) load_epi();
-    unsigned amax = 0u, mn = 0xFFFFFFFFu, mxo = 0u;
-    // descriptor fields once into registers (the stores below may alias the descriptor)
-    typedef __attribute__((address_space(1))) float gf32;
-    gf32* const HTg = (gf32*)p.HT;
-    gf32* const Xg = p.X_dbg ? (gf32*)p.X : nullptr;   // X = H_T - U is re-formed by its readers; debug output only
-    const int pI = p.I, pR = p.R;
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      const int col = col0 + 32 * (CW * wn + c) + i;
-      if (col < ld) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = row0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const size_t off = (size_t)row * ld + col;
-          const float ht = SPLIT ? __builtin_ldexpf(acc[c][r], -(epre[r] + ecol[c])) : acc[c][r];
-          const float x = ht - upre[c][r];
-          HTg[off] = ht;
-          if (Xg) Xg[off] = x;
-          if (row < pI && col < pR) {
-            amax = max(amax, __float_as_uint(x) & 0x7FFFFFFFu);
-            const unsigned e = enc_ord(x);
-            mn = min(mn, e);
-            mxo = max(mxo, e);
-          }
-        }
-      }
-    }
-    amax = wave_max_u32(amax); mn = wave_min_u32(mn); mxo = wave_max_u32(mxo);
-    if (lane == 0) { red[0][sub] = amax; red[1][sub] = mn; red[2][sub] = mxo; }
+    ADMMQ_EPILOGUE(CW, SPLIT, 0, acc, upre, epre, ecol, sub);
   }
   __syncthreads();
   if (tid == 0) {
-    unsigned a0 = red[0][0], a1 = red[1][0], a2 = red[2][0];
-#pragma unroll
-    for (int w = 1; w < NSUB; ++w) { a0 = max(a0, red[0][w]); a1 = min(a1, red[1][w]); a2 = max(a2, red[2][w]); }
-    unsigned* st = p.mv.stat + 4 * slot;
-    atomicMax(&st[0], a0);
-    atomicMin(&st[1], a1);
-    atomicMax(&st[2], a2);
-    if (ADMMQ_TRACE && blockIdx.x < kGemmTraceMax) {
-      const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
-      const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID
-      g_gemm_trace[blockIdx.x][0] = T0;
-      g_gemm_trace[blockIdx.x][3] = __builtin_amdgcn_s_memtime() - C0;
-      g_gemm_trace[blockIdx.x][1] = ADMMQ_NOW();
-      g_gemm_trace[blockIdx.x][2] = ((unsigned long long)blockIdx.x << 48) | ((unsigned long long)(nk & 0xFF) << 40) |
-                                    ((unsigned long long)(xcc & 0xFF) << 32) | hw;
-    }
+    stat_reduce<NSUB>(p, slot, red);
+    if (ADMMQ_TRACE && blockIdx.x < kGemmTraceMax) gemm_trace_store(T0, C0, nk, 0ull);
   }
 }
 
@@ -578,8 +671,8 @@ __global__ __launch_bounds__(128 * WM * KS) __attribute__((amdgpu_waves_per_eu(
 //   BM  32 x 64  (2 waves of 32 x 32 x 2 K-halves)   k_gemm<2,1,..> / k_gemm<1,2,..>
 // Every element's MFMA sequence (k = 16 h + 4 qq + j per K-step, KS = 1) is the one of
 // the 64 x 64 tiles, so BM 128 and BM 64 give identical bits; BM 32 sums two K-halves
-// like k_gemm<1, 2, ..>. Staging as k_gemm: K-step 32, LDS-DMA into an NS-deep ring of
-// (128 + 64)-row stages (the rows of smaller tiles use the front of each stage).
+// like k_gemm<1, 2, ..>. Staging: K-step 32, glds16 (per-lane addresses) into an NS-deep
+// ring of (128 + 64)-row stages (the rows of smaller tiles use the front of each stage).
 template <int BM, int NS>
 __device__ __forceinline__ void f32_tile(const ProbDesc* __restrict__ probs, const GemmTile& tl, int slot, int iter,
                                          float eps, int ncand, float* const (&stp)[4], unsigned (*red)[4]) {
@@ -630,40 +723,12 @@ __device__ __forceinline__ void f32_tile(const ProbDesc* __restrict__ probs, con
 #define ADMMQ_ISSUE(s, kt)                                                 \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                         \
     glds16(src[j] + (kt) * BK, stp[s] + (wave * GPW + j) * 256)
-  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
-  // of the stages, one dependent level after the tile record like the stages themselves,
-  // and the test waits for the first stage first (the first K-step's own wait)
-  const bool early = tl.flags != nullptr;
   StopIn si;
-  if (early) stop_load(tl, slot ^ 1, iter, si);
+  const bool early = stop_begin(tl, slot, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip;
-  if (early) {
-    wait_vmcnt<GPW * (NS - 2)>();
-    stop_hold(si, iter);
-    const int st = stop_test(si, iter, eps);
-    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = st != 0;
-  } else {
-    skip = p.flags[0] != 0;
-    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-      skip = true;
-    }
-  }
-  if (skip) {
-    wait_vmcnt<0>();   // the speculative stage loads land before the stages are reused
-    return;
-  }
-  if (tl.first) {   // this iteration's quantizer-search accumulators start at zero
-    unsigned long long* sse = p.mv.sse + (size_t)slot * ncand;
-    unsigned long long* h1 = p.mv.h1 + (size_t)slot * kHistRep * (ncand + 1);
-    unsigned long long* h2 = p.mv.h2 + (size_t)slot * kHistRep * (ncand + 1);
-    for (int c = tid; c < ncand; c += 256) sse[c] = 0ull;
-    for (int c = tid; c < kHistRep * (ncand + 1); c += 256) { h1[c] = 0ull; h2[c] = 0ull; }
-    if (tid == 0) { p.mv.s2[slot] = 0.0; p.mv.ticket[slot] = 0u; }
-  }
+  ADMMQ_STOP_DECIDE(GPW * (NS - 2));   // returns from here when the problem has stopped
+  if (tl.first) reset_search<256>(p, slot, ncand, tid);
   f32x16 acc[CW];
 #pragma unroll
   for (int c = 0; c < CW; ++c)
@@ -692,75 +757,16 @@ __device__ __forceinline__ void f32_tile(const ProbDesc* __restrict__ probs, con
         acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[c].w, acc[c], 0, 0, 0);          \
     }                                                                                         \
   } while (0)
-  const int nfull = nk / NS * NS;
-  for (int kt0 = 0; kt0 < nfull; kt0 += NS) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) ADMMQ_STEP(s, kt0 + s);
-  }
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (nfull + s < nk) ADMMQ_STEP(s, nfull + s);
+  ADMMQ_RING(NS, nk);
 #undef ADMMQ_STEP
 #undef ADMMQ_ISSUE
-  __syncthreads();   // nothing in flight any more; the stages may be reused
-  if (KS > 1) {      // fixed-order reduction of the K-slice partial accumulators (deterministic)
-    if (ks > 0) {
-      float* dst = stp[0] + ((ks - 1) * NSUB + sub) * 1024;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[r * 64 + lane] = acc[0][r];
-    }
-    __syncthreads();
-    if (ks == 0) {
-#pragma unroll
-      for (int j = 1; j < KS; ++j) {
-        const float* s2 = stp[0] + ((j - 1) * NSUB + sub) * 1024;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][r] += s2[r * 64 + lane];
-      }
-    }
-  }
-  // epilogue (waves ks == 0): C/D map col = lane&31, row = (r&3) + 8(r>>2) + 4(lane>>5)
+  ADMMQ_KSLICE_REDUCE(KS, NSUB, acc[0], stp[0]);
   if (ks == 0) {
     if constexpr (!PRE) load_u();
-    unsigned amax = 0u, mn = 0xFFFFFFFFu, mxo = 0u;
-    typedef __attribute__((address_space(1))) float gf32;
-    gf32* const HTg = (gf32*)p.HT;
-    gf32* const Xg = p.X_dbg ? (gf32*)p.X : nullptr;   // X = H_T - U is re-formed by its readers; debug output only
-    const int pI = p.I, pR = p.R;
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-      const int col = col0 + 32 * (CW * wn + c) + i;
-      if (col < ld) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = row0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-          const size_t off = (size_t)row * ld + col;
-          const float ht = acc[c][r];
-          const float x = ht - upre[c][r];
-          HTg[off] = ht;
-          if (Xg) Xg[off] = x;
-          if (row < pI && col < pR) {
-            amax = max(amax, __float_as_uint(x) & 0x7FFFFFFFu);
-            const unsigned e = enc_ord(x);
-            mn = min(mn, e);
-            mxo = max(mxo, e);
-          }
-        }
-      }
-    }
-    amax = wave_max_u32(amax); mn = wave_min_u32(mn); mxo = wave_max_u32(mxo);
-    if (lane == 0) { red[0][sub] = amax; red[1][sub] = mn; red[2][sub] = mxo; }
+    ADMMQ_EPILOGUE(CW, false, 0, acc, upre, kNoExp, kNoExp, sub);
   }
   __syncthreads();
-  if (tid == 0) {
-    unsigned a0 = red[0][0], a1 = red[1][0], a2 = red[2][0];
-#pragma unroll
-    for (int w = 1; w < NSUB; ++w) { a0 = max(a0, red[0][w]); a1 = min(a1, red[1][w]); a2 = max(a2, red[2][w]); }
-    unsigned* stt = p.mv.stat + 4 * slot;
-    atomicMax(&stt[0], a0);
-    atomicMin(&stt[1], a1);
-    atomicMax(&stt[2], a2);
-  }
+  if (tid == 0) stat_reduce<NSUB>(p, slot, red);
 }
 
 template <int NS>
@@ -885,66 +891,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
 #define ADMMQ_ISSUE(s, kt)                                                                            \
   _Pragma("unroll") for (int j = 0; j < GPW; ++j)                                                    \
     blds16(rs, stp[s] + (wave * GPW + j) * 256, voff[j], (kt) * (BK * 4))
-  // launch-head bit 0 (the tile carries the stop test's inputs): their loads go out ahead
-  // of the stages, one dependent level after the tile record like the stages themselves,
-  // and the test waits for the first stage first (the first K-step's own wait)
-  const bool early = tl.flags != nullptr;
   StopIn si;
-  if (early) stop_load(tl, slot ^ 1, iter, si);
+  const bool early = stop_begin(tl, slot, iter, si);
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) ADMMQ_ISSUE(s, min(s, nk - 1));
-  bool skip;
-  if (early) {
-    wait_vmcnt<GPW * (NS - 2)>();
-    stop_hold(si, iter);
-    const int st = stop_test(si, iter, eps);
-    if (st == 2 && tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-    skip = st != 0;
-  } else {
-    skip = p.flags[0] != 0;
-    if (!skip && converged_before(p, slot ^ 1, iter, eps)) {
-      if (tl.first && tid == 0) p.flags[0] = 1;   // sticky "break" (source/admm.py:64-65)
-      skip = true;
-    }
-  }
-  if (skip) {
-    wait_vmcnt<0>();   // the speculative stage loads land before the wave ends
-    return;
-  }
+  ADMMQ_STOP_DECIDE(GPW * (NS - 2));   // returns from here when the problem has stopped
   unsigned long long TH = 0ull;
   if (ADMMQ_TRACE) {   // the head's end: the wait the first K-step is about to make, made here
     wait_vmcnt<GPW * (NS - 2)>();
     TH = ADMMQ_NOW();
   }
-  if (tl.first) {   // this iteration's quantizer-search accumulators start at zero
-    unsigned long long* sse = p.mv.sse + (size_t)slot * ncand;
-    unsigned long long* h1 = p.mv.h1 + (size_t)slot * kHistRep * (ncand + 1);
-    unsigned long long* h2 = p.mv.h2 + (size_t)slot * kHistRep * (ncand + 1);
-    for (int c = tid; c < ncand; c += 256) sse[c] = 0ull;
-    for (int c = tid; c < kHistRep * (ncand + 1); c += 256) { h1[c] = 0ull; h2[c] = 0ull; }
-    if (tid == 0) { p.mv.s2[slot] = 0.0; p.mv.ticket[slot] = 0u; }
-  }
-  f32x16 acc, psum;
+  if (tl.first) reset_search<256>(p, slot, ncand, tid);
+  f32x16 acc;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = psum[r] = 0.f;
-  // serial K-split (tl.ser pieces): at the first K-step of piece pf, fold the finished
-  // piece into the running sum ((p0 + p1) + ...: ksplit_combine's order) and restart
-  const int ser = tl.ser;
-  int pf = 1, kb = ser > 1 ? nk / ser : nk;
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  SerialFold fold(tl.ser, nk);
 #define ADMMQ_STEP(s, kt)                                                                     \
   do {                                                                                        \
     wait_vmcnt<GPW * (NS - 2)>();                                                             \
     __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): reads of the refilled stage done */    \
     raw_barrier();                                                                            \
     ADMMQ_ISSUE(((s) + NS - 1) % NS, min((kt) + NS - 1, nk - 1));                             \
-    if ((kt) == kb && (kt) > 0) {                                                             \
-      _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                        \
-        psum[r] = pf == 1 ? acc[r] : psum[r] + acc[r];                                        \
-        acc[r] = 0.f;                                                                         \
-      }                                                                                       \
-      ++pf;                                                                                   \
-      kb = pf * nk / ser;                                                                     \
-    }                                                                                         \
+    fold.step(acc, (kt), nk);                                                                 \
     const float* st = stp[s];                                                                 \
     float4 fa[2], fb[2];                                                                      \
     if (PRIO) __builtin_amdgcn_s_setprio(1);                                                  \
@@ -970,22 +938,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
     }                                                                                         \
     if (PRIO) __builtin_amdgcn_s_setprio(0);                                                  \
   } while (0)
-  const int nfull = nk / NS * NS;
-  for (int kt0 = 0; kt0 < nfull; kt0 += NS) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) ADMMQ_STEP(s, kt0 + s);
-  }
-#pragma unroll
-  for (int s = 0; s < NS - 1; ++s)
-    if (nfull + s < nk) ADMMQ_STEP(s, nfull + s);
+  ADMMQ_RING(NS, nk);
 #undef ADMMQ_STEP
 #undef ADMMQ_ISSUE
   wait_vmcnt<0>();   // the refills past the end land before the workgroup ends
   const unsigned long long TK = ADMMQ_NOW();
-  if (ser > 1) {     // serial K-split: the last piece
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = psum[r] + acc[r];
-  }
+  fold.last(acc);    // serial K-split: the last piece
   if (tl.np > 1) {   // K-split piece: only the piece that completes the tile goes on
     __shared__ int klast;
     const bool go = ksplit_combine(tl, acc, &klast);
@@ -993,15 +951,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
       g_gemm_trace2[blockIdx.x][0] = TK;
       g_gemm_trace2[blockIdx.x][1] = ADMMQ_NOW();
       g_gemm_trace3[blockIdx.x] = TH;
-      if (!go) {   // a piece that did not complete its tile: {start, end, info | 1 << 63}
-        g_gemm_trace[blockIdx.x][0] = T0;
-        g_gemm_trace[blockIdx.x][3] = __builtin_amdgcn_s_memtime() - C0;
-        g_gemm_trace[blockIdx.x][1] = ADMMQ_NOW();
-        g_gemm_trace[blockIdx.x][2] = (1ull << 63) | ((unsigned long long)blockIdx.x << 48) |
-                                      ((unsigned long long)(nk & 0xFF) << 40) |
-                                      ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFF) << 32) |
-                                      __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      }
+      if (!go) gemm_trace_store(T0, C0, nk, 1ull << 63);   // a piece that did not complete its tile
     }
     if (!go) return;
   } else if (ADMMQ_TRACE && tid == 0 && blockIdx.x < kGemmTraceMax) {
@@ -1010,56 +960,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 2 ? 4
     g_gemm_trace3[blockIdx.x] = TH;
   }
   if constexpr (!PRE) load_u();
-  unsigned amax = 0u, mn = 0xFFFFFFFFu, mxo = 0u;
-  typedef __attribute__((address_space(1))) float gf32;
-  [[maybe_unused]] gf32* const HTg = (gf32*)p.HT;
-  [[maybe_unused]] const __amdgpu_buffer_rsrc_t htrs = __builtin_amdgcn_make_buffer_rsrc(p.HT, 0, 0x7FFFFFFF, 0x00020000);
-  gf32* const Xg = p.X_dbg ? (gf32*)p.X : nullptr;   // debug output only
-  const int pI = p.I, pR = p.R;
-  const int col = col0 + 32 * wn + i;
-  if (col < ld) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = row0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * h;
-      const size_t off = (size_t)row * ld + col;
-      const float ht = acc[r];
-      const float x = ht - upre[r];
-#if ADMMQ_SC1_STORES & 4
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ht), htrs, (int)(off * 4), 0, 16);
-#elif ADMMQ_NT_STORES & 4
-      __builtin_nontemporal_store(ht, HTg + off);
-#else
-      HTg[off] = ht;
-#endif
-      if (Xg) Xg[off] = x;
-      if (row < pI && col < pR) {
-        amax = max(amax, __float_as_uint(x) & 0x7FFFFFFFu);
-        const unsigned e = enc_ord(x);
-        mn = min(mn, e);
-        mxo = max(mxo, e);
-      }
-    }
-  }
-  amax = wave_max_u32(amax); mn = wave_min_u32(mn); mxo = wave_max_u32(mxo);
-  if (lane == 0) { red[0][wave] = amax; red[1][wave] = mn; red[2][wave] = mxo; }
+  constexpr int HT_STORE = (ADMMQ_SC1_STORES & 4) ? 1 : (ADMMQ_NT_STORES & 4) ? 2 : 0;
+  ADMMQ_EPILOGUE(1, false, HT_STORE, &acc, &upre, kNoExp, kNoExp, wave);
   __syncthreads();
   if (tid == 0) {
-    unsigned a0 = red[0][0], a1 = red[1][0], a2 = red[2][0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) { a0 = max(a0, red[0][w]); a1 = min(a1, red[1][w]); a2 = max(a2, red[2][w]); }
-    unsigned* stt = p.mv.stat + 4 * slot;
-    atomicMax(&stt[0], a0);
-    atomicMin(&stt[1], a1);
-    atomicMax(&stt[2], a2);
-    if (ADMMQ_TRACE && blockIdx.x < kGemmTraceMax) {
-      const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
-      const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_REG_HW_ID
-      g_gemm_trace[blockIdx.x][0] = T0;
-      g_gemm_trace[blockIdx.x][3] = __builtin_amdgcn_s_memtime() - C0;
-      g_gemm_trace[blockIdx.x][1] = ADMMQ_NOW();
-      g_gemm_trace[blockIdx.x][2] = ((unsigned long long)blockIdx.x << 48) | ((unsigned long long)(nk & 0xFF) << 40) |
-                                    ((unsigned long long)(xcc & 0xFF) << 32) | hw;
-    }
+    stat_reduce<4>(p, slot, red);
+    if (ADMMQ_TRACE && blockIdx.x < kGemmTraceMax) gemm_trace_store(T0, C0, nk, 0ull);
   }
 }
 

@@ -282,8 +282,8 @@ def test_c5_llama_full_layer_batch(torch_dev, mode, solve):
 
 def test_fp32_staging_forms_equal(torch_dev):
     """The fp32 64x64 solve tiles have four staging forms (ADMMQ_GEMM_F32_STAGE /
-    admmq_debug_set_gemm_stage: k_gemm's global_load_lds with per-lane addresses, and
-    k_gemm_f32b's scalar-offset buffer loads with / without the U prefetch, 3- or 2-deep
+    admmq_debug_set_gemm_stage: k_gemm's buffer loads to LDS from two descriptors, and
+    k_gemm_f32b's from one descriptor per wave with / without the U prefetch, 3- or 2-deep
     ring). The tile, the wave layout, the K order and the epilogue are the
     same, so every element's MFMA chain is too: H and U equal bit for bit over 3 inner
     iterations, on factors whose launch pads the grid to whole rounds (>256 tiles) and on

@@ -275,6 +275,23 @@ def test_f32_persistent_kernels(torch_dev, kernel, rule):
     _check_steps(F32_SHAPES, runs, _f32_id(kernel, rule).split("[")[0])
 
 
+@pytest.mark.parametrize("kernel", [1, 2], ids=["f32p", "f32t"])
+def test_f32_persistent_32_row_statistics(torch_dev, kernel):
+    """A 32-row tile of k_gemm_f32p / k_gemm_f32t has two sub-tile waves, the other tile shapes
+    four, and the workgroup folds that many per-wave max|X| / min X / max X values into the
+    quantizer's range. _check_steps cannot see that range (it takes H_k from the device), so:
+    the (20, 70) factor sums the same two K-halves per element as the default kernel's 32-row
+    tiles, hence its H, U and H_T of 3 steps equal the default run's bit for bit. (65, 129) is
+    company in the launch only and is not compared (its rule-1 tiles are 32-row ones, which
+    share f32p's workgroups; its bits differ from the default's 64-row tiles): r[0] below is
+    the (20, 70) factor."""
+    shapes = [(20, 70), (65, 129)]
+    default = _run_steps(torch_dev, shapes)
+    with _setter("admmq_debug_set_f32_persistent", (kernel, 1), (0, 1)):
+        runs = _run_steps(torch_dev, shapes)
+    _same_runs([[r[0]] for r in default], [[r[0]] for r in runs])
+
+
 @pytest.mark.parametrize("I,R", [(65, 129), (64, 1000)], ids=lambda v: str(v))
 def test_gemm_ks2(torch_dev, I, R):
     """Eight waves per 64 x 64 tile, two half chains per K-step summed in fixed order."""
