@@ -192,6 +192,7 @@ def load() -> ctypes.CDLL:
         "admmq_cp_workspace_size": (S, [P, I32, I32]),
         "admmq_cp_gram_mttkrp": (I32, [P, I32, I32, P, S, P]),
         "admmq_cp_rel_error": (I32, [P, I32, P, P, S, P]),
+        "admmq_debug_cp_plan": (I32, [P, I32, I32, I32, P]),
         "admmq_cp64_workspace_size": (S, [P, I32, I32]),
         "admmq_cp64_gram_mttkrp": (I32, [P, I32, I32, P, S, P]),
         "admmq_lowrank_workspace_size": (S, [I64]),
@@ -408,6 +409,33 @@ def debug_spd_inverse(Gs, shift: float = 0.0, reps: int = 1):
     for o, f in zip(out, flags):
         o["flag"] = int(f)
     return out, float(ms.value)
+
+
+CP_KINDS = {"mttkrp": 0, "gram": 1, "error": 2}
+CP_JOB_GENERIC, CP_JOB_GRAM, CP_JOB_ERROR, CP_JOB_SPATIAL = 0, 1, 2, 3
+
+
+def debug_cp_plan(layers, mode: int, kind: str = "mttkrp", raw: bool = False):
+    """Diagnostics (host only): the form the ALS planner gives each ``(dims, R, w_address)`` of
+    a ``gram_mttkrp`` (kind "mttkrp" / "gram") or ``rel_error`` ("error") call, as dicts
+    ``{job, BM, tiles_m, tiles_n, nsplit, kchunk}`` (job: one of CP_JOB_*). Only the
+    alignment of ``w_address`` matters; nothing is read and no device is needed.
+    ``raw=True`` returns the status code instead of raising on a refusal."""
+    n = len(layers)
+    arr = (CpLayer * max(n, 1))()
+    for L, (dims, R, w_address) in zip(arr, layers):
+        L.W = w_address
+        L.ndim, L.R = len(dims), R
+        for d in range(3):
+            L.factors[d] = 0x1000 if d < len(dims) else None
+            L.dims[d] = dims[d] if d < len(dims) else 0
+    out = (ctypes.c_int32 * (6 * max(n, 1)))()
+    rc = load().admmq_debug_cp_plan(arr, n, mode, CP_KINDS[kind], out)
+    if raw:
+        return rc
+    check(rc, "debug_cp_plan")
+    keys = ("job", "BM", "tiles_m", "tiles_n", "nsplit", "kchunk")
+    return [dict(zip(keys, (int(v) for v in out[6 * l:6 * l + 6]))) for l in range(n)]
 
 
 def shared_stage2_count(reset: bool = False) -> int:

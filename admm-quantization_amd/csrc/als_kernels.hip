@@ -552,7 +552,7 @@ static int plan_als(const admmq_cp_layer* layers, int n, int mode, int kind, dou
     } else {   // reconstruction error: rec (I x J*K) = A . (B ⊙ C)^T
       j.R = R; j.M = I; j.N = J * Kd; j.K2 = Kd;
       j.X = L.factors[0]; j.Y = L.factors[1]; j.Z = L.ndim == 3 ? L.factors[2] : nullptr;
-      j.eout = eout + l;
+      j.eout = eout ? eout + l : nullptr;   // the sizing pass has no result array
       const int bi = bm_index(I), BM = bi ? 64 : 32;
       j.unit0 = (int)pl.units[bi][2].size();
       for (int a = 0; a < cdiv(I, BM); ++a)
@@ -687,6 +687,25 @@ int32_t admmq_cp_rel_error(const admmq_cp_layer* layers, int32_t n, double* out,
   int rc = plan_als(layers, n, 0, 2, out, workspace, pl, err);
   if (!rc) rc = run_als(pl, workspace, workspace_bytes, static_cast<hipStream_t>(stream), err);
   if (rc) return set_error(rc, ("cp_rel_error: " + err).c_str());
+  return ADMMQ_OK;
+}
+
+// diagnostics: the form plan_als gives every layer, so a test can assert the kernel it is
+// there for. Plans as the sizing pass does (base == nullptr): host only, no device call,
+// W is looked at for its alignment only.
+int32_t admmq_debug_cp_plan(const admmq_cp_layer* layers, int32_t n, int32_t mode, int32_t kind, int32_t* out) {
+  if (n < 0 || (n > 0 && (!layers || !out))) return set_error(ADMMQ_ERR_ARG, "cp_plan: bad arguments");
+  if (kind < 0 || kind > 2) return set_error(ADMMQ_ERR_ARG, "cp_plan: kind must be 0 (MTTKRP), 1 (Gram) or 2 (error)");
+  AlsPlan pl;
+  std::string err;
+  const int rc = plan_als(layers, n, kind == 2 ? 0 : mode, kind, nullptr, nullptr, pl, err);
+  if (rc) return set_error(rc, ("cp_plan: " + err).c_str());
+  for (int l = 0; l < n; ++l) {
+    const AlsJob& j = pl.jobs[l];
+    const int BM = bm_index(j.M) ? 64 : 32;
+    const int32_t row[6] = {j.kind, BM, cdiv(j.M, BM), cdiv(j.N, kAlsBN), std::max(j.nsplit, 1), j.kchunk};
+    std::memcpy(out + 6 * l, row, sizeof(row));
+  }
   return ADMMQ_OK;
 }
 

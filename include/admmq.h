@@ -696,6 +696,15 @@ int32_t admmq_cp_colnorm64(const double* A, int64_t rowsA, const double* B, int6
  * read of a device counter: synchronises); reset != 0 zeroes it. -1 on a HIP error. */
 int64_t admmq_debug_shared_stage2_count(int32_t reset);
 
+/* Diagnostics: the kernel form the ALS planner gives every layer of an admmq_cp_gram_mttkrp
+ * (kind 0: F, kind 1: G) or admmq_cp_rel_error (kind 2; mode ignored) call. Host only: no device
+ * call, W and the factors are never read (W's address decides the 16-byte-aligned spatial form).
+ * out: n x 6 int32 {job kind (0 generic MTTKRP, 1 Gram, 2 error, 3 spatial MTTKRP), tile rows BM
+ * (32 / 64), row tiles, column tiles, nsplit (partial planes summed by k_als_reduce; 1: none),
+ * kchunk (reduction rows per K chunk of the generic MTTKRP, else 0)}. Returns the planner's
+ * refusal (ADMMQ_ERR_ARG: bad layer, mode out of range, Khatri-Rao index range >= 2^24). */
+int32_t admmq_debug_cp_plan(const admmq_cp_layer* layers, int32_t n, int32_t mode, int32_t kind, int32_t* out);
+
 /* Library version (major*10000 + minor*100 + patch) and the last error text of this thread. */
 int32_t admmq_version(void);
 const char* admmq_last_error(void);

@@ -229,13 +229,9 @@ def _rel_case(dims, R, kind):
 
 
 def _banded(torch, dev, a, band):
-    """`a` on the device as the middle of a flat buffer with `band` NaNs on both sides
-    (band 64: 16-byte aligned; band 65: 4-byte aligned only). Returns (view, buffer)."""
-    buf = torch.full((a.size + 2 * band,), float("nan"), dtype=torch.float32, device=dev)
-    v = buf[band:band + a.size].view(a.shape)
-    v.copy_(torch.from_numpy(a))
-    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * band) % 16
-    return v, buf
+    """`a` inside NaN guard bands (shared with tests/test_gpu_als_forms.py): (view, buffer)."""
+    from oracle import als_bound
+    return als_bound.banded(torch, dev, a, band)
 
 
 @pytest.mark.parametrize("band", [64, 65])

@@ -5,7 +5,8 @@
  * host-only planners (workspace-size queries: problem layout, tile lists and their CU
  * ordering, stage-1 chunking, the finalize / small-job plans; the search form and the
  * run's launch schedule through admmq_debug_admm_run_schedule) over the bench configs
- * C3 / C4 / C5 and seeded random batches, and the argument-validation error paths. Any
+ * C3 / C4 / C5 and seeded random batches, the ALS planner through admmq_debug_cp_plan over
+ * random CP batches, and the argument-validation error paths. Any
  * heap / stack overflow or UB in that code aborts with a sanitizer report.
  * usage: build/asan/asan_host_check   (exit 0 = clean) */
 #include <stdint.h>
@@ -484,6 +485,46 @@ int main(void) {
       fails += IDW(&qm, 512, 1141, &a8, 2, 2, ti, 3, 1, 1, NULL, yc, &a6, &a8, 16) != ADMMQ_ERR_WORKSPACE;
 #undef IDW
     }
+  }
+  /* the ALS planner (csrc/als_kernels.hip plan_als) through its host-only plan query and the
+   * workspace size: random 2-way / 3-way batches (9-tap layers, aligned and not, among them), every
+   * kind and mode, and the refusals (made-up addresses: nothing is read) */
+  for (int t = 0; t < 300; ++t) {
+    admmq_cp_layer L[12] = {{0}};
+    int32_t out[12 * 6];
+    const int n = rnd(1, 12), nd = t % 3 == 0 ? 2 : 3;
+    for (int i = 0; i < n; ++i) {
+      L[i].W = (const float*)(uintptr_t)(0x100000 + 4 * rnd(0, 3));
+      L[i].ndim = nd; L[i].R = rnd(1, 300);
+      for (int d = 0; d < nd; ++d) { L[i].factors[d] = (const float*)0x1000; L[i].dims[d] = rnd(1, t % 7 == 0 ? 1200 : 150); }
+      if (nd == 3 && rnd(0, 1)) { L[i].dims[2] = 9; L[i].dims[1] = 4 * rnd(1, 40); L[i].dims[0] = 4 * rnd(1, 40); }
+    }
+    for (int mode = 0; mode < nd; ++mode) {
+      fails += admmq_cp_workspace_size(L, n, mode) == 0;
+      for (int kind = 0; kind < 3; ++kind) {
+        fails += admmq_debug_cp_plan(L, n, mode, kind, out) != ADMMQ_OK;
+        for (int i = 0; i < n; ++i) {
+          const int32_t* o = out + 6 * i;
+          fails += (kind ? o[0] != kind : (o[0] != 0 && o[0] != 3)) || (o[1] != 32 && o[1] != 64) || o[2] < 1 || o[3] < 1 || o[4] < 1;
+        }
+      }
+    }
+    fails += admmq_debug_cp_plan(L, n, nd, 0, out) != ADMMQ_ERR_ARG;
+  }
+  {
+    admmq_cp_layer L = {(const float*)0x100000, {(const float*)0x1000, (const float*)0x1000, (const float*)0x1000},
+                        NULL, NULL, {4096, 4096, 2}, 3, 3};
+    int32_t out[6];
+    fails += admmq_debug_cp_plan(&L, 1, 2, 0, out) != ADMMQ_ERR_ARG;   /* Khatri-Rao range 2^24 */
+    L.dims[1] = 4095;
+    fails += admmq_debug_cp_plan(&L, 1, 2, 0, out) != ADMMQ_OK;
+    fails += admmq_debug_cp_plan(&L, 1, 0, 3, out) != ADMMQ_ERR_ARG;
+    fails += admmq_debug_cp_plan(NULL, 1, 0, 0, out) != ADMMQ_ERR_ARG;
+    fails += admmq_debug_cp_plan(&L, 1, 0, 0, NULL) != ADMMQ_ERR_ARG;
+    L.ndim = 4;
+    fails += admmq_debug_cp_plan(&L, 1, 0, 0, out) != ADMMQ_ERR_ARG;
+    L.ndim = 3; L.R = 0;
+    fails += admmq_debug_cp_plan(&L, 1, 0, 0, out) != ADMMQ_ERR_ARG;
   }
   printf("last error: %s\n", admmq_last_error());
   printf("%s (%d failures)\n", fails ? "FAIL" : "OK", fails);
