@@ -38,7 +38,7 @@ from torch import nn
 from . import _lib
 from .packed import (PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
                      _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
-                     packed_gemm, packed_lrgemm, packed_rowsums, packed_taps_int, taps_kp)
+                     packed_gemm, packed_gemv, packed_lrgemm, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -146,11 +146,19 @@ class _PackedWeight(nn.Module):
 
 
 class PackedLinear(_PackedWeight):
-    """``nn.Linear`` on packed codes: ``x [..., in] -> [..., out]``."""
+    """``nn.Linear`` on packed codes: ``x [..., in] -> [..., out]``. ``skinny`` (an attribute, default ``False``, not
+    part of the state dict): send an input of at most ``GEMV_N_MAX`` rows to the decode kernel ``packed_gemv``
+     while the layer has no output quantizer; every other input takes the default route."""
     _layout = 1
+    skinny = False
 
     def forward(self, x):
+        if self.skinny and self._act is None and skinny_rows(x, self.in_features):
+            return packed_gemv(self.codes, self._meta, self.transpose, self.out_features, self.in_features, x, self.bias)
         return self._gemm(x)
+
+    def extra_repr(self):
+        return super().extra_repr() + (", skinny=True" if self.skinny else "")
 
 
 class PackedLowRankLinear(_PackedWeight):

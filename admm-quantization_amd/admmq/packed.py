@@ -19,6 +19,10 @@ fixed-range quantizer's level clamped to ``0 .. 2^bits - 1``), and ``packed_line
 ``packed_depthwise_conv1x1_int`` is the fused depthwise + 1x1 stage on such codes (``k_packed_idwgemm``: an
 int8 stencil over the codes feeds the int8 MFMA).
 
+``packed_gemv`` is the decode-shape product: at most ``GEMV_N_MAX`` rows of float32 / bfloat16 / float16
+activations through a packed weight with plain FMAs from the codes (``k_packed_gemv`` / ``k_packed_gemv_t``: no
+MFMA tile, no LDS weight image). ``packed_linear(..., skinny=True)`` routes to it.
+
 ``PackedLowRank`` is the deployable form of ``admmq.lowrank``'s ``W ~ W_q + W_r``: ``W_q`` as packed
 codes, ``W_r`` as its thin factors ``L [M, r]``, ``Rt [r, K]``; ``packed_lowrank_linear`` evaluates
 ``x (W_q + L Rt)^T (+ bias)`` from the three in one GEMM (``k_lr_down`` + ``k_packed_lrgemm``).
@@ -37,7 +41,7 @@ import torch
 from . import _lib
 
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
-           "packed_gemm", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
+           "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
            "packed_lrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
@@ -224,6 +228,8 @@ def dequantize_packed(packed: Sequence[PackedTensor]) -> List[torch.Tensor]:
 
 
 HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}   # ADMMQ_DT_F16 / ADMMQ_DT_BF16 (include/admmq.h)
+GEMV_DTYPES = {torch.float32: 0, **HALF_DTYPES}        # ... and ADMMQ_DT_F32
+GEMV_N_MAX = 8                                         # ADMMQ_GEMV_N_MAX
 
 
 # --- the call frame of the packed GEMM wrappers ---------------------------------
@@ -417,6 +423,54 @@ def _packed_hgemm(codes, meta_words, transpose, M, K, x, x_layout, bias, act, ou
 _opaque_packed_hgemm = torch.compiler.disable(_packed_hgemm)
 
 
+def packed_gemv(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int, x: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
+    """The skinny product for decode shapes (``admmq_packed_gemv``): ``x [..., K] -> [..., M]`` with
+    at most ``GEMV_N_MAX`` rows after flattening the leading dimensions, ``x`` in float32, bfloat16 or float16,
+    ``W`` as for ``packed_gemm``. The result has ``x``'s dtype, or float32 with ``out_dtype=torch.float32``; ``bias``
+    may be float32 or of ``x``'s dtype. Every output's bits depend on its own row of ``x`` only (not on the row
+    count); they are not ``packed_gemm``'s bits (another sum order, the same error bound). Inference only."""
+    _require_gpu("packed_gemv", "codes and activations", x, codes)
+    if x.dtype not in GEMV_DTYPES:
+        raise TypeError(f"admmq: packed_gemv: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+        raise ValueError(f"packed_gemv: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+    _inference_only("packed_gemv", x, "x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_gemv(codes, meta_words, transpose, M, K, x, bias, out_dtype)
+    M, K = int(M), int(K)
+    oshape, _, N, xc = _gemm_geometry("packed_gemv", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    if N > GEMV_N_MAX:
+        raise ValueError(f"packed_gemv: x must hold 1..{GEMV_N_MAX} rows, got {N}")
+    out_f32 = out_dtype == torch.float32
+    if bias is not None:
+        _require_gpu("packed_gemv", "bias", bias)
+        if bias.dtype != torch.float32 and bias.dtype != x.dtype:
+            raise TypeError(f"admmq: packed_gemv: bias must be float32 or x's dtype {x.dtype}, got {bias.dtype}")
+        bias = bias.detach().float()   # (exact)
+    if _lib.use_ops():   # torch.ops.admmq.packed_gemv (csrc/torch_ops.cpp) -> admmq_packed_gemv
+        return _lib.ops().packed_gemv(codes, meta_words, bool(transpose), M, K, xc, bias, out_f32)
+    lib = _lib.load()
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_gemv", bias, M)
+    xdt = GEMV_DTYPES[x.dtype]
+    y = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    nbytes = lib.admmq_packed_gemv_workspace_size(ctypes.byref(meta), 1 if transpose else 0, M, K, N)
+    ws = _lib.workspace(nbytes, x.device) if nbytes else None   # (the one-launch plan needs none)
+    rc = lib.admmq_packed_gemv(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc), xdt, N,
+                               _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws), nbytes,
+                               _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_gemv")
+    return y
+
+
+_opaque_packed_gemv = torch.compiler.disable(packed_gemv)
+
+
+def skinny_rows(x, K: int) -> bool:
+    """Whether ``x [..., K]`` holds at most ``GEMV_N_MAX`` rows: the shapes ``skinny=True`` sends to ``packed_gemv``."""
+    return isinstance(x, torch.Tensor) and x.dim() >= 1 and x.shape[-1] == K and 0 < x.numel() <= GEMV_N_MAX * K
+
+
 def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
     _validate(p.bits, p.qscheme)
     if len(p.shape) != 2:
@@ -431,11 +485,18 @@ def _weight_dims(p: "PackedTensor", transpose: bool) -> Tuple[int, int]:
 
 
 def packed_linear(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
-                  transpose: bool = False, act=None, out_dtype=None) -> torch.Tensor:
+                  transpose: bool = False, act=None, out_dtype=None, skinny: bool = False) -> torch.Tensor:
     """``F.linear(x, W, bias)`` with ``W = p.dequantize()`` (``transpose``: its transpose) computed
     from the codes: ``x [..., K] -> [..., M]``. A bfloat16 / float16 ``x`` gives a result of its dtype
-    (float32 with ``out_dtype=torch.float32``), as ``packed_gemm``. Inference only."""
+    (float32 with ``out_dtype=torch.float32``), as ``packed_gemm``. ``skinny=True`` sends an ``x`` of at most
+    ``GEMV_N_MAX`` rows to ``packed_gemv`` (the decode kernel: faster there, another sum order, so other bits
+    than the default route's) and any other ``x`` down the default route; it cannot be combined with ``act``.
+    Inference only."""
+    if skinny and act is not None:
+        raise ValueError("packed_linear: skinny=True cannot be combined with act= (the skinny GEMV has no output quantizer)")
     M, K = _weight_dims(p, transpose)
+    if skinny and skinny_rows(x, K):
+        return packed_gemv(p.codes, _meta_words(p), transpose, M, K, x, bias, out_dtype)
     return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 1, bias, act, out_dtype)
 
 

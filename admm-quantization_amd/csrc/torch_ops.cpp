@@ -10,6 +10,7 @@
 //                                     (no reference counterpart; DESIGN.md "Packed codes")
 //   admmq::packed_gemm             a packed weight times float32 activations
 //   admmq::packed_hgemm            a packed weight times bfloat16 / float16 activations
+//   admmq::packed_gemv             the skinny GEMV of a packed weight for 1..8 rows of x
 //   admmq::packed_lrgemm           packed codes + low-rank factors times float32 activations, one GEMM
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
@@ -743,6 +744,53 @@ at::Tensor packed_hgemm_meta(const at::Tensor& codes, const at::Tensor& meta_wor
   return at::empty(packed_gemm_shape(x, M, K, x_layout), out_f32 ? x.options().dtype(at::kFloat) : x.options());
 }
 
+// --- packed_gemv ----------------------------------------------------------------------------
+// The skinny GEMV of a packed weight (admmq_packed_gemv): x [..., K] with at most
+// ADMMQ_GEMV_N_MAX rows in float32, bfloat16 or float16 -> [..., M] of x's dtype, or float32 with
+// out_f32. bias: float32. Inference only.
+std::vector<int64_t> packed_gemv_shape(const at::Tensor& x, int64_t M, int64_t K) {
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16,
+              "admmq: packed_gemv: x must be float32, float16 or bfloat16, got ", x.scalar_type());
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_gemv: M and K must be positive");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "admmq: packed_gemv: x must be [..., ", K, "], got ", x.sizes());
+  const int64_t N = x.numel() / K;
+  TORCH_CHECK(N >= 1 && N <= ADMMQ_GEMV_N_MAX, "admmq: packed_gemv: x must hold 1..", ADMMQ_GEMV_N_MAX, " rows, got ", N);
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  shape.back() = M;
+  return shape;
+}
+
+at::Tensor packed_gemv_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, const std::optional<at::Tensor>& bias, bool out_f32) {
+  TORCH_CHECK(x.is_cuda(), "admmq: x must live on a ROCm GPU (the MI355X path has no CPU implementation)");
+  check_inference_only(x.requires_grad(), "packed_gemv", "x");
+  check_codes(codes, "packed_gemv");
+  check_same_device(codes, x, "codes");
+  check_meta_words(meta_words, "packed_gemv");
+  const std::vector<int64_t> oshape = packed_gemv_shape(x, M, K);
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_gemv", meta);
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor bc = bias_of(bias, x, M, "packed_gemv", false);
+  const int64_t N = xc.numel() / K;
+  const int32_t xdt = x.scalar_type() == at::kFloat ? ADMMQ_DT_F32 : x.scalar_type() == at::kHalf ? ADMMQ_DT_F16 : ADMMQ_DT_BF16;
+  at::Tensor y = at::empty(oshape, out_f32 ? xc.options().dtype(at::kFloat) : xc.options());
+  const size_t nbytes = admmq_packed_gemv_workspace_size(&meta, trans_w ? 1 : 0, M, K, N);
+  at::Tensor ws;   // (the one-launch plan needs none: no allocation)
+  if (nbytes > 0) ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_gemv(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr(), xdt, N, f32_or_null(bc),
+                             y.data_ptr(), out_f32 ? ADMMQ_DT_F32 : xdt, nbytes > 0 ? ws.data_ptr() : nullptr,
+                             nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
+           "packed_gemv");
+  return y;
+}
+
+at::Tensor packed_gemv_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w, int64_t M, int64_t K,
+                            const at::Tensor& x, const std::optional<at::Tensor>& bias, bool out_f32) {
+  return at::empty(packed_gemv_shape(x, M, K), out_f32 ? x.options().dtype(at::kFloat) : x.options());
+}
+
 // --- packed_lrgemm --------------------------------------------------------------------------
 // y = x (D + L Rt)^T (+ bias): D the [M, K] de-quantization of `codes`, L [M, r], Rt [r, K]
 // (admmq_packed_lrgemm). x [..., K] -> [..., M]. Inference only.
@@ -1019,6 +1067,8 @@ TORCH_LIBRARY(admmq, m) {
         "Tensor? bias=None) -> Tensor");
   m.def("packed_hgemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
         "Tensor? bias=None, bool out_f32=False) -> Tensor");
+  m.def("packed_gemv(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, Tensor? bias=None, "
+        "bool out_f32=False) -> Tensor");
   m.def("packed_lrgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor x, Tensor? bias=None) "
         "-> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
@@ -1053,6 +1103,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("dequantize_packed", &dequantize_packed_cuda);
   m.impl("packed_gemm", &packed_gemm_cuda);
   m.impl("packed_hgemm", &packed_hgemm_cuda);
+  m.impl("packed_gemv", &packed_gemv_cuda);
   m.impl("packed_lrgemm", &packed_lrgemm_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
@@ -1076,6 +1127,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("dequantize_packed", &dequantize_packed_meta);
   m.impl("packed_gemm", &packed_gemm_meta);
   m.impl("packed_hgemm", &packed_hgemm_meta);
+  m.impl("packed_gemv", &packed_gemv_meta);
   m.impl("packed_lrgemm", &packed_lrgemm_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);

@@ -471,6 +471,55 @@ int32_t admmq_packed_hgemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
                            const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Skinny packed GEMV: decode-shape linear layers straight from the codes,
+ *   y[c, m] = sum_k W[m, k] x[c, k] (+ bias[m]),   c = 0 .. N-1,   1 <= N <= ADMMQ_GEMV_N_MAX
+ * with x [N, K] and y [N, M] row-major (the linear layout only), W = D (trans_w 0, the packed
+ * tensor is [M, K]) or D^T (trans_w 1, it is [K, M]), the code stream and the HOST meta record
+ * admmq_packed_gemm's. x_dtype is ADMMQ_DT_F32, ADMMQ_DT_F16 or ADMMQ_DT_BF16; y_dtype is
+ * ADMMQ_DT_F32 or x_dtype; bias (may be NULL) is float32. No MFMA and no LDS weight image
+ * (k_packed_gemv, k_packed_gemv_t; k_packed_gemv_reduce where K is split over workgroups).
+ * Arithmetic: the weight is an exact integer in float32 and its scale is applied behind the sum.
+ *   mse-minmax, symmetric, affine: a = (u - q) - zero_point (q = 2^(bits-1); zero_point 0
+ *   unless affine), converted to float32
+ *     S = a float32 sum of the terms fmaf(a[m, k], x[c, k], .), a half x widened to float32
+ *     exactly;  y32 = (S * scale) + bias[m]
+ *   tensor_minmax (bits >= 2): the operand is u (0 .. 255)
+ *     y32 = ((S_u * rng) / n + mn * S_x) + bias[m],  n = float(2^bits - 1)
+ *     with S_x the column's sum of x, formed in the same order as S_u.
+ * Every operation other than the fused multiply-adds is a separately rounded float32 one. y is
+ * y32, or y32 rounded once to nearest even to x_dtype. The order in which the K terms of one
+ * output are added is a fixed function of (K, bits, trans_w) and of the planner's split of K,
+ * which is a function of (M, K, trans_w): with ks the k per range and ns = ceil(K / ks) ranges,
+ *   trans_w 0: a range is cut into chunks of 1024 k and a chunk into 32 runs of 32 k; lane l of
+ *     32 adds run l of every chunk from zero in increasing k, the 32 lanes meet as
+ *     t(l0..l15) + t(l16..l31), t the tree v += v[l-1]; v += v[l-2]; v += v[l-4]; v += v[l-8]
+ *     read at its last lane (a lane without that neighbour adds 0);
+ *   trans_w 1: a range is cut into chunks of 512 k and a chunk into four quarters; quarter w of
+ *     every chunk is added from zero in increasing k, and the four meet as ((s0 + s1) + s2) + s3;
+ *   the ranges are added in increasing k, ((p_0 + p_1) + ...) + p_{ns-1}.
+ * A k past the range or past K adds fmaf(a, 0, s) = s. So an output's bits depend only on its
+ * own row of x, the weight and bias[m]: the same at every N in 1..8, at every column position
+ * and on every call. No atomics, and no workgroup waits for another. The bits are NOT those of
+ * admmq_packed_gemm / admmq_packed_hgemm on the same operands (a different sum order); both
+ * meet the same error bound. Half subnormal inputs are outside the contract.
+ * codes: device, 16-byte aligned; x and y: device, aligned to their element (2 or 4 bytes) - no
+ * wider alignment is needed; bias: float aligned. Limits: admmq_packed_gemm's on M, K and M*K.
+ * ADMMQ_ERR_ARG for NULL codes / meta / x / y, non-positive M or K or sizes past the limits, N
+ * outside 1..ADMMQ_GEMV_N_MAX, what admmq_packed_gemm refuses of a meta record, trans_w other
+ * than 0 or 1, for a half x_dtype an affine record whose -q - zero_point or q - 1 - zero_point is
+ * not an integer exact in x_dtype (magnitude above 256 for bfloat16, 2048 for float16), a dtype
+ * pair other than the above, misaligned pointers; ADMMQ_ERR_WORKSPACE for a short workspace -
+ * all before any launch, each with its own admmq_last_error text.
+ * admmq_packed_gemv_workspace_size depends on its arguments only (of meta: the scheme): 0 for a
+ * NULL meta or arguments out of range and when the plan is one launch (ns = 1); else the
+ * float32 partial sums 4 ns N M bytes, plus 4 ns N bytes for tensor_minmax (the ranges' sums of
+ * x). No entry point allocates or synchronises. */
+#define ADMMQ_GEMV_N_MAX 8
+size_t admmq_packed_gemv_workspace_size(const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K, int64_t N);
+int32_t admmq_packed_gemv(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                          const void* x, int32_t x_dtype, int64_t N, const float* bias, void* y, int32_t y_dtype,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

@@ -272,6 +272,41 @@ int main(void) {
       fails += HG(c, &qm, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
       fails += HG(c, &qx, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 18 * 512 * 4 * 4) != ADMMQ_ERR_WORKSPACE;
 #undef HG
+      /* the skinny GEMV: the size query over random and named shapes (pure: asked twice), and every refusal
+       * before any launch */
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, t % 3 ? 6000 : 70000), K = rnd(1, t % 3 ? 6000 : 40000), N = rnd(1, 8);
+        const size_t w = admmq_packed_gemv_workspace_size(&qm, t & 1, M, K, N);
+        fails += w != admmq_packed_gemv_workspace_size(&qm, t & 1, M, K, N) || w % (4 * N * M) != 0;
+        fails += admmq_packed_gemv_workspace_size(&qx, t & 1, M, K, N) != w + w / M;
+      }
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 11008, 4096, 8) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 4096, 4096, 8) != (size_t)4 * 4 * 8 * 4096;
+      fails += admmq_packed_gemv_workspace_size(&qm, 1, 4096, 4096, 1) != (size_t)4 * 16 * 4096;
+      fails += admmq_packed_gemv_workspace_size(NULL, 0, 8, 2048, 4) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 2, 8, 2048, 4) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 0, 2048, 4) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 8, 2048, 0) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 8, 2048, 9) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, (int64_t)1 << 40, 8, 8) != 0;
+      fails += admmq_packed_gemv_workspace_size(&qm, 0, 8, 2048, 4) != 2 * 4 * 8 * 4;
+#define GV(cc, mm, tr, M, K, xx, xd, N, bb, yy, yd, wsp, wsb) admmq_packed_gemv(cc, mm, tr, M, K, xx, xd, N, bb, yy, yd, wsp, wsb, NULL)
+      fails += GV(NULL, &qm, 0, 8, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 8, hx, BF, 0, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 8, hx, BF, 9, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 2, 8, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 8, hx, HF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 8, (const void*)0x10001, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 8, hx, BF, 4, (const float*)0x30002, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 3;
+      fails += GV(c, &q2, 0, 8, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 200;
+      fails += GV(c, &q2, 0, 8, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, (int64_t)1 << 30, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += GV(c, &qm, 0, 8, 2048, hx, BF, 4, NULL, hy, BF, ws, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += GV(c, &qm, 0, 8, 2048, hx, BF, 4, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+      fails += GV(c, &qx, 0, 8, 2048, hx, BF, 4, NULL, hy, BF, ws, 2 * 4 * 8 * 4) != ADMMQ_ERR_WORKSPACE;
+#undef GV
     }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
