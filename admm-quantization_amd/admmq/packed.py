@@ -26,6 +26,8 @@ MFMA tile, no LDS weight image). ``packed_linear(..., skinny=Tru
 ``PackedLowRank`` is the deployable form of ``admmq.lowrank``'s ``W ~ W_q + W_r``: ``W_q`` as packed
 codes, ``W_r`` as its thin factors ``L [M, r]``, ``Rt [r, K]``; ``packed_lowrank_linear`` evaluates
 ``x (W_q + L Rt)^T (+ bias)`` from the three in one GEMM (``k_lr_down`` + ``k_packed_lrgemm``).
+``packed_lrgemv`` is its decode-shape product (``k_lr_down_gemv`` + ``k_packed_lrgemv``, float32 / bfloat16 /
+float16 activations); ``packed_lowrank_linear(..., skinny=True)`` routes to it.
 
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
@@ -44,7 +46,7 @@ __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed"
            "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
-           "packed_lrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
+           "packed_lrgemm", "packed_lrgemv", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -1066,12 +1068,71 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
 _opaque_packed_lrgemm = torch.compiler.disable(packed_lrgemm)
 
 
+def packed_lrgemv(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
+                  x: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
+    """The skinny quant + low-rank product for decode shapes (``admmq_packed_lrgemv``):
+    ``y = x (D + L Rt)^T (+ bias)`` for ``x [..., K]`` with at most ``GEMV_N_MAX`` rows after flattening the leading
+    dimensions, ``x`` in float32, bfloat16 or float16 - the half types run the same fused kernels, not a
+    composition. ``L [M, r]`` and ``Rt [r, K]`` are both float32 or both of a 16-bit ``x``'s dtype (a module after
+    ``.half()``); ``t = x Rt^T`` stays float32 either way. The result has ``x``'s dtype, or float32 with
+    ``out_dtype=torch.float32``; ``bias`` may be float32 or of ``x``'s dtype. Every output's bits depend on its own
+    row of ``x`` only; with ``L = 0`` they are ``packed_gemv``'s. Not ``packed_lrgemm``'s bits (another sum order).
+    Inference only."""
+    _require_gpu("packed_lrgemv", "codes, factors and activations", x, codes, L, Rt)
+    if x.dtype not in GEMV_DTYPES:
+        raise TypeError(f"admmq: packed_lrgemv: x must be float32, bfloat16 or float16, got {x.dtype}")
+    if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+        raise ValueError(f"packed_lrgemv: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+    _inference_only("packed_lrgemv", x, "x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_lrgemv(codes, meta_words, M, K, L, Rt, x, bias, out_dtype)
+    M, K = int(M), int(K)
+    L, Rt = L.detach(), Rt.detach()
+    if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
+        raise ValueError(f"packed_lrgemv: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
+    if L.dtype != Rt.dtype or (L.dtype != torch.float32 and L.dtype != x.dtype):
+        raise TypeError(f"admmq: packed_lrgemv: L and Rt must both be float32 or both of x's dtype {x.dtype}, got "
+                        f"{L.dtype} and {Rt.dtype}")
+    r = int(L.shape[1])
+    if not 1 <= r <= RANK_MAX:
+        raise ValueError(f"packed_lrgemv: rank must be 1..{RANK_MAX}, got {r}")
+    oshape, _, N, xc = _gemm_geometry("packed_lrgemv", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    if N > GEMV_N_MAX:
+        raise ValueError(f"packed_lrgemv: x must hold 1..{GEMV_N_MAX} rows, got {N}")
+    out_f32 = out_dtype == torch.float32
+    if bias is not None:
+        _require_gpu("packed_lrgemv", "bias", bias)
+        if bias.dtype != torch.float32 and bias.dtype != x.dtype:
+            raise TypeError(f"admmq: packed_lrgemv: bias must be float32 or x's dtype {x.dtype}, got {bias.dtype}")
+        bias = bias.detach().float()   # (exact)
+    if _lib.use_ops():   # torch.ops.admmq.packed_lrgemv (csrc/torch_ops.cpp) -> admmq_packed_lrgemv
+        return _lib.ops().packed_lrgemv(codes, meta_words, M, K, L, Rt, xc, bias, out_f32)
+    lib = _lib.load()
+    Lc, Rc = L.contiguous(), Rt.contiguous()
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_lrgemv", bias, M)
+    xdt = GEMV_DTYPES[x.dtype]
+    y = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    ws = _lib.workspace(lib.admmq_packed_lrgemv_workspace_size(ctypes.byref(meta), M, K, N, r), x.device)
+    rc = lib.admmq_packed_lrgemv(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), GEMV_DTYPES[L.dtype], r,
+                                 _lib.ptr(xc), xdt, N, _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws),
+                                 ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_lrgemv")
+    return y
+
+
+_opaque_packed_lrgemv = torch.compiler.disable(packed_lrgemv)
+
+
 def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[torch.Tensor] = None,
-                          out_dtype=None) -> torch.Tensor:
+                          out_dtype=None, skinny: bool = False) -> torch.Tensor:
     """``F.linear(x, W_q + L Rt, bias)`` computed from ``p``'s codes and factors in one GEMM: ``x [..., K] ->
     [..., M]``. A bfloat16 / float16 ``x`` runs ``packed_lrgemm``'s composition (the half packed GEMM plus two
-    library products in float32; not a fused kernel). Inference only."""
+    library products in float32; not a fused kernel). ``skinny=True`` sends an ``x`` of at most ``GEMV_N_MAX`` rows
+    to ``packed_lrgemv`` (the decode kernels, fused for the half types too: faster there, another sum order, so
+    other bits than the default route's) and any other ``x`` down the default route. Inference only."""
     M, K, _ = _lowrank_dims(p)
+    if skinny and skinny_rows(x, K):
+        return packed_lrgemv(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
     return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
 
 

@@ -520,6 +520,52 @@ int32_t admmq_packed_gemv(const uint8_t* codes, const admmq_qmeta* meta, int32_t
                           const void* x, int32_t x_dtype, int64_t N, const float* bias, void* y, int32_t y_dtype,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Skinny quant + low-rank GEMV: admmq_packed_lrgemm's layer W ~ D + L Rt at
+ * decode shapes, for 1 <= N <= ADMMQ_GEMV_N_MAX rows of x [N, K] in float32, bfloat16 or float16,
+ * D [M, K] from codes (bits 1..8, the four tensor schemes, no transpose), L [M, r], Rt [r, K]
+ * row-major, 1 <= r <= 256:
+ *   t[c, j] = sum_k Rt[j, k] x[c, k]                  float32, one fmaf per term
+ *   v[c, m] = epilogue(sum_k a[m, k] x[c, k])         exactly admmq_packed_gemv's value (trans_w 0)
+ *                                                     before the bias
+ *   q[c, m] = sum_j L[m, j] t[c, j]                   float32, one fmaf per term, summed from zero
+ *   y[c, m] = (v + q) (+ bias[m])                     each add rounded once
+ * y is that float32 value, or it rounded once to nearest even to x_dtype. x is widened to float32
+ * exactly. L and Rt share one type f_dtype: ADMMQ_DT_F32, or a 16-bit x_dtype (widened exactly
+ * as they are read); t is float32 throughout and is never rounded to a half type.
+ * Sum orders, functions of (M, K, r, bits) and the plan alone, never of N:
+ *   t: K is cut into nsd ranges of ksd k (a multiple of 256), a range into steps of 256 k; lane l
+ *     of 64 adds k = 256 s + 4 l .. + 3 of every step s of the range from zero in increasing k;
+ *     the 64 lanes meet as ((T(0..15) + T(16..31)) + T(32..47)) + T(48..63), T the tree of
+ *     admmq_packed_gemv; the ranges are added in increasing k, ((t_0 + t_1) + ...) + t_{nsd-1};
+ *   v: admmq_packed_gemv's order on the same (M, K, bits), its ns ranges included;
+ *   q: lane l of 32 adds j = l, l + 32, ... in increasing j from zero; the 32 lanes meet as
+ *     T(0..15) + T(16..31).
+ * So an output has the same bits at every N, column position and call. With L = 0, q is an exact
+ * +0 and y equals admmq_packed_gemv's value, but for the sign of a zero without a bias.
+ * Extra roundings on the longest t / q path beside the K + r fused multiply-adds, the c of the
+ * forward bound |y - y64| <= 2^-23 [(K + 4)(|D||x| + |bias|) + (K + r + c) |L|(|Rt||x|)]:
+ * c = 29 = 15 (range adds of t, nsd <= 16) + 7 (t's lane tree, 4 + 3) + 5 (q's lane tree, 4 + 1)
+ * + 2 (v + q, + bias).
+ * Launches: k_lr_down_gemv (t, nsd ranges: no reduce launch, the consumer adds the images),
+ * k_packed_lrgemv (the code sum and the tail) and, where admmq_packed_gemv's plan splits K
+ * (ns > 1; the tail is then one more slice), k_packed_lrgemv_reduce. No atomics, and no workgroup
+ * waits for another.
+ * Pointers, limits and refusals are admmq_packed_gemv's, and: L, Rt device, aligned to their
+ * element; ADMMQ_ERR_ARG for NULL L / Rt, r outside 1..256, an f_dtype other than the above;
+ * ADMMQ_ERR_WORKSPACE for a NULL or short workspace (t always lives there) - all before any
+ * launch, each with its own admmq_last_error text.
+ * admmq_packed_lrgemv_workspace_size depends on its arguments only (of meta: the scheme): 0 for a
+ * NULL meta or arguments out of range, else 4 nsd N r bytes, plus where ns > 1
+ * 4 (ns + 1) N M bytes and 4 ns N for tensor_minmax. admmq_packed_lrgemv_plan writes
+ * out = (ns, nsd, launches) of (M, K, r) - a pure function; ADMMQ_ERR_ARG (and nothing written)
+ * for arguments out of range. */
+size_t admmq_packed_lrgemv_workspace_size(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int32_t r);
+int32_t admmq_packed_lrgemv_plan(const admmq_qmeta* meta, int64_t M, int64_t K, int32_t r, int32_t out[3]);
+int32_t admmq_packed_lrgemv(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const void* L,
+                            const void* Rt, int32_t f_dtype, int32_t r, const void* x, int32_t x_dtype, int64_t N,
+                            const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

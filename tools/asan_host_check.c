@@ -307,6 +307,61 @@ int main(void) {
       fails += GV(c, &qm, 0, 8, 2048, hx, BF, 4, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
       fails += GV(c, &qx, 0, 8, 2048, hx, BF, 4, NULL, hy, BF, ws, 2 * 4 * 8 * 4) != ADMMQ_ERR_WORKSPACE;
 #undef GV
+      /* the skinny quant + low-rank GEMV: the size and plan queries over random and named shapes (pure: asked
+       * twice; the size is the one the plan spells), and every refusal before any launch */
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, t % 3 ? 6000 : 70000), K = rnd(1, t % 3 ? 6000 : 40000), N = rnd(1, 8);
+        const int32_t r = rnd(1, 256);
+        int32_t pl[3] = {0, 0, 0}, pl2[3] = {0, 0, 0};
+        const size_t w = admmq_packed_lrgemv_workspace_size(&qm, M, K, N, r);
+        fails += admmq_packed_lrgemv_plan(&qm, M, K, r, pl) != ADMMQ_OK || admmq_packed_lrgemv_plan(&qx, M, K, r, pl2) != ADMMQ_OK;
+        fails += pl[0] != pl2[0] || pl[1] != pl2[1] || pl[2] != (pl[0] > 1 ? 3 : 2) || pl[0] < 1 || pl[0] > 16 || pl[1] < 1 || pl[1] > 16;
+        fails += w != admmq_packed_lrgemv_workspace_size(&qm, M, K, N, r);
+        fails += w != (size_t)4 * N * ((size_t)pl[1] * r + (pl[0] > 1 ? (size_t)(pl[0] + 1) * M : 0));
+        fails += admmq_packed_lrgemv_workspace_size(&qx, M, K, N, r) != w + (pl[0] > 1 ? (size_t)4 * pl[0] * N : 0);
+        fails += (pl[0] > 1) != (admmq_packed_gemv_workspace_size(&qm, 0, M, K, N) > 0);
+      }
+      {
+        int32_t pl[3] = {7, 7, 7};
+        fails += admmq_packed_lrgemv_plan(&qm, 4096, 4096, 64, pl) != ADMMQ_OK || pl[0] != 4 || pl[1] != 16 || pl[2] != 3;
+        fails += admmq_packed_lrgemv_plan(&qm, 5, 257, 1, pl) != ADMMQ_OK || pl[0] != 1 || pl[1] != 2 || pl[2] != 2;
+        fails += admmq_packed_lrgemv_plan(NULL, 8, 2048, 8, pl) != ADMMQ_ERR_ARG || admmq_packed_lrgemv_plan(&qm, 8, 2048, 8, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lrgemv_plan(&qm, 8, 2048, 0, pl) != ADMMQ_ERR_ARG || admmq_packed_lrgemv_plan(&qm, 8, 2048, 257, pl) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lrgemv_plan(&qm, 0, 2048, 8, pl) != ADMMQ_ERR_ARG || pl[1] != 2;
+      }
+      fails += admmq_packed_lrgemv_workspace_size(&qm, 8, 8, 4, 8) != 4 * 4 * 8;
+      fails += admmq_packed_lrgemv_workspace_size(NULL, 8, 2048, 4, 8) != 0;
+      fails += admmq_packed_lrgemv_workspace_size(&qm, 8, 2048, 0, 8) != 0;
+      fails += admmq_packed_lrgemv_workspace_size(&qm, 8, 2048, 9, 8) != 0;
+      fails += admmq_packed_lrgemv_workspace_size(&qm, 8, 2048, 4, 0) != 0;
+      fails += admmq_packed_lrgemv_workspace_size(&qm, 8, 2048, 4, 257) != 0;
+      fails += admmq_packed_lrgemv_workspace_size(&qm, (int64_t)1 << 40, 8, 8, 8) != 0;
+      const void* lp = (const void*)0x40000;
+      const void* rp = (const void*)0x50000;
+#define LV(cc, mm, M, K, ll, rr, fd, r, xx, xd, N, bb, yy, yd, wsp, wsb) \
+  admmq_packed_lrgemv(cc, mm, M, K, ll, rr, fd, r, xx, xd, N, bb, yy, yd, wsp, wsb, NULL)
+      fails += LV(NULL, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, NULL, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, NULL, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 0, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 9, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 0, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 257, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, HF, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, BF, 8, hx, F32, 4, NULL, hy, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, HF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, (const void*)0x40002, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, (const void*)0x10001, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, (const float*)0x30002, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 3;
+      fails += LV(c, &q2, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 200;
+      fails += LV(c, &q2, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, (int64_t)1 << 30, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * 4 * 8 - 1) != ADMMQ_ERR_WORKSPACE;
+      fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+      fails += LV(c, &qx, 8, 2048, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * (8 * 4 * 8 + 3 * 4 * 8 + 2 * 4) - 1) != ADMMQ_ERR_WORKSPACE;
+#undef LV
     }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
