@@ -153,6 +153,9 @@ def load() -> ctypes.CDLL:
         "admmq_packed_lrgemm": (I32, [P, P, I64, I64, P, P, I32, P, I64, P, P, P, S, P]),
         "admmq_packed_dwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),
         "admmq_packed_dwgemm": (I32, [P, P, I64, I64, P, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, S, P]),
+        "admmq_packed_hdwgemm_workspace_size": (S, [P, I64, I64, I64, I64, I32]),
+        "admmq_packed_hdwgemm": (I32, [P, P, I64, I64, P, I32, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, I32, P,
+                                       S, P]),
         "admmq_fixed_quantize": (I32, [P, P, I64, P, P]),
         "admmq_packed_gemm_act": (I32, [P, P, I32, I64, I64, P, I32, I64, I32, P, P, P, P, S, P]),
         "admmq_packed_dwgemm_act": (I32, [P, P, I64, I64, P, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P,

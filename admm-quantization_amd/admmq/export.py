@@ -18,7 +18,8 @@ Packed layers: ``load_packed_factors`` returns the ``PackedTensor`` factors them
 the CP builders accept them in place of float tensors: the 1x1 convs / linears then become
 ``PackedConv1x1`` / ``PackedLinear``, which keep the codes and run ``k_packed_gemm`` on them
 (inference only); no float32 copy of such a factor is ever made. ``fused=True`` replaces a
-3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``).
+3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``; on a
+bfloat16 / float16 input ``k_packed_hdwgemm``).
 ``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
 activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
 ``build_qlr_layer`` turns the ``PackedLowRank`` of ``admmq.lowrank`` (``W ~ W_q + L Rt``) into a
@@ -36,7 +37,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .packed import (PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
+from .packed import (HALF_DTYPES, PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
                      _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
                      packed_gemm, packed_gemv, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
@@ -250,7 +251,10 @@ class PackedDepthwiseConv1x1(_PackedWeight):
     (``k_packed_dwgemm``): ``x [n, R, H, W] -> [n, out, Ho, Wo]``. The weight ``A [out, R]`` stays
     packed; ``taps`` is a float32 buffer ``[kh kw, R]`` (the de-quantized ``C`` factor as it is:
     ``k k R`` values). The rank-``R`` tensor between the two stages is never written. Kernel
-    size, stride and padding travel in the extra state beside the weight's quantization."""
+    size, stride and padding travel in the extra state beside the weight's quantization. A bfloat16 /
+    float16 input runs ``k_packed_hdwgemm`` and gives an output of its dtype; after
+    ``module.half()`` the ``taps`` buffer is half and is read through one exact float32 copy. The two
+    quantizers need float32 activations."""
     _layout = 0
 
     def __init__(self, p: PackedTensor, taps: torch.Tensor, bias: Optional[torch.Tensor] = None, kernel_size=(3, 3),
@@ -263,6 +267,7 @@ class PackedDepthwiseConv1x1(_PackedWeight):
             raise TypeError(f"taps must be float32, got {taps.dtype}")
         self.register_buffer("taps", taps.detach().clone().to(self.codes.device).contiguous())
         self._mid_act = None   # quantizer of the depthwise stage's output (the reference's behind conv2)
+        self._taps32 = None    # (key, float32 copy) of a half taps buffer, for half inputs
 
     def set_mid_activation_quant(self, bits=None, min_val=None, max_val=None):
         """The fixed-range quantizer of the depthwise stage's output, applied as the kernel stages
@@ -282,9 +287,22 @@ class PackedDepthwiseConv1x1(_PackedWeight):
         a = state.get("mid_act")
         self._mid_act = (int(a[0]), float(a[1]), float(a[2])) if a else None
 
+    def _taps_f32(self):
+        """``taps`` as float32: the buffer itself, or (after ``.half()`` / ``.bfloat16()``) one exact upcast that is
+        kept while the buffer is unchanged - a forward launches no cast."""
+        t = self.taps
+        if t.dtype == torch.float32:
+            return t
+        key = (t.data_ptr(), t._version, t.dtype, t.device)
+        if self._taps32 is None or self._taps32[0] != key:
+            self._taps32 = (key, t.detach().float())
+        return self._taps32[1]
+
     def forward(self, x):
-        return packed_dwgemm(self.codes, self._meta, self.out_features, self.in_features, x, self.taps, self.kernel_size,
-                             self.stride, self.padding, self.bias, self._act_arg(self._act), self._act_arg(self._mid_act))
+        half = isinstance(x, torch.Tensor) and x.dtype in HALF_DTYPES
+        return packed_dwgemm(self.codes, self._meta, self.out_features, self.in_features, x,
+                             self._taps_f32() if half else self.taps, self.kernel_size, self.stride, self.padding,
+                             self.bias, self._act_arg(self._act), self._act_arg(self._mid_act))
 
     def extra_repr(self):
         m = "" if self._mid_act is None else \

@@ -890,16 +890,24 @@ def packed_depthwise_conv1x1_int(xq: QuantizedActivation, C_or_image, p: "Packed
 
 def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, x: torch.Tensor, taps: torch.Tensor,
                   kernel_size, stride=1, padding=0, bias: Optional[torch.Tensor] = None, act=None,
-                  mid_act=None) -> torch.Tensor:
+                  mid_act=None, out_dtype=None) -> torch.Tensor:
     """Depthwise ``kernel_size`` convolution of ``x [n, K, H, W]`` by ``taps [kh kw, K]`` followed by
     the 1x1 convolution by the ``[M, K]`` de-quantization of ``codes`` (+ ``bias``), in one kernel
     (``k_packed_dwgemm``): ``-> [n, M, Ho, Wo]``; the ``K``-channel intermediate is never written.
     ``mid_act`` / ``act = (bits, min_val, max_val)``: fixed-range quantizers of the depthwise stage's
     output (applied as it is staged; padding stays 0) and of the result (``admmq_packed_dwgemm_act``).
+    A ``torch.bfloat16`` / ``torch.float16`` ``x`` runs on the 16-bit MFMA (``k_packed_hdwgemm``):
+    the tap sums are formed in float32 and rounded once to ``x``'s dtype, and the result has the bits of the half
+    ``packed_gemm`` on them, in ``x``'s dtype or in float32 with ``out_dtype=torch.float32``; ``taps`` and ``bias``
+    may be float32 or of ``x``'s dtype; ``act`` / ``mid_act`` are not available there.
     Inference only: an ``x`` that requires grad is refused while grad mode is on."""
     _require_gpu("packed_dwgemm", "codes, taps and activations", x, codes, taps)
+    if x.dtype in HALF_DTYPES:
+        return _packed_hdwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act, out_dtype)
     _lib.require_device(x)
     _lib.require_device(taps)
+    if out_dtype is not None and out_dtype != torch.float32:
+        raise ValueError(f"packed_dwgemm: a float32 x gives a float32 result, not out_dtype={out_dtype}")
     _inference_only("packed_dwgemm", x, "x")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
         return _opaque_packed_dwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act)
@@ -941,16 +949,70 @@ def packed_dwgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
 _opaque_packed_dwgemm = torch.compiler.disable(packed_dwgemm)
 
 
+def _half_or_f32(who: str, name: str, t, x: torch.Tensor) -> torch.Tensor:
+    """The GPU tensor ``t`` (float32 or of ``x``'s half dtype) detached and as float32 (exact)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"admmq: expected a torch.Tensor, got {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise RuntimeError("admmq: tensors must live on a ROCm GPU (device 'cuda'); the MI355X path has "
+                           "no CPU implementation")
+    if t.dtype != torch.float32 and t.dtype != x.dtype:
+        raise TypeError(f"admmq: {who}: {name} must be float32 or x's dtype {x.dtype}, got {t.dtype}")
+    return t.detach().float()
+
+
+def _packed_hdwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act, out_dtype):
+    """``packed_dwgemm`` on a bfloat16 / float16 ``x`` already known to be on the GPU (``admmq_packed_hdwgemm``)."""
+    if act is not None or mid_act is not None:
+        raise ValueError(f"packed_dwgemm: act= / mid_act= (the fixed-range quantizers) are not available for a {x.dtype} "
+                         "x; they need float32 activations")
+    if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+        raise ValueError(f"packed_dwgemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+    _inference_only("packed_dwgemm", x, "x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like the float32 call
+        return _opaque_packed_hdwgemm(codes, meta_words, M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act,
+                                      out_dtype)
+    M, K = int(M), int(K)
+    ks, st, pd = _pair(kernel_size, "kernel_size"), _pair(stride, "stride"), _pair(padding, "padding")
+    (kh, kw), (sh, sw), (ph, pw) = ks, st, pd
+    out_f32 = out_dtype == torch.float32
+    taps = _half_or_f32("packed_dwgemm", "taps", taps, x)
+    if bias is not None:
+        bias = _half_or_f32("packed_dwgemm", "bias", bias, x)
+    if _lib.use_ops():   # torch.ops.admmq.packed_hdwgemm (csrc/torch_ops.cpp) -> admmq_packed_hdwgemm
+        return _lib.ops().packed_hdwgemm(codes, meta_words, M, K, x, taps, kh, kw, sh, sw, ph, pw, bias, out_f32)
+    lib = _lib.load()
+    _dw_x_shape("packed_dwgemm", x, K)
+    if tuple(taps.shape) != (kh * kw, K):
+        raise ValueError(f"packed_dwgemm: taps must be [{kh * kw}, {K}], got {tuple(taps.shape)}")
+    nb, H, W, Ho, Wo, xc = _dw_geometry("packed_dwgemm", x, ks, st, pd)
+    tc = taps.contiguous()
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_dwgemm", bias, M)
+    xdt = HALF_DTYPES[x.dtype]
+    y = torch.empty((nb, M, Ho, Wo), dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    ws = _lib.workspace(lib.admmq_packed_hdwgemm_workspace_size(ctypes.byref(meta), M, K, Ho, Wo, nb), x.device)
+    rc = lib.admmq_packed_hdwgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(xc), xdt, nb, H, W, _lib.ptr(tc), kh, kw,
+                                  sh, sw, ph, pw, _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws),
+                                  ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_hdwgemm")
+    return y
+
+
+_opaque_packed_hdwgemm = torch.compiler.disable(_packed_hdwgemm)
+
+
 def packed_depthwise_conv1x1(x: torch.Tensor, taps: torch.Tensor, p: "PackedTensor",
                              bias: Optional[torch.Tensor] = None, kernel_size=(3, 3), stride=1,
-                             padding=0, act=None, mid_act=None) -> torch.Tensor:
+                             padding=0, act=None, mid_act=None, out_dtype=None) -> torch.Tensor:
     """The last two stages of a 3-way CP layer in one call: ``F.conv2d(z, W[:, :, None, None], bias)`` with
     ``W = p.dequantize()`` (``[M, K]``) and ``z`` the depthwise ``kernel_size`` convolution of ``x [n, K, H, W]``
     (``stride``, zero ``padding``) whose kernel of channel ``k`` is ``taps[:, k]`` (``taps [kh kw, K]``: the
     de-quantized ``C`` factor as it is). ``z`` is formed inside the GEMM's staging and never written; the
-    result has the bits of ``packed_conv1x1`` on a ``z`` summed tap by tap in float32. Inference only."""
+    result has the bits of ``packed_conv1x1`` on a ``z`` summed tap by tap in float32. A bfloat16 / float16 ``x``:
+    on that ``z`` rounded once to ``x``'s dtype (``out_dtype`` as for ``packed_conv1x1``). Inference only."""
     M, K = _weight_dims(p, False)
-    return packed_dwgemm(p.codes, _meta_words(p), M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act)
+    return packed_dwgemm(p.codes, _meta_words(p), M, K, x, taps, kernel_size, stride, padding, bias, act, mid_act,
+                         out_dtype)
 
 
 def save_packed(path: str, p) -> None:

@@ -27,73 +27,10 @@
 // one 16-byte load per thread and step when every row of X starts on a 16-byte boundary), Y is
 // written with 2- or 4-byte stores.
 #include <algorithm>
-#include <type_traits>
 
-#include "../../include/admmq.h"
-#include "packed_tile.h"
+#include "packed_half.h"
 
 namespace admmq {
-
-constexpr int kHgBK = 32;                // the K step
-constexpr int kHgLD = 40;                // LDS row stride in 16-bit elements: 16-byte aligned rows, 20 dwords apart
-constexpr int64_t kHgKMax = int64_t(1) << 24;
-
-typedef float hg_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 hg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hg_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned hg_u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const unsigned short gcu16;
-typedef __attribute__((address_space(1))) const hg_u32x4 gcu32x4;
-
-struct HgArgs {
-  const unsigned char* codes;
-  const unsigned short* x;   // bf16 / fp16 bits
-  const float* bias;
-  void* y;
-  float* part;        // parallel form: [np][total] float32 partial images in Y's layout
-  float* xpart;       // parallel form, tensor_minmax: [np][C] partial column sums of x
-  long long nbytes;   // bytes of the code stream
-  long long total;    // C * M
-  long long C;
-  int M, K, N;
-  int xl;
-  int kp, np, parallel;
-  int scheme;
-  int off;            // the operand is u - off (q + zp; 0 for tensor_minmax)
-  int xal;            // x_layout 1: every row of x starts on a 16-byte boundary
-  int ydt;            // ADMMQ_DT_* of y
-  float scale, mn, rng, nlev;   // nlev = float(2^bits - 1)
-};
-
-// The float32 result of one output: the sums' epilogue, operations rounded one by one
-__device__ __forceinline__ float hg_value(float S, float Sx, const HgArgs& a, bool has_bias, float bv) {
-  float v;
-  if (a.scheme == kMinMax) v = (S * a.rng) / a.nlev + a.mn * Sx;
-  else v = S * a.scale;
-  return has_bias ? v + bv : v;
-}
-
-// y[e] = v as float32, or rounded to nearest even to bf16 / fp16
-__device__ __forceinline__ void hg_store(void* y, long long e, float v, int ydt) {
-  if (ydt == ADMMQ_DT_F32) static_cast<float*>(y)[e] = v;
-  else if (ydt == ADMMQ_DT_BF16) static_cast<__bf16*>(y)[e] = static_cast<__bf16>(v);
-  else static_cast<_Float16*>(y)[e] = static_cast<_Float16>(v);
-}
-
-// The 16 bits of the integer v (|v| <= 256 for bf16, <= 2048 for fp16: exact)
-template <typename T>
-__device__ __forceinline__ unsigned hg_int_bits(int v) {
-  if constexpr (std::is_same_v<T, __bf16>) return __builtin_bit_cast(unsigned, (float)v) >> 16;
-  else return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)(float)v);
-}
-
-template <typename T>
-__device__ __forceinline__ hg_f32x16 hg_mfma(const hg_u32x4 a, const hg_u32x4 b, const hg_f32x16 c) {
-  if constexpr (std::is_same_v<T, __bf16>)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(hg_bf16x8, a), __builtin_bit_cast(hg_bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hg_f16x8, a), __builtin_bit_cast(hg_f16x8, b), c, 0, 0, 0);
-}
 
 template <int BITS, bool TRANS, bool XL, typename T>
 __global__ __launch_bounds__(256) void k_packed_hgemm(const HgArgs a) {
@@ -341,7 +278,7 @@ __global__ __launch_bounds__(256) void k_packed_hreduce(const HgArgs a) {
 
 // The float path's plan (K step 32, K <= 2^24, M K < 2^40, float32 partial images); tensor_minmax adds
 // the partial column sums of x in the parallel regime: np C floats behind the images
-static bool plan_hg(const ::admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int64_t nb, PackedPlan& pl) {
+bool plan_hg(const ::admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int64_t nb, PackedPlan& pl) {
   if (!meta) return false;
   if (!plan_packed(M, K, N, nb, kHgBK, kHgKMax, sizeof(float), pl) || M * K >= (int64_t(1) << 40)) return false;
   if (pl.parallel && meta->scheme == kMinMax) pl.ws += (size_t)pl.np * (size_t)pl.C * sizeof(float);
@@ -350,38 +287,45 @@ static bool plan_hg(const ::admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, 
 
 static size_t dt_bytes(int32_t dt) { return dt == ADMMQ_DT_F32 ? 4 : 2; }
 
-static int32_t packed_hgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
-                                const void* x, int32_t x_dtype, int32_t x_layout, int64_t N, int32_t nb,
-                                const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
-                                void* stream) {
-  const char* const who = "packed_hgemm";
-  if (!codes || !x || !y || !meta) return packed_fail(who, ADMMQ_ERR_ARG, "codes, meta, x and y must not be NULL");
-  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return packed_fail(who, ADMMQ_ERR_ARG, "M, K, N and nb must be positive");
-  int32_t rc = packed_meta_check(meta, who, false, nullptr);
-  if (rc != ADMMQ_OK) return rc;
-  if (trans_w != 0 && trans_w != 1) return packed_fail(who, ADMMQ_ERR_ARG, "trans_w must be 0 or 1");
-  if (x_layout != 0 && x_layout != 1) return packed_fail(who, ADMMQ_ERR_ARG, "x_layout must be 0 or 1");
-  if (x_layout == 1 && nb != 1) return packed_fail(who, ADMMQ_ERR_ARG, "x_layout 1 (linear) needs nb = 1");
-  if (x_dtype != ADMMQ_DT_F16 && x_dtype != ADMMQ_DT_BF16)
-    return packed_fail(who, ADMMQ_ERR_ARG, "x_dtype must be ADMMQ_DT_F16 or ADMMQ_DT_BF16");
-  if (y_dtype != ADMMQ_DT_F32 && y_dtype != x_dtype)
-    return packed_fail(who, ADMMQ_ERR_ARG, "y_dtype must be ADMMQ_DT_F32 or x_dtype");
+int hg_dtype_check(const char* who, const char* xn, const ::admmq_qmeta* meta, int32_t x_dtype, int32_t y_dtype) {
+  char what[128];
+  if (x_dtype != ADMMQ_DT_F16 && x_dtype != ADMMQ_DT_BF16) {
+    snprintf(what, sizeof what, "%s_dtype must be ADMMQ_DT_F16 or ADMMQ_DT_BF16", xn);
+    return packed_fail(who, ADMMQ_ERR_ARG, what);
+  }
+  if (y_dtype != ADMMQ_DT_F32 && y_dtype != x_dtype) {
+    snprintf(what, sizeof what, "y_dtype must be ADMMQ_DT_F32 or %s_dtype", xn);
+    return packed_fail(who, ADMMQ_ERR_ARG, what);
+  }
   // the integer operand must be exact in x's type: 8 significant bits in bf16, 11 in fp16
   const int64_t q = int64_t(1) << (meta->bits - 1);
   const int64_t zp = meta->scheme == kAffine ? (int64_t)meta->zero_point : 0;
   const int64_t lim = x_dtype == ADMMQ_DT_BF16 ? 256 : 2048;
-  if (meta->scheme != kMinMax && (-q - zp < -lim || q - 1 - zp > lim))
-    return packed_fail(who, ADMMQ_ERR_ARG, "affine zero_point puts (u - q) - zero_point outside the integers exact in x_dtype");
+  if (meta->scheme != kMinMax && (-q - zp < -lim || q - 1 - zp > lim)) {
+    snprintf(what, sizeof what, "affine zero_point puts (u - q) - zero_point outside the integers exact in %s_dtype", xn);
+    return packed_fail(who, ADMMQ_ERR_ARG, what);
+  }
+  return ADMMQ_OK;
+}
+
+int hg_align_check(const char* who, const char* xn, const void* codes, const void* x, const void* y, int32_t y_dtype,
+                   const float* bias) {
   if ((reinterpret_cast<uintptr_t>(codes) & 15) != 0) return packed_fail(who, ADMMQ_ERR_ARG, "codes must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(x) & 1) != 0) return packed_fail(who, ADMMQ_ERR_ARG, "x must be aligned to its 2-byte element");
+  if ((reinterpret_cast<uintptr_t>(x) & 1) != 0) {
+    char what[64];
+    snprintf(what, sizeof what, "%s must be aligned to its 2-byte element", xn);
+    return packed_fail(who, ADMMQ_ERR_ARG, what);
+  }
   if ((reinterpret_cast<uintptr_t>(y) & (dt_bytes(y_dtype) - 1)) != 0)
     return packed_fail(who, ADMMQ_ERR_ARG, "y must be aligned to its element");
   if ((reinterpret_cast<uintptr_t>(bias) & 3) != 0) return packed_fail(who, ADMMQ_ERR_ARG, "bias must be float aligned");
-  PackedPlan pl;
-  if (!plan_hg(meta, M, K, N, nb, pl)) return packed_fail(who, ADMMQ_ERR_ARG, "sizes out of range");
-  rc = packed_ws_check(who, pl, workspace, workspace_bytes, "float");
-  if (rc != ADMMQ_OK) return rc;
-  HgArgs a;
+  return ADMMQ_OK;
+}
+
+void hg_fill(HgArgs& a, const uint8_t* codes, const ::admmq_qmeta* meta, const void* x, const float* bias, void* y,
+             int32_t y_dtype, void* workspace, const PackedPlan& pl, int64_t M, int64_t K, int64_t N, int32_t x_layout) {
+  const int64_t q = int64_t(1) << (meta->bits - 1);
+  const int64_t zp = meta->scheme == kAffine ? (int64_t)meta->zero_point : 0;
   a.codes = codes; a.x = static_cast<const unsigned short*>(x); a.bias = bias; a.y = y;
   a.part = pl.parallel ? static_cast<float*>(workspace) : nullptr;
   a.xpart = pl.parallel ? a.part + (size_t)pl.np * (size_t)pl.total : nullptr;
@@ -396,6 +340,39 @@ static int32_t packed_hgemm_run(const uint8_t* codes, const admmq_qmeta* meta, i
   a.ydt = y_dtype;
   a.scale = meta->scale; a.mn = meta->mn; a.rng = meta->rng;
   a.nlev = (float)((1 << meta->bits) - 1);
+}
+
+int32_t hg_finish(const HgArgs& a, const PackedPlan& pl, void* stream) {
+  if (pl.parallel)
+    hipLaunchKernelGGL(k_packed_hreduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
+  return ADMMQ_OK;
+}
+
+static int32_t packed_hgemm_run(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                                const void* x, int32_t x_dtype, int32_t x_layout, int64_t N, int32_t nb,
+                                const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  const char* const who = "packed_hgemm";
+  if (!codes || !x || !y || !meta) return packed_fail(who, ADMMQ_ERR_ARG, "codes, meta, x and y must not be NULL");
+  if (M <= 0 || K <= 0 || N <= 0 || nb <= 0) return packed_fail(who, ADMMQ_ERR_ARG, "M, K, N and nb must be positive");
+  int32_t rc = packed_meta_check(meta, who, false, nullptr);
+  if (rc != ADMMQ_OK) return rc;
+  if (trans_w != 0 && trans_w != 1) return packed_fail(who, ADMMQ_ERR_ARG, "trans_w must be 0 or 1");
+  if (x_layout != 0 && x_layout != 1) return packed_fail(who, ADMMQ_ERR_ARG, "x_layout must be 0 or 1");
+  if (x_layout == 1 && nb != 1) return packed_fail(who, ADMMQ_ERR_ARG, "x_layout 1 (linear) needs nb = 1");
+  rc = hg_dtype_check(who, "x", meta, x_dtype, y_dtype);
+  if (rc != ADMMQ_OK) return rc;
+  rc = hg_align_check(who, "x", codes, x, y, y_dtype, bias);
+  if (rc != ADMMQ_OK) return rc;
+  PackedPlan pl;
+  if (!plan_hg(meta, M, K, N, nb, pl)) return packed_fail(who, ADMMQ_ERR_ARG, "sizes out of range");
+  rc = packed_ws_check(who, pl, workspace, workspace_bytes, "float");
+  if (rc != ADMMQ_OK) return rc;
+  HgArgs a;
+  hg_fill(a, codes, meta, x, bias, y, y_dtype, workspace, pl, M, K, N, x_layout);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)pl.tiles_c, (unsigned)pl.tiles_m, pl.parallel ? (unsigned)pl.np : 1u);
   const bool bf = x_dtype == ADMMQ_DT_BF16;
@@ -412,11 +389,7 @@ static int32_t packed_hgemm_run(const uint8_t* codes, const admmq_qmeta* meta, i
   PACKED_BITS_SWITCH(meta->bits, ADMMQ_HG_BITS)
 #undef ADMMQ_HG_BITS
 #undef ADMMQ_HG_LAUNCH
-  if (pl.parallel)
-    hipLaunchKernelGGL(k_packed_hreduce, dim3((unsigned)((pl.total + 255) / 256)), dim3(256), 0, s, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(ADMMQ_ERR_HIP, hipGetErrorString(err));
-  return ADMMQ_OK;
+  return hg_finish(a, pl, stream);
 }
 
 }  // namespace admmq

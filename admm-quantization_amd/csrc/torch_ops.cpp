@@ -14,6 +14,7 @@
 //   admmq::packed_lrgemv           the skinny quant + low-rank GEMV for 1..8 rows of x
 //   admmq::packed_lrgemm           packed codes + low-rank factors times float32 activations, one GEMM
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
+//   admmq::packed_hdwgemm          that stage on bfloat16 / float16 activations
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
 //   admmq::packed_taps_i8, packed_idwgemm   int8 tap image and the integer fused depthwise + 1x1 stage
@@ -983,6 +984,55 @@ at::Tensor packed_dwgemm_meta(const at::Tensor& codes, const at::Tensor& meta_wo
   return at::empty(packed_dwgemm_shape(x, taps, M, K, kh, kw, sh, sw, ph, pw), x.options().dtype(at::kFloat));
 }
 
+// packed_dwgemm on bfloat16 / float16 activations (admmq_packed_hdwgemm): taps and
+// bias float32; the result has x's dtype, or float32 with out_f32. Inference only.
+void check_half_x(const at::Tensor& x, const char* who) {
+  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16, "admmq: ", who,
+              ": x must be float16 or bfloat16, got ", x.scalar_type());
+}
+
+at::Tensor packed_hdwgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                               const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                               int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias, bool out_f32) {
+  TORCH_CHECK(x.is_cuda(), "admmq: x must live on a ROCm GPU (the MI355X path has no CPU implementation)");
+  check_half_x(x, "packed_hdwgemm");
+  check_inference_only(x.requires_grad(), "packed_dwgemm", "x");
+  check_f32_device(taps, "taps");
+  check_same_device(taps, x, "taps");
+  check_codes(codes, "packed_hdwgemm");
+  check_same_device(codes, x, "codes");
+  check_meta_words(meta_words, "packed_hdwgemm");
+  const std::vector<int64_t> oshape = packed_dw_shape("packed_hdwgemm", "taps", K, x, taps, M, K, kh, kw, sh, sw, ph, pw);
+  TORCH_CHECK(std::max(sh, sw) <= INT32_MAX && x.size(0) <= INT32_MAX, "admmq: packed_hdwgemm: sizes out of range");
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_hdwgemm", meta);
+  TORCH_CHECK(x.numel() > 0, "admmq: packed_hdwgemm: empty x");
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor tc = taps.detach().contiguous();
+  const at::Tensor bc = bias_of(bias, x, M, "packed_hdwgemm", false);
+  const int32_t nb = static_cast<int32_t>(xc.size(0));
+  const int32_t xdt = x.scalar_type() == at::kHalf ? ADMMQ_DT_F16 : ADMMQ_DT_BF16;
+  at::Tensor y = at::empty(oshape, out_f32 ? xc.options().dtype(at::kFloat) : xc.options());
+  at::Tensor ws = workspace(admmq_packed_hdwgemm_workspace_size(&meta, M, K, oshape[2], oshape[3], nb), xc);
+  check_rc(admmq_packed_hdwgemm(cc.data_ptr<uint8_t>(), &meta, M, K, xc.data_ptr(), xdt, nb, xc.size(2), xc.size(3),
+                                tc.data_ptr<float>(), static_cast<int32_t>(kh), static_cast<int32_t>(kw),
+                                static_cast<int32_t>(sh), static_cast<int32_t>(sw), static_cast<int32_t>(ph),
+                                static_cast<int32_t>(pw), f32_or_null(bc), y.data_ptr(), out_f32 ? ADMMQ_DT_F32 : xdt,
+                                ws.data_ptr(), ws.numel(), stream_of(xc)),
+           "packed_hdwgemm");
+  return y;
+}
+
+at::Tensor packed_hdwgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                               const at::Tensor& x, const at::Tensor& taps, int64_t kh, int64_t kw, int64_t sh,
+                               int64_t sw, int64_t ph, int64_t pw, const std::optional<at::Tensor>& bias, bool out_f32) {
+  check_half_x(x, "packed_hdwgemm");
+  TORCH_CHECK(taps.scalar_type() == at::kFloat, "admmq: packed_hdwgemm: taps must be float32, got ", taps.scalar_type());
+  return at::empty(packed_dw_shape("packed_hdwgemm", "taps", K, x, taps, M, K, kh, kw, sh, sw, ph, pw),
+                   out_f32 ? x.options().dtype(at::kFloat) : x.options());
+}
+
 // --- quantize_channel (channel_symmetric / channel_affine with an explicit dim) ----------------
 at::Tensor quantize_channel_cuda(const at::Tensor& x, int64_t bits, int64_t qscheme, int64_t dim) {
   check_f32_device(x, "tensor");
@@ -1136,6 +1186,8 @@ TORCH_LIBRARY(admmq, m) {
         "bool out_f32=False) -> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
         "int sw, int ph, int pw, Tensor? bias=None) -> Tensor");
+  m.def("packed_hdwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
+        "int sw, int ph, int pw, Tensor? bias=None, bool out_f32=False) -> Tensor");
   m.def("packed_gemm_act(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_layout, "
         "Tensor? bias, int out_bits, float out_mn, float out_rng) -> Tensor");
   m.def("packed_dwgemm_act(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
@@ -1170,6 +1222,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("packed_lrgemm", &packed_lrgemm_cuda);
   m.impl("packed_lrgemv", &packed_lrgemv_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
+  m.impl("packed_hdwgemm", &packed_hdwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_cuda);
   m.impl("fixed_quantize", &fixed_quantize_cuda);
@@ -1195,6 +1248,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("packed_lrgemm", &packed_lrgemm_meta);
   m.impl("packed_lrgemv", &packed_lrgemv_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
+  m.impl("packed_hdwgemm", &packed_hdwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_meta);
   m.impl("fixed_quantize", &fixed_quantize_meta);

@@ -471,6 +471,39 @@ int32_t admmq_packed_hgemm(const uint8_t* codes, const admmq_qmeta* meta, int32_
                            const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* Half-precision fused depthwise + 1x1: admmq_packed_dwgemm's stage on bfloat16
+ * or float16 activations, on the 16-bit MFMA.
+ *   t     [nb, K, H, W] in t_dtype (ADMMQ_DT_F16 or ADMMQ_DT_BF16), contiguous
+ *   taps  [kh*kw, K]    float32, row-major
+ *   codes, meta         the packed weight D [M, K] (not transposed), as for admmq_packed_gemm
+ *   bias  [M]           float32, may be NULL
+ *   y     [nb, M, Ho, Wo] in y_dtype (ADMMQ_DT_F32 or t_dtype); Ho, Wo as for admmq_packed_dwgemm
+ * 1. z32: admmq_packed_dwgemm's step 1 on t widened exactly to float32: from +0.0f, the taps in
+ *    increasing order, product and sum rounded separately; a tap outside the image contributes
+ *    nothing.
+ * 2. zh = z32 rounded once, to nearest even, to t_dtype (float16 subnormals are kept).
+ * 3. Y = exactly admmq_packed_hgemm's arithmetic on zh for (M, K, N = Ho*Wo, nb), trans_w = 0,
+ *    x_layout = 0: the same K pieces, fold order, regimes, S_x accumulator for tensor_minmax and
+ *    float32 epilogue. The result has the bits of admmq_packed_hgemm on a Z formed by steps 1-2,
+ *    for every nb and on every call. zh never exists in memory.
+ * Limits: admmq_packed_dwgemm's geometry limits (1 <= kh, kw <= 7; sh, sw >= 1; 0 <= ph < kh,
+ * 0 <= pw < kw; Ho, Wo >= 1; nb*K*H*W < 2^40) and admmq_packed_hgemm's limits. codes: device,
+ * 16-byte aligned; t and y: aligned to their element; taps, bias: float aligned. ADMMQ_ERR_ARG
+ * for NULL codes / meta / t / taps / y, non-positive sizes, a bad meta record, a kernel size,
+ * stride or padding outside the limits, a window that does not fit the padded image, a dtype
+ * pair other than the above, an affine record that is not exact in t_dtype (as for
+ * admmq_packed_hgemm), misaligned pointers, sizes past the limits; ADMMQ_ERR_WORKSPACE for a
+ * short workspace - all before any launch, each with its own admmq_last_error text.
+ * admmq_packed_hdwgemm_workspace_size(meta, M, K, Ho, Wo, nb) equals
+ * admmq_packed_hgemm_workspace_size(meta, M, K, Ho*Wo, nb) (0 for arguments out of range): there
+ * is no buffer for Z. */
+size_t admmq_packed_hdwgemm_workspace_size(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t Ho, int64_t Wo,
+                                           int32_t nb);
+int32_t admmq_packed_hdwgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const void* t,
+                             int32_t t_dtype, int32_t nb, int64_t H, int64_t W, const float* taps, int32_t kh, int32_t kw,
+                             int32_t sh, int32_t sw, int32_t ph, int32_t pw, const float* bias, void* y, int32_t y_dtype,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Skinny packed GEMV: decode-shape linear layers straight from the codes,
  *   y[c, m] = sum_k W[m, k] x[c, k] (+ bias[m]),   c = 0 .. N-1,   1 <= N <= ADMMQ_GEMV_N_MAX
  * with x [N, K] and y [N, M] row-major (the linear layout only), W = D (trans_w 0, the packed

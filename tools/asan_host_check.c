@@ -272,6 +272,42 @@ int main(void) {
       fails += HG(c, &qm, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
       fails += HG(c, &qx, 0, 512, 1141, hx, BF, 0, 4, 1, NULL, hy, BF, ws, 18 * 512 * 4 * 4) != ADMMQ_ERR_WORKSPACE;
 #undef HG
+      /* the half fused depthwise + 1x1 stage: the half GEMM's workspace for N = Ho Wo, and its refusals */
+      for (int t = 0; t < 200; ++t) {
+        const int64_t M = rnd(1, 3000), K = rnd(1, 3000), Ho = rnd(1, 60), Wo = rnd(1, 60);
+        const int32_t nb = rnd(1, 4);
+        fails += admmq_packed_hdwgemm_workspace_size(&qm, M, K, Ho, Wo, nb) != admmq_packed_hgemm_workspace_size(&qm, M, K, Ho * Wo, nb);
+        fails += admmq_packed_hdwgemm_workspace_size(&qx, M, K, Ho, Wo, nb) != admmq_packed_hgemm_workspace_size(&qx, M, K, Ho * Wo, nb);
+      }
+      fails += admmq_packed_hdwgemm_workspace_size(NULL, 8, 65, 2, 2, 1) != 0;
+      fails += admmq_packed_hdwgemm_workspace_size(&qm, 8, 65, 0, 2, 1) != 0;
+      fails += admmq_packed_hdwgemm_workspace_size(&qm, 8, 65, 2, ((int64_t)1 << 30) + 1, 1) != 0;
+#define HD(cc, mm, M, K, tt, td, nb, H, W, pp, kh, sh, ph, bb, yy, yd, wsp, wsb) \
+  admmq_packed_hdwgemm(cc, mm, M, K, tt, td, nb, H, W, pp, kh, 3, sh, 1, ph, 1, bb, yy, yd, wsp, wsb, NULL)
+      const float* hp = (const float*)0x30000;
+      fails += HD(NULL, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, NULL, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, NULL, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, NULL, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, NULL, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 0, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 8, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 0, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 3, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 1, 6, hp, 3, 1, 0, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, F32, 1, 6, 6, hp, 3, 1, 1, NULL, hy, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, HF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 200;
+      fails += HD(c, &q2, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c + 4, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, (const void*)0x10001, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, (const float*)0x30002, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, (void*)0x20002, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, (int64_t)1 << 30, 8, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 8, (int64_t)1 << 22, hx, BF, 4, 1 << 10, 1 << 10, hp, 3, 1, 1, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HD(c, &qm, 512, 1141, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 16) != ADMMQ_ERR_WORKSPACE;
+      fails += HD(c, &qx, 512, 1141, hx, BF, 1, 6, 6, hp, 3, 1, 1, NULL, hy, BF, ws, 18 * 512 * 36 * 4) != ADMMQ_ERR_WORKSPACE;
+#undef HD
       /* the skinny GEMV: the size query over random and named shapes (pure: asked twice), and every refusal
        * before any launch */
       for (int t = 0; t < 400; ++t) {
