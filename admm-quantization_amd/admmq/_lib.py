@@ -149,6 +149,9 @@ def load() -> ctypes.CDLL:
         "admmq_packed_lrgemv_workspace_size": (S, [P, I64, I64, I64, I32]),
         "admmq_packed_lrgemv_plan": (I32, [P, I64, I64, I32, P]),
         "admmq_packed_lrgemv": (I32, [P, P, I64, I64, P, P, I32, I32, P, I32, I64, P, P, I32, P, S, P]),
+        "admmq_packed_hlrgemm_workspace_size": (S, [P, I64, I64, I64, I32]),
+        "admmq_packed_hlrgemm_plan": (I32, [P, I64, I64, I64, I32, P]),
+        "admmq_packed_hlrgemm": (I32, [P, P, I64, I64, P, P, I32, I32, P, I32, I64, P, P, I32, P, S, P]),
         "admmq_packed_lrgemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_lrgemm": (I32, [P, P, I64, I64, P, P, I32, P, I64, P, P, P, S, P]),
         "admmq_packed_dwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),

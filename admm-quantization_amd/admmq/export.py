@@ -39,7 +39,7 @@ from torch import nn
 from . import _lib
 from .packed import (HALF_DTYPES, PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
                      _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
-                     packed_gemm, packed_gemv, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
+                     packed_gemm, packed_gemv, packed_hlrgemm, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -166,12 +166,15 @@ class PackedLowRankLinear(_PackedWeight):
     """``nn.Linear`` on the quant + low-rank form ``W = W_q + L Rt`` of ``admmq.lowrank``: ``x [..., in] -> [..., out]``
     by ``k_lr_down`` + ``k_packed_lrgemm``. ``W_q`` stays packed in ``codes``; ``L [out, r]`` and
     ``Rt [r, in]`` are float32 buffers. Neither ``W_q`` nor ``L Rt`` is ever formed. No activation quantizer yet.
-    A bfloat16 / float16 input is a composition, not the fused kernel: the half packed GEMM with a float32
+    A bfloat16 / float16 input is by default a composition, not a fused kernel: the half packed GEMM with a float32
     result plus ``(x.float() @ Rt.float().T) @ L.float().T`` and the bias, converted once to the input's dtype.
     ``skinny`` (an attribute, default ``False``, not part of the state dict): send an input of at most
-    ``GEMV_N_MAX`` rows to the decode kernels ``packed_lrgemv`` (DESIGN.md 2.33; fused for the half types too);
-    every other input takes the default route."""
+    ``GEMV_N_MAX`` rows to the decode kernels ``packed_lrgemv`` (fused for the half types too).
+    ``fused`` (likewise an attribute, default ``False``): send every other bfloat16 / float16 input to the opt-in
+    fused route ``packed_hlrgemm`` (16-bit MFMA throughout, another sum order and ``t`` rounded
+    once to the input's dtype, so other bits than the default route's). Every other input takes the default route."""
     skinny = False
+    fused = False
 
     def __init__(self, p: PackedLowRank, bias: Optional[torch.Tensor] = None, act=None):
         if act is not None:
@@ -214,11 +217,14 @@ class PackedLowRankLinear(_PackedWeight):
     def forward(self, x):
         if self.skinny and skinny_rows(x, self.in_features):
             return packed_lrgemv(self.codes, self._meta, self.out_features, self.in_features, self.L, self.Rt, x, self.bias)
+        if self.fused and x.dtype in HALF_DTYPES:
+            return packed_hlrgemm(self.codes, self._meta, self.out_features, self.in_features, self.L, self.Rt, x, self.bias)
         return packed_lrgemm(self.codes, self._meta, self.out_features, self.in_features, self.L, self.Rt, x, self.bias)
 
     def extra_repr(self):
         return (f"{self.in_features}, {self.out_features}, rank={self.rank}, bits={self._q['bits']}, "
-                f"qscheme={self._q['qscheme']}, bias={self.bias is not None}" + (", skinny=True" if self.skinny else ""))
+                f"qscheme={self._q['qscheme']}, bias={self.bias is not None}" + (", skinny=True" if self.skinny else "")
+                + (", fused=True" if self.fused else ""))
 
 
 def build_qlr_layer(p: PackedLowRank, bias: Optional[torch.Tensor] = None) -> PackedLowRankLinear:

@@ -28,6 +28,8 @@ codes, ``W_r`` as its thin factors ``L [M, r]``, ``Rt [r, K]``; ``packed_lowrank
 ``x (W_q + L Rt)^T (+ bias)`` from the three in one GEMM (``k_lr_down`` + ``k_packed_lrgemm``).
 ``packed_lrgemv`` is its decode-shape product (``k_lr_down_gemv`` + ``k_packed_lrgemv``, float32 / bfloat16 /
 float16 activations); ``packed_lowrank_linear(..., skinny=True)`` routes to it.
+``packed_hlrgemm`` is its fused bfloat16 / float16 product at any row count (``k_hlr_down`` + ``k_packed_hlrgemm``
+on the 16-bit MFMA); ``packed_lowrank_linear(..., fused=True)`` routes to it.
 
 Schemes: ``tensor_mseminmax_symmetric``, ``tensor_minmax`` (``bits >= 2``),
 ``tensor_symmetric``, ``tensor_affine`` (with its ``tmin`` / ``tmax``); ``bits`` 1..8.
@@ -46,7 +48,7 @@ __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed"
            "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
-           "packed_lrgemm", "packed_lrgemv", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
+           "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -1086,7 +1088,8 @@ def packed_lrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
                   x: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
     """``y = x (D + L Rt)^T (+ bias)`` with ``D`` the ``[M, K]`` de-quantization of ``codes``, ``L [M, r]`` and
     ``Rt [r, K]`` float32 (``admmq_packed_lrgemm``): ``x [..., K] -> [..., M]``. Neither ``D`` nor ``L Rt`` is
-    written to memory. A bfloat16 / float16 ``x`` is a composition, not a fused kernel:
+    written to memory. A bfloat16 / float16 ``x`` is a composition here (the fused kernels for
+    such an ``x`` are the opt-in ``packed_hlrgemm``):
     ``(packed_gemm(x, out float32) + (x.float() @ Rt.float().T) @ L.float().T + bias)`` converted once to ``x``'s
     dtype (or kept float32 with ``out_dtype=torch.float32``); ``L`` / ``Rt`` / ``bias`` may then be of ``x``'s dtype
     (a module after ``.half()``). Inference only: an ``x`` that requires grad is refused while grad mode is on."""
@@ -1185,16 +1188,76 @@ def packed_lrgemv(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int,
 _opaque_packed_lrgemv = torch.compiler.disable(packed_lrgemv)
 
 
+def packed_hlrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
+                   x: torch.Tensor, bias: Optional[torch.Tensor] = None, out_dtype=None) -> torch.Tensor:
+    """The fused half-precision quant + low-rank product (``admmq_packed_hlrgemm``):
+    ``y = x (D + L Rt)^T (+ bias)`` for a bfloat16 / float16 ``x [..., K]`` of any row count, on the 16-bit MFMA
+    throughout - two launches (three where the K pieces run in parallel), no float32 copy of ``x``. ``L [M, r]`` and
+    ``Rt [r, K]`` are both float32 (rounded once to ``x``'s dtype as they are staged) or both of ``x``'s dtype (a
+    module after ``.half()``: the same bits when the factors are representable); ``t = x Rt^T`` is summed in
+    float32 and rounded once to ``x``'s dtype. The result has ``x``'s dtype, or float32 with
+    ``out_dtype=torch.float32``; ``bias`` may be float32 or of ``x``'s dtype. A row's bits depend on that row only;
+    with ``L = 0`` they are ``packed_linear``'s. Not ``packed_lrgemm``'s bits (another sum order, ``t`` rounded).
+    Inference only."""
+    _require_gpu("packed_hlrgemm", "codes, factors and activations", x, codes, L, Rt)
+    if x.dtype not in HALF_DTYPES:
+        raise TypeError(f"admmq: packed_hlrgemm: x must be bfloat16 or float16, got {x.dtype} (a float32 x runs "
+                        f"packed_lrgemm, the fused float32 kernels)")
+    if out_dtype is not None and out_dtype != torch.float32 and out_dtype != x.dtype:
+        raise ValueError(f"packed_hlrgemm: out_dtype must be None, torch.float32 or x's dtype {x.dtype}, got {out_dtype}")
+    _inference_only("packed_hlrgemm", x, "x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_hlrgemm(codes, meta_words, M, K, L, Rt, x, bias, out_dtype)
+    M, K = int(M), int(K)
+    L, Rt = L.detach(), Rt.detach()
+    if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
+        raise ValueError(f"packed_hlrgemm: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
+    if L.dtype != Rt.dtype or (L.dtype != torch.float32 and L.dtype != x.dtype):
+        raise TypeError(f"admmq: packed_hlrgemm: L and Rt must both be float32 or both of x's dtype {x.dtype}, got "
+                        f"{L.dtype} and {Rt.dtype}")
+    r = int(L.shape[1])
+    if not 1 <= r <= RANK_MAX:
+        raise ValueError(f"packed_hlrgemm: rank must be 1..{RANK_MAX}, got {r}")
+    oshape, _, N, xc = _gemm_geometry("packed_hlrgemm", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    out_f32 = out_dtype == torch.float32
+    if bias is not None:
+        _require_gpu("packed_hlrgemm", "bias", bias)
+        if bias.dtype != torch.float32 and bias.dtype != x.dtype:
+            raise TypeError(f"admmq: packed_hlrgemm: bias must be float32 or x's dtype {x.dtype}, got {bias.dtype}")
+        bias = bias.detach().float()   # (exact)
+    if _lib.use_ops():   # torch.ops.admmq.packed_hlrgemm (csrc/torch_ops.cpp) -> admmq_packed_hlrgemm
+        return _lib.ops().packed_hlrgemm(codes, meta_words, M, K, L, Rt, xc, bias, out_f32)
+    lib = _lib.load()
+    Lc, Rc = L.contiguous(), Rt.contiguous()
+    (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_hlrgemm", bias, M)
+    xdt = GEMV_DTYPES[x.dtype]
+    y = torch.empty(oshape, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    ws = _lib.workspace(lib.admmq_packed_hlrgemm_workspace_size(ctypes.byref(meta), M, K, N, r), x.device)
+    rc = lib.admmq_packed_hlrgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), GEMV_DTYPES[L.dtype], r,
+                                  _lib.ptr(xc), xdt, N, _lib.ptr(bc), _lib.ptr(y), 0 if out_f32 else xdt, _lib.ptr(ws),
+                                  ws.numel(), _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_hlrgemm")
+    return y
+
+
+_opaque_packed_hlrgemm = torch.compiler.disable(packed_hlrgemm)
+
+
 def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[torch.Tensor] = None,
-                          out_dtype=None, skinny: bool = False) -> torch.Tensor:
+                          out_dtype=None, skinny: bool = False, fused: bool = False) -> torch.Tensor:
     """``F.linear(x, W_q + L Rt, bias)`` computed from ``p``'s codes and factors in one GEMM: ``x [..., K] ->
-    [..., M]``. A bfloat16 / float16 ``x`` runs ``packed_lrgemm``'s composition (the half packed GEMM plus two
-    library products in float32; not a fused kernel). ``skinny=True`` sends an ``x`` of at most ``GEMV_N_MAX`` rows
+    [..., M]``. A bfloat16 / float16 ``x`` runs by default ``packed_lrgemm``'s composition (the half packed GEMM
+    plus two library products in float32). ``skinny=True`` sends an ``x`` of at most ``GEMV_N_MAX`` rows
     to ``packed_lrgemv`` (the decode kernels, fused for the half types too: faster there, another sum order, so
-    other bits than the default route's) and any other ``x`` down the default route. Inference only."""
+    other bits than the default route's). ``fused=True`` sends any other bfloat16 / float16 ``x`` to
+    ``packed_hlrgemm`` (the fused 16-bit MFMA kernels, DESIGN.md 2.35: another sum order and ``t`` rounded once to
+    ``x``'s dtype, so other bits again); for a float32 ``x`` it changes nothing. Everything else goes down the
+    default route. Inference only."""
     M, K, _ = _lowrank_dims(p)
     if skinny and skinny_rows(x, K):
         return packed_lrgemv(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
+    if fused and x.dtype in HALF_DTYPES:
+        return packed_hlrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
     return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
 
 

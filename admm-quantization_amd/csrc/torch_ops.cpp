@@ -12,6 +12,7 @@
 //   admmq::packed_hgemm            a packed weight times bfloat16 / float16 activations
 //   admmq::packed_gemv             the skinny GEMV of a packed weight for 1..8 rows of x
 //   admmq::packed_lrgemv           the skinny quant + low-rank GEMV for 1..8 rows of x
+//   admmq::packed_hlrgemm          the fused half-precision quant + low-rank GEMM, any row count
 //   admmq::packed_lrgemm           packed codes + low-rank factors times float32 activations, one GEMM
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::packed_hdwgemm          that stage on bfloat16 / float16 activations
@@ -902,6 +903,61 @@ at::Tensor packed_lrgemv_meta(const at::Tensor& codes, const at::Tensor& meta_wo
   return at::empty(packed_lrgemv_shape(x, L, Rt, M, K), out_f32 ? x.options().dtype(at::kFloat) : x.options());
 }
 
+// --- packed_hlrgemm -------------------------------------------------------------------------
+// The half-precision fused quant + low-rank GEMM (admmq_packed_hlrgemm): x [..., K] in
+// bfloat16 or float16, any row count -> [..., M] of x's dtype, or float32 with out_f32. L [M, r] and
+// Rt [r, K]: float32, or both of x's dtype. bias: float32. Inference only.
+std::vector<int64_t> packed_hlrgemm_shape(const at::Tensor& x, const at::Tensor& L, const at::Tensor& Rt, int64_t M, int64_t K) {
+  TORCH_CHECK(x.scalar_type() == at::kHalf || x.scalar_type() == at::kBFloat16,
+              "admmq: packed_hlrgemm: x must be float16 or bfloat16 (a float32 x runs packed_lrgemm), got ", x.scalar_type());
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_hlrgemm: M and K must be positive");
+  TORCH_CHECK(L.dim() == 2 && Rt.dim() == 2 && L.size(0) == M && Rt.size(1) == K && L.size(1) == Rt.size(0),
+              "admmq: packed_hlrgemm: L must be [", M, ", r] and Rt [r, ", K, "], got ", L.sizes(), " and ", Rt.sizes());
+  TORCH_CHECK(L.size(1) >= 1 && L.size(1) <= 256, "admmq: packed_hlrgemm: rank r must be 1..256, got ", L.size(1));
+  TORCH_CHECK(L.scalar_type() == Rt.scalar_type() && (L.scalar_type() == at::kFloat || L.scalar_type() == x.scalar_type()),
+              "admmq: packed_hlrgemm: L and Rt must both be float32 or both of x's dtype ", x.scalar_type(), ", got ",
+              L.scalar_type(), " and ", Rt.scalar_type());
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K && x.numel() > 0, "admmq: packed_hlrgemm: x must be [..., ", K,
+              "] with at least one row, got ", x.sizes());
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  shape.back() = M;
+  return shape;
+}
+
+at::Tensor packed_hlrgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                               const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& x,
+                               const std::optional<at::Tensor>& bias, bool out_f32) {
+  TORCH_CHECK(x.is_cuda() && L.is_cuda() && Rt.is_cuda(),
+              "admmq: x, L and Rt must live on a ROCm GPU (the MI355X path has no CPU implementation)");
+  check_inference_only(x.requires_grad() || L.requires_grad() || Rt.requires_grad(), "packed_hlrgemm", "x");
+  check_codes(codes, "packed_hlrgemm");
+  check_same_device(codes, x, "codes");
+  check_same_device(L, x, "L");
+  check_same_device(Rt, x, "Rt");
+  check_meta_words(meta_words, "packed_hlrgemm");
+  const std::vector<int64_t> oshape = packed_hlrgemm_shape(x, L, Rt, M, K);
+  admmq_qmeta meta;
+  const at::Tensor cc = packed_weight_of(codes, meta_words, M, K, "packed_hlrgemm", meta);
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous(), Lc = L.contiguous(), Rc = Rt.contiguous();
+  const at::Tensor bc = bias_of(bias, x, M, "packed_hlrgemm", false);
+  const int64_t N = xc.numel() / K;
+  const int32_t r = static_cast<int32_t>(Lc.size(1)), xdt = dt_of(xc);
+  at::Tensor y = at::empty(oshape, out_f32 ? xc.options().dtype(at::kFloat) : xc.options());
+  at::Tensor ws = workspace(admmq_packed_hlrgemm_workspace_size(&meta, M, K, N, r), xc);
+  check_rc(admmq_packed_hlrgemm(cc.data_ptr<uint8_t>(), &meta, M, K, Lc.data_ptr(), Rc.data_ptr(), dt_of(Lc), r, xc.data_ptr(),
+                                xdt, N, f32_or_null(bc), y.data_ptr(), out_f32 ? ADMMQ_DT_F32 : xdt, ws.data_ptr(),
+                                static_cast<size_t>(ws.numel()), stream_of(xc)),
+           "packed_hlrgemm");
+  return y;
+}
+
+at::Tensor packed_hlrgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
+                               const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& x,
+                               const std::optional<at::Tensor>& bias, bool out_f32) {
+  return at::empty(packed_hlrgemm_shape(x, L, Rt, M, K), out_f32 ? x.options().dtype(at::kFloat) : x.options());
+}
+
 // --- packed_dwgemm --------------------------------------------------------------------------
 // The depthwise kh x kw stage (taps [kh kw, K]) and the 1x1 stage by the packed [M, K] weight
 // in one kernel (admmq_packed_dwgemm): x [nb, K, H, W] -> [nb, M, Ho, Wo]. Inference only.
@@ -1184,6 +1240,8 @@ TORCH_LIBRARY(admmq, m) {
         "-> Tensor");
   m.def("packed_lrgemv(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor x, Tensor? bias=None, "
         "bool out_f32=False) -> Tensor");
+  m.def("packed_hlrgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor x, Tensor? bias=None, "
+        "bool out_f32=False) -> Tensor");
   m.def("packed_dwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
         "int sw, int ph, int pw, Tensor? bias=None) -> Tensor");
   m.def("packed_hdwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
@@ -1221,6 +1279,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("packed_gemv", &packed_gemv_cuda);
   m.impl("packed_lrgemm", &packed_lrgemm_cuda);
   m.impl("packed_lrgemv", &packed_lrgemv_cuda);
+  m.impl("packed_hlrgemm", &packed_hlrgemm_cuda);
   m.impl("packed_dwgemm", &packed_dwgemm_cuda);
   m.impl("packed_hdwgemm", &packed_hdwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
@@ -1247,6 +1306,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("packed_gemv", &packed_gemv_meta);
   m.impl("packed_lrgemm", &packed_lrgemm_meta);
   m.impl("packed_lrgemv", &packed_lrgemv_meta);
+  m.impl("packed_hlrgemm", &packed_hlrgemm_meta);
   m.impl("packed_dwgemm", &packed_dwgemm_meta);
   m.impl("packed_hdwgemm", &packed_hdwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);

@@ -599,6 +599,54 @@ int32_t admmq_packed_lrgemv(const uint8_t* codes, const admmq_qmeta* meta, int64
                             const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Half-precision quant + low-rank GEMM: the layer W ~ D + L Rt at any row count
+ * N >= 1 of x [N, K] in bfloat16 or float16 (type T, u = 2^-8 / 2^-11), on
+ * v_mfma_f32_32x32x16_{bf16,f16}. D [M, K] from codes (bits 1..8, the four tensor schemes, no
+ * transpose, linear layout), L [M, r], Rt [r, K] row-major, 1 <= r <= 256. Neither D, L Rt nor
+ * a float32 copy of x is written.
+ *   Factors: L and Rt share one type f_dtype, ADMMQ_DT_F32 or x_dtype. A float32 factor is
+ *     rounded once, to nearest even, to T as it is staged (L_T, Rt_T); one representable in T
+ *     enters exactly, so a module before and after .half() / .bfloat16() gives the same bits.
+ *   t32[c, j] = sum_k Rt_T[j, k] x[c, k]: K is cut into nsd ranges (1 <= nsd <= 8, a pure
+ *     function of (K, r, N)), a range is one MFMA accumulator chain from zero in steps of 16 k,
+ *     the ranges are added in range order; t_T = t32 rounded once to nearest even to T (fp16
+ *     subnormals kept).
+ *   S (and S_x for tensor_minmax): exactly admmq_packed_hgemm's sums for (M, K, N, nb = 1),
+ *     trans_w = 0, x_layout = 1 - the same plan, pieces, fold order, regimes and integer operand;
+ *     v = their epilogue without the bias.
+ *   q[c, m] = sum_j L_T[m, j] t_T[c, j]: one MFMA chain from zero, j zero padded to the 32-wide step.
+ *   y32[c, m] = (v + q) + bias[m], each add rounded once; y is y32, or it rounded once to T.
+ * A column's bits depend on that column, K, r and the plans only - not on N within a regime,
+ * nor on the call. With L = 0 the result equals admmq_packed_hgemm's (but for the sign of a zero
+ * without a bias).
+ * Forward bound, one float32 ulp (eps = 2^-23) an operation, g = (1 + eps)^(K + r + 6) - 1,
+ * A = |D||x|, B = |L_T|(|Rt_T||x|):
+ *   |y - y64| <= g (A + B + |bias|) + u (1 + g) B
+ * with y64 the float64 value on the factors as rounded to T (first order:
+ * (K + r + 6) eps (A + B + |bias|) + u B).
+ * Launches: k_hlr_down (t's nsd float32 images, rows padded to rp = 32 ceil(r / 32) floats with
+ * exact zeros; no reduce launch, the consumer adds the images), k_packed_hlrgemm (the code sum,
+ * then the tail in the same LDS images) and, in admmq_packed_hgemm's parallel regime (one more
+ * workgroup a tile runs the tail alone), k_packed_hlrreduce. No atomics, no workgroup waits for
+ * another, nothing past the code stream's last byte is read.
+ * Pointers, limits and refusals are admmq_packed_hgemm's (the dtype pair, an affine record not
+ * exact in T, alignment to the element) and admmq_packed_lrgemm's (NULL pointers, sizes, r
+ * outside 1..256), and: an f_dtype other than ADMMQ_DT_F32 or x_dtype; L, Rt aligned to their
+ * element; the workspace 16-byte aligned, and ADMMQ_ERR_WORKSPACE where it is NULL or short (t
+ * always lives there) - all before any launch, each with its own admmq_last_error text.
+ * admmq_packed_hlrgemm_workspace_size is a function of its arguments only (of meta: the scheme):
+ * 0 for a NULL meta or arguments out of range, else, in this order, 4 (np + 1) N M bytes of y
+ * images and 4 np N of column sums (tensor_minmax) in the parallel regime, rounded up to 16
+ * bytes, then 4 nsd N rp bytes of t. admmq_packed_hlrgemm_plan writes
+ * out = (np, parallel, nsd, launches) - a pure function; ADMMQ_ERR_ARG (and nothing written) for
+ * arguments out of range. */
+size_t admmq_packed_hlrgemm_workspace_size(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int32_t r);
+int32_t admmq_packed_hlrgemm_plan(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int32_t r, int32_t out[4]);
+int32_t admmq_packed_hlrgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const void* L,
+                             const void* Rt, int32_t f_dtype, int32_t r, const void* x, int32_t x_dtype, int64_t N,
+                             const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

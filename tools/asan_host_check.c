@@ -398,6 +398,65 @@ int main(void) {
       fails += LV(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
       fails += LV(c, &qx, 8, 2048, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * (8 * 4 * 8 + 3 * 4 * 8 + 2 * 4) - 1) != ADMMQ_ERR_WORKSPACE;
 #undef LV
+      /* the half-precision fused quant + low-rank GEMM: the size and plan queries over random and named shapes
+       * (pure: asked twice; the size is the one the plan spells), and every refusal before any launch */
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, t % 3 ? 600 : 7000), K = rnd(1, t % 3 ? 600 : 40000), N = rnd(1, t % 3 ? 600 : 5000);
+        const int32_t r = rnd(1, 256);
+        const size_t rpad = 32 * (((size_t)r + 31) / 32);
+        int32_t pl[4] = {0, 0, 0, 0}, pl2[4] = {0, 0, 0, 0};
+        const size_t w = admmq_packed_hlrgemm_workspace_size(&qm, M, K, N, r), wx = admmq_packed_hlrgemm_workspace_size(&qx, M, K, N, r);
+        fails += admmq_packed_hlrgemm_plan(&qm, M, K, N, r, pl) != ADMMQ_OK || admmq_packed_hlrgemm_plan(&qx, M, K, N, r, pl2) != ADMMQ_OK;
+        fails += pl[0] != pl2[0] || pl[1] != pl2[1] || pl[2] != pl2[2] || pl[3] != (pl[1] ? 3 : 2);
+        fails += pl[0] < 1 || pl[0] > 32 || pl[2] < 1 || pl[2] > 8 || (pl[1] != 0) != (admmq_packed_hgemm_workspace_size(&qm, M, K, N, 1) > 0);
+        fails += w != admmq_packed_hlrgemm_workspace_size(&qm, M, K, N, r);
+        const size_t img = pl[1] ? (size_t)4 * (pl[0] + 1) * N * M : 0, xs = pl[1] ? (size_t)4 * pl[0] * N : 0;
+        fails += w != ((img + 15) & ~(size_t)15) + (size_t)4 * pl[2] * N * rpad;
+        fails += wx != ((img + xs + 15) & ~(size_t)15) + (size_t)4 * pl[2] * N * rpad;
+      }
+      {
+        int32_t pl[4] = {7, 7, 7, 7};
+        fails += admmq_packed_hlrgemm_plan(&qm, 64, 134, 37, 33, pl) != ADMMQ_OK || pl[0] != 3 || pl[1] != 1 || pl[2] != 3 || pl[3] != 3;
+        fails += admmq_packed_hlrgemm_plan(&qm, 1024, 65, 1024, 9, pl) != ADMMQ_OK || pl[0] != 2 || pl[1] != 0 || pl[2] != 2 || pl[3] != 2;
+        fails += admmq_packed_hlrgemm_plan(NULL, 8, 8, 4, 8, pl) != ADMMQ_ERR_ARG || admmq_packed_hlrgemm_plan(&qm, 8, 8, 4, 8, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_hlrgemm_plan(&qm, 8, 8, 4, 0, pl) != ADMMQ_ERR_ARG || admmq_packed_hlrgemm_plan(&qm, 8, 8, 4, 257, pl) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_hlrgemm_plan(&qm, 8, 8, 0, 8, pl) != ADMMQ_ERR_ARG || pl[0] != 2;
+      }
+      fails += admmq_packed_hlrgemm_workspace_size(&qm, 8, 8, 4, 8) != 4 * 4 * 32;
+      fails += admmq_packed_hlrgemm_workspace_size(NULL, 8, 8, 4, 8) != 0;
+      fails += admmq_packed_hlrgemm_workspace_size(&qm, 8, 8, 0, 8) != 0;
+      fails += admmq_packed_hlrgemm_workspace_size(&qm, 8, 8, 4, 0) != 0;
+      fails += admmq_packed_hlrgemm_workspace_size(&qm, 8, 8, 4, 257) != 0;
+      fails += admmq_packed_hlrgemm_workspace_size(&qm, (int64_t)1 << 40, 8, 8, 8) != 0;
+#define HL(cc, mm, M, K, ll, rr, fd, r, xx, xd, N, bb, yy, yd, wsp, wsb) \
+  admmq_packed_hlrgemm(cc, mm, M, K, ll, rr, fd, r, xx, xd, N, bb, yy, yd, wsp, wsb, NULL)
+      fails += HL(NULL, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, NULL, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, NULL, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, NULL, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 0, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 0, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 257, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, F32, 4, NULL, hy, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, HF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, HF, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, 3, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c + 4, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, (const void*)0x40002, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, (const void*)0x50001, BF, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, (const void*)0x10001, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, (void*)0x20002, F32, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, (const float*)0x30002, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.bad = 3;
+      fails += HL(c, &q2, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      q2 = qm; q2.scheme = ADMMQ_TENSOR_AFFINE; q2.bits = 8; q2.zero_point = 200;
+      fails += HL(c, &q2, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, (int64_t)1 << 30, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * 4 * 32 - 1) != ADMMQ_ERR_WORKSPACE;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+      fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, (void*)0x100004, 1 << 20) != ADMMQ_ERR_ARG;
+      fails += HL(c, &qx, 8, 134, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * (4 * 4 * 8 + 3 * 4 + 3 * 4 * 32) - 1) != ADMMQ_ERR_WORKSPACE;
+#undef HL
     }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
