@@ -168,6 +168,9 @@ def load() -> ctypes.CDLL:
         "admmq_packed_rowsums": (I32, [P, P, I32, I64, I64, P, P]),
         "admmq_packed_igemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_igemm": (I32, [P, P, I32, I64, I64, P, P, P, I32, I64, I32, P, P, P, P, P, P, S, P]),
+        "admmq_packed_igemv_workspace_size": (S, [P, I32, I64, I64, I64]),
+        "admmq_packed_igemv_plan": (I32, [P, I32, I64, I64, P]),
+        "admmq_packed_igemv": (I32, [P, P, I32, I64, I64, P, P, P, I64, P, P, P, P, P, P, S, P]),
         "admmq_packed_taps_i8_bytes": (S, [I32, I64]),
         "admmq_packed_taps_i8": (I32, [P, P, I32, I64, P, P]),
         "admmq_packed_idwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),

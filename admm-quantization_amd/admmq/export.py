@@ -38,7 +38,7 @@ from torch import nn
 
 from . import _lib
 from .packed import (HALF_DTYPES, PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
-                     _meta_words, _pair, _weight_dims, _igemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
+                     _meta_words, _pair, _weight_dims, _igemm, _igemv, act_encode, load_packed, packed_bytes, packed_dwgemm,
                      packed_gemm, packed_gemv, packed_hlrgemm, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
 
@@ -325,7 +325,11 @@ class IntegerPackedPair(nn.Module):
     children keep the float layer's names and are its ``PackedConv1x1`` / ``PackedLinear`` stages
     (stage 1's output quantizer is the inter-stage one); ``in_act`` and the weights' integer row
     sums travel in this module's extra state. ``last_clamped``: the device counters of the two
-    encodings of the last forward (input, inter-stage); no forward reads them."""
+    encodings of the last forward (input, inter-stage); no forward reads them. ``skinny`` (an attribute,
+    default ``False``, not part of the state dict - an old state loads to the same module): both stages of
+    a linear pair take ``k_packed_igemv`` / ``k_packed_igemv_t`` at at most ``GEMV_N_MAX`` rows (the same bits,
+    DESIGN.md 2.36); conv pairs ignore it."""
+    skinny = False
 
     def __init__(self, names, stage1: _PackedWeight, stage2: _PackedWeight, in_act):
         super().__init__()
@@ -375,14 +379,22 @@ class IntegerPackedPair(nn.Module):
         mid = s1._act
         if mid is None or not 2 <= mid[0] <= 8:
             raise ValueError("integer layer: stage 1 needs its output quantizer with 2 <= bits <= 8 (it writes codes)")
+        out = s2._act if s2._act is not None else (0, 0.0, 0.0)
+        if self.skinny and s1._layout == 1 and s2._layout == 1 and skinny_rows(xq.codes, s1.in_features):
+            h = _igemv(s1.codes, s1._meta, s1.transpose, s1.out_features, s1.in_features, xq.codes, self._in_act,
+                       self._rowsums(0), s1.bias, mid, True)
+            self.last_clamped = (xq.clamped, h.clamped)
+            return _igemv(s2.codes, s2._meta, s2.transpose, s2.out_features, s2.in_features, h.codes, mid, self._rowsums(1),
+                          s2.bias, out, False)
         h = _igemm(s1.codes, s1._meta, s1.transpose, s1.out_features, s1.in_features, xq.codes, self._in_act, self._rowsums(0),
                    s1._layout, s1.bias, mid, True)
         self.last_clamped = (xq.clamped, h.clamped)
         return _igemm(s2.codes, s2._meta, s2.transpose, s2.out_features, s2.in_features, h.codes, mid, self._rowsums(1),
-                      s2._layout, s2.bias, s2._act if s2._act is not None else (0, 0.0, 0.0), False)
+                      s2._layout, s2.bias, out, False)
 
     def extra_repr(self):
-        return f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]})"
+        return (f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]})"
+                + (", skinny=True" if self.skinny else ""))
 
 
 def _integer_pair(who, names, factors, acts, in_act, make):

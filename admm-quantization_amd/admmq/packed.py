@@ -22,6 +22,8 @@ int8 stencil over the codes feeds the int8 MFMA).
 ``packed_gemv`` is the decode-shape product: at most ``GEMV_N_MAX`` rows of float32 / bfloat16 / float16
 activations through a packed weight with plain FMAs from the codes (``k_packed_gemv`` / ``k_packed_gemv_t``: no
 MFMA tile, no LDS weight image). ``packed_linear(..., skinny=True)`` routes to it.
+``packed_igemv`` is the same for activation codes (``k_packed_igemv`` / ``k_packed_igemv_t`` on the dot4 unit: exact
+integer sums, ``packed_igemm``'s bits); ``packed_linear_int(..., skinny=True)`` routes to it.
 
 ``PackedLowRank`` is the deployable form of ``admmq.lowrank``'s ``W ~ W_q + W_r``: ``W_q`` as packed
 codes, ``W_r`` as its thin factors ``L [M, r]``, ``Rt [r, K]``; ``packed_lowrank_linear`` evaluates
@@ -46,7 +48,7 @@ from . import _lib
 
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
            "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
-           "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_linear_int",
+           "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_igemv", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
            "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
 
@@ -730,16 +732,71 @@ def _igemm(codes, meta_words, transpose, M, K, x, x3, rowsums, x_layout, bias, o
 _opaque_igemm = torch.compiler.disable(_igemm)
 
 
+def packed_igemv(codes: torch.Tensor, meta_words: torch.Tensor, transpose: bool, M: int, K: int,
+                 xq: QuantizedActivation, rowsums: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 act=None, out_codes: bool = False):
+    """The skinny integer product for decode shapes (``admmq_packed_igemv``): ``packed_igemm`` in
+    the linear layout for ``xq.codes [..., K]`` of at most ``GEMV_N_MAX`` rows, on the dot4 unit (no MFMA tile, no
+    LDS weight image). The sums are exact integers, so every output form has ``packed_igemm``'s bits.
+    Inference only."""
+    x3 = _in_triple(xq, "packed_igemv")
+    o3 = _out_triple(act, out_codes, "packed_igemv")
+    return _igemv(codes, meta_words, bool(transpose), int(M), int(K), xq.codes, x3, rowsums, bias, o3, bool(out_codes))
+
+
+def _igemv(codes, meta_words, transpose, M, K, x, x3, rowsums, bias, o3, out_codes):
+    """The call behind ``packed_igemv`` on checked quantizers ``x3`` / ``o3 = (bits, mn, rng)``."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise TypeError("packed_igemv: xq.codes must be a uint8 tensor")
+    _require_gpu("packed_igemv", "codes and activations", x, codes)
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_igemm
+        return _opaque_igemv(codes, meta_words, transpose, M, K, x, x3, rowsums, bias, o3, out_codes)
+    oshape, _, N, xc = _gemm_geometry("packed_igemv", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    if N > GEMV_N_MAX:
+        raise ValueError(f"packed_igemv: x must hold 1..{GEMV_N_MAX} rows, got {N}")
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_igemv (csrc/torch_ops.cpp) -> admmq_packed_igemv
+        y, clamped = _lib.ops().packed_igemv(codes, meta_words, transpose, M, K, xc, x3[0], x3[1], x3[2], rowsums, bias,
+                                             o3[0], o3[1], o3[2], out_codes)
+    else:
+        lib = _lib.load()
+        (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_igemv", bias, M)
+        if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
+            raise ValueError(f"packed_igemv: rowsums must be int32 [{M}]")
+        xr, oq = _actq(x3), _actq(o3)
+        y = torch.empty(oshape, dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
+        clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
+        nbytes = lib.admmq_packed_igemv_workspace_size(ctypes.byref(meta), 1 if transpose else 0, M, K, N)
+        ws = _lib.workspace(nbytes, x.device) if nbytes else None   # (the one-launch plan needs none)
+        rc = lib.admmq_packed_igemv(_lib.ptr(cc), ctypes.byref(meta), 1 if transpose else 0, M, K, _lib.ptr(xc),
+                                    ctypes.byref(xr), _lib.ptr(rowsums.contiguous()), N, _lib.ptr(bc),
+                                    _lib.ptr(None if out_codes else y), _lib.ptr(y if out_codes else None), _byref(oq),
+                                    _lib.ptr(clamped if out_codes else None), _lib.ptr(ws), nbytes,
+                                    _lib.stream_handle(x.device))
+        _lib.check(rc, "packed_igemv")
+    if out_codes:
+        return QuantizedActivation(y, o3[0], o3[1], o3[2], clamped)
+    return y
+
+
+_opaque_igemv = torch.compiler.disable(_igemv)
+
+
 def packed_linear_int(xq: QuantizedActivation, p: "PackedTensor", bias: Optional[torch.Tensor] = None,
-                      transpose: bool = False, act=None, out_codes: bool = False):
+                      transpose: bool = False, act=None, out_codes: bool = False, skinny: bool = False):
     """``packed_linear`` on activation codes, in integer arithmetic: ``xq.codes [..., K] -> [..., M]``
     (a float tensor, or with ``out_codes=True`` - which needs ``act`` - a ``QuantizedActivation``).
-    The weight's row sums are computed on the first call and kept on ``p``."""
+    The weight's row sums are computed on the first call and kept on ``p``. ``skinny=True`` sends codes of at
+    most ``GEMV_N_MAX`` rows to ``packed_igemv`` (the decode kernel; the same bits, every output form) and any
+    other input down the default route."""
     transpose = bool(transpose)
     e = _int_plan(p, transpose, "packed_linear_int")
     o3 = _out_triple(act, out_codes, "packed_linear_int")
     x3 = _in_triple(xq, "packed_linear_int")
     rs = e[2] if e[2] is not None else packed_rowsums(p, transpose)
+    if skinny and skinny_rows(xq.codes, e[1]):
+        return _igemv(p.codes, _meta_words(p), transpose, e[0], e[1], xq.codes, x3, rs, bias, o3, bool(out_codes))
     return _igemm(p.codes, _meta_words(p), transpose, e[0], e[1], xq.codes, x3, rs, 1, bias, o3, bool(out_codes))
 
 

@@ -18,6 +18,7 @@
 //   admmq::packed_hdwgemm          that stage on bfloat16 / float16 activations
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
+//   admmq::packed_igemv            the skinny integer GEMV for 1..8 rows of activation codes
 //   admmq::packed_taps_i8, packed_idwgemm   int8 tap image and the integer fused depthwise + 1x1 stage
 //   admmq::quantize_channel        <- source/quantization.py:29-33, 91-106 (channel_* schemes with a dim)
 //   admmq::cp_gram_mttkrp          <- scripts/factorize.py:215-237 / :276-287 (G, F of one mode)
@@ -593,6 +594,63 @@ std::tuple<at::Tensor, at::Tensor> packed_igemm_meta(const at::Tensor& codes, co
   (void)codeq_of(x_bits, x_mn, x_rng, "packed_igemm");
   (void)outq_of(out_codes, out_bits, out_mn, out_rng, "packed_igemm");
   return {at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(out_codes ? at::kByte : at::kFloat)),
+          at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
+}
+
+// --- skinny integer GEMV ------------------------------------------------------------
+// admmq_packed_igemv: packed_igemm's value for a code tensor x [..., K] of at most ADMMQ_GEMV_N_MAX
+// rows (the linear layout) -> [..., M], float32 or codes, with the clamp counter as packed_igemm's.
+std::vector<int64_t> packed_igemv_shape(const at::Tensor& x, int64_t M, int64_t K) {
+  TORCH_CHECK(x.scalar_type() == at::kByte, "admmq: packed_igemv: x must be a uint8 code tensor, got ", x.scalar_type());
+  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_igemv: M and K must be positive");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K, "admmq: packed_igemv: x must be [..., ", K, "], got ", x.sizes());
+  const int64_t N = x.numel() / K;
+  TORCH_CHECK(N >= 1 && N <= ADMMQ_GEMV_N_MAX, "admmq: packed_igemv: x must hold 1..", ADMMQ_GEMV_N_MAX, " rows, got ", N);
+  std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
+  shape.back() = M;
+  return shape;
+}
+
+std::tuple<at::Tensor, at::Tensor> packed_igemv_cuda(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w,
+                                                     int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits, double x_mn,
+                                                     double x_rng, const at::Tensor& rowsums,
+                                                     const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
+                                                     double out_rng, bool out_codes) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte, "admmq: packed_igemv: x must be a uint8 code tensor on the GPU");
+  const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_igemv");
+  const admmq_actq oq = outq_of(out_codes, out_bits, out_mn, out_rng, "packed_igemv");
+  admmq_qmeta meta;
+  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, "packed_igemv", meta);
+  check_same_device(codes, x, "codes");
+  check_rowsums(rowsums, x, M, "packed_igemv");
+  const std::vector<int64_t> oshape = packed_igemv_shape(x, M, K);
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor rc = rowsums.contiguous();
+  const at::Tensor bc = bias_of(bias, x, M, "packed_igemv", true);
+  const int64_t N = xc.numel() / K;
+  at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
+  at::Tensor clamped = at::empty({out_codes ? 1 : 0}, xc.options().dtype(at::kInt));
+  const size_t nbytes = admmq_packed_igemv_workspace_size(&meta, trans_w ? 1 : 0, M, K, N);
+  at::Tensor ws;   // (the one-launch plan needs none: no allocation)
+  if (nbytes > 0) ws = workspace(nbytes, xc);
+  check_rc(admmq_packed_igemv(cc.data_ptr<uint8_t>(), &meta, trans_w ? 1 : 0, M, K, xc.data_ptr<uint8_t>(), &xq,
+                              rc.data_ptr<int32_t>(), N, f32_or_null(bc), out_codes ? nullptr : y.data_ptr<float>(),
+                              out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq,
+                              out_codes ? clamped.data_ptr<int32_t>() : nullptr, nbytes > 0 ? ws.data_ptr() : nullptr,
+                              nbytes > 0 ? static_cast<size_t>(ws.numel()) : 0, stream_of(xc)),
+           "packed_igemv");
+  return {y, clamped};
+}
+
+std::tuple<at::Tensor, at::Tensor> packed_igemv_meta(const at::Tensor& codes, const at::Tensor& meta_words, bool trans_w,
+                                                     int64_t M, int64_t K, const at::Tensor& x, int64_t x_bits, double x_mn,
+                                                     double x_rng, const at::Tensor& rowsums,
+                                                     const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
+                                                     double out_rng, bool out_codes) {
+  (void)codeq_of(x_bits, x_mn, x_rng, "packed_igemv");
+  (void)outq_of(out_codes, out_bits, out_mn, out_rng, "packed_igemv");
+  return {at::empty(packed_igemv_shape(x, M, K), x.options().dtype(out_codes ? at::kByte : at::kFloat)),
           at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
 }
 
@@ -1258,6 +1316,9 @@ TORCH_LIBRARY(admmq, m) {
   m.def("packed_igemm(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_bits, float x_mn, "
         "float x_rng, Tensor rowsums, int x_layout, Tensor? bias, int out_bits, float out_mn, float out_rng, "
         "bool out_codes) -> (Tensor y, Tensor clamped)");
+  m.def("packed_igemv(Tensor codes, Tensor meta_words, bool trans_w, int M, int K, Tensor x, int x_bits, float x_mn, "
+        "float x_rng, Tensor rowsums, Tensor? bias, int out_bits, float out_mn, float out_rng, bool out_codes) "
+        "-> (Tensor y, Tensor clamped)");
   m.def("packed_taps_i8(Tensor codes, Tensor meta_words, int ntaps, int K) -> Tensor");
   m.def("packed_idwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, int x_bits, float x_mn, float x_rng, "
         "Tensor taps_i8, float s_c, int kh, int kw, int sh, int sw, int ph, int pw, Tensor rowsums, Tensor? bias, "
@@ -1289,6 +1350,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("act_decode", &act_decode_cuda);
   m.impl("packed_rowsums", &packed_rowsums_cuda);
   m.impl("packed_igemm", &packed_igemm_cuda);
+  m.impl("packed_igemv", &packed_igemv_cuda);
   m.impl("packed_taps_i8", &packed_taps_i8_cuda);
   m.impl("packed_idwgemm", &packed_idwgemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
@@ -1316,6 +1378,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("act_decode", &act_decode_meta);
   m.impl("packed_rowsums", &packed_rowsums_meta);
   m.impl("packed_igemm", &packed_igemm_meta);
+  m.impl("packed_igemv", &packed_igemv_meta);
   m.impl("packed_taps_i8", &packed_taps_i8_meta);
   m.impl("packed_idwgemm", &packed_idwgemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);

@@ -599,6 +599,43 @@ int32_t admmq_packed_lrgemv(const uint8_t* codes, const admmq_qmeta* meta, int64
                             const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* Skinny integer GEMV: admmq_packed_igemm at decode shapes, for 1 <= N <=
+ * ADMMQ_GEMV_N_MAX rows of activation codes x [N, K] (uint8, any address) in the linear layout,
+ * y / y_codes [N, M] row-major, W = D (trans_w 0, the packed tensor is [M, K]) or D^T (trans_w 1,
+ * it is [K, M]). No MFMA and no LDS weight image: the sums run on v_dot4_u32_u8 over the raw
+ * weight and activation codes (k_packed_igemv, k_packed_igemv_t; k_packed_igemv_reduce where K is
+ * split over workgroups),
+ *   U[c,m] = sum_k uw[m,k] ux[c,k]     Sx[c] = sum_k ux[c,k]     S = U - (q + zp) Sx   (int64)
+ * Value: exactly admmq_packed_igemm's formula ("Integer packed GEMM" above) on the exact integer S
+ * and on A[m] = rowsums[m]. Every sum is an integer, so the output bits equal those of
+ * admmq_packed_igemm on the same arguments with x_layout = 1, nb = 1 - at every N, on every call
+ * and in both plans; there is no other-sum-order caveat. U <= 255 * 255 * 65536 < 2^32 holds at
+ * the limit K = 65536 in the instruction's uint32 accumulator.
+ * The three output forms and the clamped counter are admmq_packed_igemm's: y float32 (with out_q
+ * on, bits 1..24: admmq_fixed_quantize of it) or y_codes uint8 (out_q on, bits 2..8) with
+ * *clamped (may be NULL) zeroed on the stream first - by a one-thread kernel, not a memset - and
+ * each clamped element counted once; every output byte is written by exactly one thread.
+ * rowsums: admmq_packed_rowsums of the same weight and orientation (the epilogue's mn_x A[m]).
+ * `meta` is a HOST record. Refusals, all before any launch, each with its own admmq_last_error
+ * text: admmq_packed_igemm's (ADMMQ_ERR_SCHEME for tensor_minmax; ADMMQ_ERR_ARG for an affine
+ * record outside int8, K > 65536, activation bits outside 2..8, both or neither of y / y_codes,
+ * NULL codes / meta / x / x_q / rowsums, non-positive or out-of-range sizes, trans_w other than 0
+ * or 1, misaligned codes (16 bytes) / y / bias / rowsums / clamped / workspace (4 bytes)), N
+ * outside 1..ADMMQ_GEMV_N_MAX (ADMMQ_ERR_ARG), and ADMMQ_ERR_WORKSPACE for a short workspace.
+ * The plan is a pure function of (trans_w, M, K, meta->bits): ns ranges of ks k over gridDim.z.
+ * admmq_packed_igemv_plan writes out = (ks, ns, launches), launches = 1 (ns = 1) or 2 (the
+ * reduce), not counting the counter's reset; ADMMQ_ERR_ARG (and nothing written) for arguments
+ * out of range. admmq_packed_igemv_workspace_size: 0 for a NULL meta or arguments out of range
+ * and when ns = 1; else 4 ns N (M + 1) bytes, the uint32 images of U [ns][N][M] and of Sx
+ * [ns][N]. No output is combined with atomics and no workgroup waits for another. No entry point
+ * allocates or synchronises. */
+size_t admmq_packed_igemv_workspace_size(const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K, int64_t N);
+int32_t admmq_packed_igemv_plan(const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K, int32_t out[3]);
+int32_t admmq_packed_igemv(const uint8_t* codes, const admmq_qmeta* meta, int32_t trans_w, int64_t M, int64_t K,
+                           const uint8_t* x, const admmq_actq* x_q, const int32_t* rowsums, int64_t N, const float* bias,
+                           float* y, uint8_t* y_codes, const admmq_actq* out_q, int32_t* clamped, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* Half-precision quant + low-rank GEMM: the layer W ~ D + L Rt at any row count
  * N >= 1 of x [N, K] in bfloat16 or float16 (type T, u = 2^-8 / 2^-11), on
  * v_mfma_f32_32x32x16_{bf16,f16}. D [M, K] from codes (bits 1..8, the four tensor schemes, no
