@@ -23,7 +23,8 @@ bfloat16 / float16 input ``k_packed_hdwgemm``).
 ``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
 activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
 ``build_qlr_layer`` turns the ``PackedLowRank`` of ``admmq.lowrank`` (``W ~ W_q + L Rt``) into a
-``PackedLowRankLinear``: codes and thin factors, one GEMM (``k_packed_lrgemm``).
+``PackedLowRankLinear``: codes and thin factors, one GEMM (``k_packed_lrgemm``); with
+``integer=True`` into an ``IntegerPackedLowRank`` on activation codes (``k_packed_ilrgemm``).
 ``integer=True`` of ``build_cp_layer`` returns an ``IntegerPackedCP``: ``conv1`` on ``k_packed_igemm`` and
 the fused depthwise + 1x1 stage on ``k_packed_idwgemm`` (an int8 stencil feeding the int8 MFMA).
 """
@@ -38,7 +39,7 @@ from torch import nn
 
 from . import _lib
 from .packed import (HALF_DTYPES, PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
-                     _meta_words, _pair, _weight_dims, _igemm, _igemv, act_encode, load_packed, packed_bytes, packed_dwgemm,
+                     _meta_words, _pair, _weight_dims, _factorsums, _igemm, _igemv, _ilrgemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
                      packed_gemm, packed_gemv, packed_hlrgemm, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
 
@@ -227,10 +228,87 @@ class PackedLowRankLinear(_PackedWeight):
                 + (", fused=True" if self.fused else ""))
 
 
-def build_qlr_layer(p: PackedLowRank, bias: Optional[torch.Tensor] = None) -> PackedLowRankLinear:
+_TAIL_NAMES = {"bfloat16": torch.bfloat16, "float16": torch.float16}
+
+
+class IntegerPackedLowRank(nn.Module):
+    """A quant + low-rank linear layer on integer activations: the float input is encoded once by
+    ``in_act`` (``k_act_encode``) and ``packed_ilrgemm`` runs ``W_q`` on the int8 MFMA and ``L Rt`` on the 16-bit
+    MFMA in ``tail_dtype``; the output is float32. The child ``linear`` is the float layer's ``PackedLowRankLinear``
+    (codes, factors, bias); ``in_act``, the tail type, the weight's integer row sums and the factor sums travel in
+    this module's extra state, in ``IntegerPackedPair``'s manner. ``last_clamped``: the device counter of the last
+    forward's input encoding; no forward reads it."""
+
+    def __init__(self, linear: "PackedLowRankLinear", in_act, tail_dtype=torch.bfloat16):
+        super().__init__()
+        if tail_dtype not in HALF_DTYPES:
+            raise TypeError(f"IntegerPackedLowRank: tail_dtype must be torch.bfloat16 or torch.float16, got {tail_dtype}")
+        self.linear = linear
+        self._in_act = in_act   # (bits, mn, rng), resolved float32 values
+        self.tail_dtype = tail_dtype
+        self._rs = None
+        self._rho = None        # (Rt, its version, rho)
+        self.last_clamped = None
+        if linear.codes.device.type == "cuda":
+            self._rowsums(), self._factorsums()
+
+    def _rowsums(self):
+        st = self.linear
+        if self._rs is None:
+            self._rs = packed_rowsums(st.packed(), False)
+        elif self._rs.device != st.codes.device:
+            self._rs = self._rs.to(st.codes.device)
+        return self._rs
+
+    def _factorsums(self):
+        Rt = self.linear.Rt
+        c = self._rho
+        if c is None or c[0] is not Rt or c[1] != Rt._version:
+            c = self._rho = (Rt, Rt._version, _factorsums(Rt, self.tail_dtype))
+        return c[2]
+
+    def get_extra_state(self):
+        return dict(in_act=list(self._in_act), tail_dtype=str(self.tail_dtype).replace("torch.", ""),
+                    rowsums=None if self._rs is None else self._rs.detach().cpu())
+
+    def set_extra_state(self, state):
+        a = state["in_act"]
+        self._in_act = (int(a[0]), float(a[1]), float(a[2]))
+        self.tail_dtype = _TAIL_NAMES[state["tail_dtype"]]
+        r = state.get("rowsums")
+        if r is not None and (r.dtype != torch.int32 or tuple(r.shape) != (self.linear.out_features,)):
+            raise ValueError(f"integer layer state: row sums must be int32 [{self.linear.out_features}], got {r.dtype} "
+                             f"{tuple(r.shape)}")
+        self._rs, self._rho = r, None   # (the factor sums follow Rt: one small launch at the next forward)
+
+    @torch.compiler.disable
+    def forward(self, x):
+        st = self.linear
+        xq = act_encode(x, _lib.ActQ(self._in_act[0], 1, self._in_act[1], self._in_act[2]), check=False)
+        self.last_clamped = xq.clamped
+        return _ilrgemm(st.codes, st._meta, st.out_features, st.in_features, st.L, st.Rt, self._factorsums(), xq.codes,
+                        self._in_act, self._rowsums(), st.bias, (0, 0.0, 0.0), False, self.tail_dtype)
+
+    def extra_repr(self):
+        return (f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]}), "
+                f"tail_dtype={self.tail_dtype}")
+
+
+def build_qlr_layer(p: PackedLowRank, bias: Optional[torch.Tensor] = None, integer: bool = False, in_act=None,
+                    tail_dtype=torch.bfloat16):
     """The linear layer of a quant + low-rank factorization (``factorize_lowrank(..., return_packed=True)`` or
-    ``load_packed_lowrank``): ``y = (W_q + L Rt) x + bias`` straight from the codes and the factors."""
-    return PackedLowRankLinear(p, bias)
+    ``load_packed_lowrank``): ``y = (W_q + L Rt) x + bias`` straight from the codes and the factors.
+    ``integer=True`` with ``in_act = (bits, min_val, max_val)`` (bits 2..8) returns an ``IntegerPackedLowRank``: the
+    input is encoded to codes and the layer runs ``packed_ilrgemm`` with its tail in ``tail_dtype``."""
+    lin = PackedLowRankLinear(p, bias)
+    if not integer:
+        return lin
+    if in_act is None:
+        raise ValueError("build_qlr_layer: integer=True needs in_act, the (bits, min_val, max_val) quantizer of the layer's input")
+    if not 2 <= int(in_act[0]) <= 8:
+        raise ValueError(f"build_qlr_layer: in_act needs 2 <= bits <= 8 for activation codes, got {in_act[0]}")
+    _int_weight_dims(p.q, False, "build_qlr_layer")
+    return IntegerPackedLowRank(lin, _PackedWeight._resolve_act(*in_act), tail_dtype)
 
 
 class PackedConv1x1(_PackedWeight):

@@ -50,7 +50,8 @@ __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed"
            "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_igemv", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
-           "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear", "save_packed_lowrank", "load_packed_lowrank"]
+           "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear",
+           "packed_lowrank_factorsums", "packed_ilrgemm", "packed_lowrank_linear_int", "save_packed_lowrank", "load_packed_lowrank"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -1316,6 +1317,138 @@ def packed_lowrank_linear(x: torch.Tensor, p: "PackedLowRank", bias: Optional[to
     if fused and x.dtype in HALF_DTYPES:
         return packed_hlrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
     return packed_lrgemm(p.q.codes, _meta_words(p.q), M, K, p.L, p.Rt, x, bias, out_dtype)
+
+
+# --- quant + low-rank on activation codes ---------------------------------------
+def _tail_code(tail_dtype, who: str) -> int:
+    if tail_dtype not in HALF_DTYPES:
+        raise TypeError(f"admmq: {who}: tail_dtype must be torch.bfloat16 or torch.float16, got {tail_dtype}")
+    return HALF_DTYPES[tail_dtype]
+
+
+def _tail_factors(who: str, L: torch.Tensor, Rt: torch.Tensor, M: int, K: int, tail_dtype) -> int:
+    """The rank of ``L [M, r]`` / ``Rt [r, K]``, both float32 or both of ``tail_dtype``, checked on the host."""
+    if L.dim() != 2 or Rt.dim() != 2 or L.shape[0] != M or Rt.shape[1] != K or L.shape[1] != Rt.shape[0]:
+        raise ValueError(f"{who}: L must be [{M}, r] and Rt [r, {K}], got {tuple(L.shape)} and {tuple(Rt.shape)}")
+    if L.dtype != Rt.dtype or (L.dtype != torch.float32 and L.dtype != tail_dtype):
+        raise TypeError(f"admmq: {who}: L and Rt must both be float32 or both of the tail dtype {tail_dtype}, got "
+                        f"{L.dtype} and {Rt.dtype}")
+    r = int(L.shape[1])
+    if not 1 <= r <= RANK_MAX:
+        raise ValueError(f"{who}: rank must be 1..{RANK_MAX}, got {r}")
+    return r
+
+
+@torch.compiler.disable
+def _factorsums(Rt: torch.Tensor, tail_dtype) -> torch.Tensor:
+    """``rho [r]`` of ``Rt [r, K]`` (float32 or ``tail_dtype``) by ``k_ilr_factorsums``."""
+    tdt = _tail_code(tail_dtype, "packed_lowrank_factorsums")
+    _require_gpu("packed_lowrank_factorsums", "factor Rt", Rt)
+    if Rt.dim() != 2 or not 1 <= Rt.shape[0] <= RANK_MAX or Rt.shape[1] < 1 or Rt.dtype not in (torch.float32, tail_dtype):
+        raise ValueError(f"packed_lowrank_factorsums: Rt must be [r, K] with rank 1..{RANK_MAX}, float32 or {tail_dtype}, got "
+                         f"{tuple(Rt.shape)} {Rt.dtype}")
+    Rc = Rt.detach().contiguous()
+    if _lib.use_ops():   # torch.ops.admmq.packed_lowrank_factorsums (csrc/torch_ops.cpp)
+        return _lib.ops().packed_lowrank_factorsums(Rc, tdt)
+    rho = torch.empty(Rc.shape[0], dtype=torch.float32, device=Rc.device)
+    _lib.check(_lib.load().admmq_packed_lowrank_factorsums(_lib.ptr(Rc), GEMV_DTYPES[Rc.dtype], tdt, int(Rc.shape[0]),
+                                                           int(Rc.shape[1]), _lib.ptr(rho), _lib.stream_handle(Rc.device)),
+               "packed_lowrank_factorsums")
+    return rho
+
+
+def packed_lowrank_factorsums(p: "PackedLowRank", tail_dtype=torch.bfloat16) -> torch.Tensor:
+    """``rho[j] = float(sum_k double(Rt_T[j, k]))`` (float32 ``[r]``) of ``p.Rt`` as rounded to ``tail_dtype``, in the
+    fixed order of ``k_ilr_factorsums``; kept on ``p`` while ``Rt`` is unchanged, the way the row
+    sums are."""
+    _tail_code(tail_dtype, "packed_lowrank_factorsums")
+    if not isinstance(p, PackedLowRank):
+        raise TypeError("expected a PackedLowRank")
+    Rt = p.Rt
+    c = getattr(p, "_fs", None)
+    if c is None or c[0] is not Rt or c[1] != Rt._version:
+        c = p._fs = (Rt, Rt._version, {})
+    if tail_dtype not in c[2]:
+        c[2][tail_dtype] = _factorsums(Rt, tail_dtype)
+    return c[2][tail_dtype]
+
+
+def packed_ilrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
+                   rho: torch.Tensor, xq: QuantizedActivation, rowsums: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   act=None, out_codes: bool = False, tail_dtype=torch.bfloat16):
+    """The quant + low-rank product on activation codes (``admmq_packed_ilrgemm``):
+    ``y = x^ (D + L Rt)^T (+ bias)`` for ``xq.codes [..., K]`` of any row count, ``x^`` the decoded codes. The code
+    product runs on the int8 MFMA (``packed_igemm``'s exact integer sums), the rank-``r`` branch on the 16-bit MFMA
+    in ``tail_dtype``: ``L [M, r]`` and ``Rt [r, K]`` are both float32 (rounded once to ``tail_dtype`` as they are
+    staged) or both of ``tail_dtype``; ``rho`` is ``packed_lowrank_factorsums`` of ``Rt`` and ``rowsums``
+    ``packed_rowsums`` of the weight. The result is ``packed_igemm``'s: a float32 tensor (quantized by ``act`` when
+    given) or, with ``out_codes=True``, a ``QuantizedActivation``. With ``L = 0`` it has ``packed_igemm``'s bits.
+    Inference only."""
+    x3 = _in_triple(xq, "packed_ilrgemm")
+    o3 = _out_triple(act, out_codes, "packed_ilrgemm")
+    return _ilrgemm(codes, meta_words, int(M), int(K), L, Rt, rho, xq.codes, x3, rowsums, bias, o3, bool(out_codes), tail_dtype)
+
+
+def _ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype):
+    """The call behind ``packed_ilrgemm`` on checked quantizers ``x3`` / ``o3 = (bits, mn, rng)``."""
+    tdt = _tail_code(tail_dtype, "packed_ilrgemm")
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
+        raise TypeError("packed_ilrgemm: xq.codes must be a uint8 tensor")
+    _require_gpu("packed_ilrgemm", "codes, factors and activations", x, codes, L, Rt, rho)
+    _inference_only("packed_ilrgemm", L, "L")
+    _inference_only("packed_ilrgemm", Rt, "Rt")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_igemm
+        return _opaque_ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype)
+    L, Rt = L.detach(), Rt.detach()
+    r = _tail_factors("packed_ilrgemm", L, Rt, M, K, tail_dtype)
+    oshape, _, N, xc = _gemm_geometry("packed_ilrgemm", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    if bias is not None:
+        bias = bias.detach()
+    if _lib.use_ops():   # torch.ops.admmq.packed_ilrgemm (csrc/torch_ops.cpp) -> admmq_packed_ilrgemm
+        y, clamped = _lib.ops().packed_ilrgemm(codes, meta_words, M, K, L, Rt, rho, tdt, xc, x3[0], x3[1], x3[2], rowsums, bias,
+                                               o3[0], o3[1], o3[2], out_codes)
+    else:
+        lib = _lib.load()
+        (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_ilrgemm", bias, M)
+        if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
+            raise ValueError(f"packed_ilrgemm: rowsums must be int32 [{M}]")
+        if rho.dtype != torch.float32 or tuple(rho.shape) != (r,):
+            raise ValueError(f"packed_ilrgemm: rho must be float32 [{r}]")
+        Lc, Rc = L.contiguous(), Rt.contiguous()
+        xr, oq = _actq(x3), _actq(o3)
+        y = torch.empty(oshape, dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
+        clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
+        ws = _lib.workspace(lib.admmq_packed_ilrgemm_workspace_size(M, K, N, r), x.device)
+        rc = lib.admmq_packed_ilrgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), GEMV_DTYPES[L.dtype],
+                                      tdt, r, _lib.ptr(rho.contiguous()), _lib.ptr(xc), ctypes.byref(xr),
+                                      _lib.ptr(rowsums.contiguous()), N, _lib.ptr(bc), _lib.ptr(None if out_codes else y),
+                                      _lib.ptr(y if out_codes else None), _byref(oq), _lib.ptr(clamped if out_codes else None),
+                                      _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
+        _lib.check(rc, "packed_ilrgemm")
+    if out_codes:
+        return QuantizedActivation(y, o3[0], o3[1], o3[2], clamped)
+    return y
+
+
+_opaque_ilrgemm = torch.compiler.disable(_ilrgemm)
+
+
+def packed_lowrank_linear_int(xq: QuantizedActivation, p: "PackedLowRank", bias: Optional[torch.Tensor] = None, act=None,
+                              out_codes: bool = False, tail_dtype=torch.bfloat16):
+    """``packed_lowrank_linear`` on activation codes: ``xq.codes [..., K] -> [..., M]`` through ``packed_ilrgemm``
+    (int8 MFMA for ``W_q``, 16-bit MFMA in ``tail_dtype`` for ``L Rt``) - a float32 tensor, or with
+    ``out_codes=True`` (which needs ``act``) a ``QuantizedActivation``. The weight's row sums and the factor sums are
+    computed on the first call and kept on ``p``. Opt-in: nothing routes here by itself. Inference only."""
+    if not isinstance(p, PackedLowRank):
+        raise TypeError("expected a PackedLowRank")
+    e = _int_plan(p.q, False, "packed_lowrank_linear_int")
+    o3 = _out_triple(act, out_codes, "packed_lowrank_linear_int")
+    x3 = _in_triple(xq, "packed_lowrank_linear_int")
+    _tail_code(tail_dtype, "packed_lowrank_linear_int")
+    _tail_factors("packed_lowrank_linear_int", p.L, p.Rt, e[0], e[1], tail_dtype)
+    rs = e[2] if e[2] is not None else packed_rowsums(p.q, False)
+    rho = packed_lowrank_factorsums(p, tail_dtype)
+    return _ilrgemm(p.q.codes, _meta_words(p.q), e[0], e[1], p.L, p.Rt, rho, xq.codes, x3, rs, bias, o3, bool(out_codes), tail_dtype)
 
 
 def save_packed_lowrank(path: str, p: "PackedLowRank") -> None:

@@ -684,6 +684,76 @@ int32_t admmq_packed_hlrgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
                              const float* bias, void* y, int32_t y_dtype, void* workspace, size_t workspace_bytes,
                              void* stream);
 
+/* Integer quant + low-rank GEMM: the layer W ~ D + L Rt on activation codes, at
+ * any row count N >= 1:
+ *   y[N, M] = x^[N, K] (D + L Rt)^T (+ bias[M]),   x^ = g ux + mn_x,  g = rng_x / n_x,  n_x = 2^bits_x - 1
+ * The code product runs on v_mfma_i32_32x32x32_i8, the rank-r branch on
+ * v_mfma_f32_32x32x16_{bf16,f16}; no decoded copy of the codes is written.
+ *   ux [N, K] uint8 activation codes (any address) with their admmq_actq x_q (bits 2..8).
+ *   codes, meta, rowsums: the packed W_q = D [M, K] and A[m] exactly as admmq_packed_igemm takes
+ *     them, with trans_w = 0, the linear layout and nb = 1: no tensor_minmax, an int8-fitting
+ *     a = (uw - q) - zp, K <= 65536.
+ *   L [M, r], Rt [r, K] row-major, 1 <= r <= 256, both of one type f_dtype: ADMMQ_DT_F32 or the tail
+ *     type T = t_dtype (ADMMQ_DT_BF16 or ADMMQ_DT_F16, u = 2^-8 / 2^-11). A float32 factor is rounded
+ *     once, to nearest even, to T as it is staged (L_T, Rt_T); one representable in T enters exactly.
+ *   rho [r] float32: admmq_packed_lowrank_factorsums of (Rt, f_dtype, t_dtype), once per weight:
+ *     rho[j] = float(sum_k double(Rt_T[j, k])), the order fixed: one wave a row j, lane l adds
+ *     k = l, l + 64, ... in double in increasing k, and the 64 partials are added in increasing l.
+ * Arithmetic:
+ *   S[c, m] = sum_k a[m, k] ux[c, k], the exact integer sum, in admmq_packed_igemm's tile, K pieces
+ *     and two regimes for (M, K, N, nb = 1).
+ *   U32[c, j] = sum_k Rt_T[j, k] ux[c, k] on the 16-bit MFMA; the code enters as an exact T integer.
+ *     K is cut into nsd ranges (1 <= nsd <= 8, a pure function of (K, r, N): admmq_packed_hlrgemm's
+ *     rule), a range is one accumulator chain from zero in steps of 16 k, the ranges are added in
+ *     range order.
+ *   t32[c, j] = float(gd * double(U32) + double(mn_x) * double(rho[j])), gd = double(rng_x) /
+ *     double(n_x), every double operation rounded on its own; t_T = t32 rounded once to nearest
+ *     even to T (fp16 subnormals kept).
+ *   q[c, m] = sum_j L_T[m, j] t_T[c, j]: one 16-bit MFMA chain from zero, j zero padded to the
+ *     32-wide step.
+ *   y[c, m] = float(double(scale) * (gd * double(S) + double(mn_x) * double(A[m])) + double(q)
+ *                   + double(bias[m])): every operation in double and rounded on its own, the bias
+ *     added only when given, one rounding to float32.
+ * Outputs: admmq_packed_igemm's three forms - y float32 (with out_q on, bits 1..24:
+ * admmq_fixed_quantize of it), or y_codes uint8 (out_q on, bits 2..8) with *clamped (may be NULL)
+ * zeroed on the stream first by a one-thread kernel and each clamped element counted once. With
+ * L = 0 every form has admmq_packed_igemm's bits on the same arguments (but for the sign of a zero
+ * without a bias). A column's bits depend on that column, K, r, the quantizers and the plans only -
+ * not on N within a regime, nor on the call.
+ * Forward bound against y64, the float64 value on the factors as rounded to T, with eps = 2^-23,
+ * gamma = (1 + eps)^(K + r + 4) - 1 and B = |L_T| (|Rt_T| (g ux + |mn_x|)):
+ *   |y - y64| <= gamma B + u (1 + gamma) B + eps |y64|
+ * Launches: k_ilr_down (U's nsd float32 images, rows padded to rp = 32 ceil(r / 32) floats with
+ * exact zeros; no reduce launch, the consumer adds them), k_packed_ilrgemm (the int8 K loop, then
+ * the tail in the same LDS) and, in the parallel regime (few output tiles: int32 piece images, and
+ * one more workgroup a tile that runs the tail alone into a float32 image of q),
+ * k_packed_ilrreduce. No atomics on outputs, no workgroup waits for another, nothing past the
+ * code stream's last byte is read, no memset.
+ * Refusals, all before any launch, each with its own admmq_last_error text: admmq_packed_igemm's
+ * (ADMMQ_ERR_SCHEME for tensor_minmax; ADMMQ_ERR_ARG for an affine record outside int8, K > 65536,
+ * activation bits outside 2..8, both or neither of y / y_codes, NULL codes / meta / x / x_q /
+ * rowsums, sizes, misaligned codes (16 bytes) / y / bias / rowsums / clamped (4 bytes)),
+ * admmq_packed_hlrgemm's (NULL L / Rt, r outside 1..256, L / Rt not aligned to their element, the
+ * workspace NULL or short: ADMMQ_ERR_WORKSPACE - U always lives there), and: a t_dtype that is not
+ * a half type, an f_dtype other than ADMMQ_DT_F32 or t_dtype, a NULL (or misaligned) rho, a
+ * workspace that is not 16-byte aligned.
+ * admmq_packed_ilrgemm_workspace_size is a function of its arguments only: 0 for arguments out of
+ * range, else, in this order, 4 np N M bytes of int32 images and 4 N M of q's image in the parallel
+ * regime, rounded up to 16 bytes, then 4 nsd N rp bytes of U. admmq_packed_ilrgemm_plan writes
+ * out = (np, parallel, nsd, launches), launches = 2 or 3 (the reduce), not counting the counter's
+ * reset - a pure function; ADMMQ_ERR_ARG (and nothing written) for arguments out of range.
+ * admmq_packed_lowrank_factorsums: ADMMQ_ERR_ARG for NULL Rt / rho, the dtype pair, r outside
+ * 1..256, K outside 1..65536, misaligned Rt / rho. No entry point allocates or synchronises. */
+int32_t admmq_packed_lowrank_factorsums(const void* Rt, int32_t f_dtype, int32_t t_dtype, int32_t r, int64_t K, float* rho,
+                                        void* stream);
+size_t admmq_packed_ilrgemm_workspace_size(int64_t M, int64_t K, int64_t N, int32_t r);
+int32_t admmq_packed_ilrgemm_plan(int64_t M, int64_t K, int64_t N, int32_t r, int32_t out[4]);
+int32_t admmq_packed_ilrgemm(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const void* L,
+                             const void* Rt, int32_t f_dtype, int32_t t_dtype, int32_t r, const float* rho,
+                             const uint8_t* x, const admmq_actq* x_q, const int32_t* rowsums, int64_t N, const float* bias,
+                             float* y, uint8_t* y_codes, const admmq_actq* out_q, int32_t* clamped, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast

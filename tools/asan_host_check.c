@@ -457,6 +457,61 @@ int main(void) {
       fails += HL(c, &qm, 8, 8, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, (void*)0x100004, 1 << 20) != ADMMQ_ERR_ARG;
       fails += HL(c, &qx, 8, 134, lp, rp, F32, 8, hx, BF, 4, NULL, hy, BF, ws, 4 * (4 * 4 * 8 + 3 * 4 + 3 * 4 * 32) - 1) != ADMMQ_ERR_WORKSPACE;
 #undef HL
+      /* the integer quant + low-rank GEMM: the size and plan queries over random and named shapes (pure: asked
+       * twice; the size is the one the plan spells), and the refusals it adds, before any launch */
+      for (int t = 0; t < 400; ++t) {
+        const int64_t M = rnd(1, t % 3 ? 600 : 7000), K = rnd(1, t % 3 ? 600 : 40000), N = rnd(1, t % 3 ? 600 : 5000);
+        const int32_t r = rnd(1, 256);
+        const size_t rpad = 32 * (((size_t)r + 31) / 32);
+        int32_t pl[4] = {0, 0, 0, 0};
+        const size_t w = admmq_packed_ilrgemm_workspace_size(M, K, N, r);
+        fails += admmq_packed_ilrgemm_plan(M, K, N, r, pl) != ADMMQ_OK || pl[3] != (pl[1] ? 3 : 2);
+        fails += pl[0] < 1 || pl[0] > 32 || pl[2] < 1 || pl[2] > 8 || (pl[1] != 0) != (admmq_packed_igemm_workspace_size(M, K, N, 1) > 0);
+        fails += w != admmq_packed_ilrgemm_workspace_size(M, K, N, r);
+        const size_t img = pl[1] ? (size_t)4 * (pl[0] + 1) * N * M : 0;
+        fails += w != ((img + 15) & ~(size_t)15) + (size_t)4 * pl[2] * N * rpad;
+      }
+      {
+        int32_t pl[4] = {7, 7, 7, 7};
+        fails += admmq_packed_ilrgemm_plan(134, 134, 70, 24, pl) != ADMMQ_OK || pl[0] != 3 || pl[1] != 1 || pl[2] != 3 || pl[3] != 3;
+        fails += admmq_packed_ilrgemm_plan(1024, 65, 1024, 9, pl) != ADMMQ_OK || pl[0] != 2 || pl[1] != 0 || pl[2] != 2 || pl[3] != 2;
+        fails += admmq_packed_ilrgemm_plan(8, 8, 4, 8, NULL) != ADMMQ_ERR_ARG || admmq_packed_ilrgemm_plan(8, 65537, 4, 8, pl) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_ilrgemm_plan(8, 8, 4, 0, pl) != ADMMQ_ERR_ARG || admmq_packed_ilrgemm_plan(8, 8, 4, 257, pl) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_ilrgemm_plan(8, 8, 0, 8, pl) != ADMMQ_ERR_ARG || pl[0] != 2;
+      }
+      fails += admmq_packed_ilrgemm_workspace_size(8, 8, 4, 8) != 4 * 4 * 32;
+      fails += admmq_packed_ilrgemm_workspace_size(8, 8, 0, 8) != 0 || admmq_packed_ilrgemm_workspace_size(8, 8, 4, 0) != 0;
+      fails += admmq_packed_ilrgemm_workspace_size(8, 8, 4, 257) != 0 || admmq_packed_ilrgemm_workspace_size(8, 65537, 4, 8) != 0;
+      {
+        const admmq_actq xq8 = {8, 1, -1.0f, 2.0f};
+        const uint8_t* ux = (const uint8_t*)0x10001;
+        const int32_t* rs = (const int32_t*)0x70000;
+        const float* rho = (const float*)0x60000;
+        float* fy = (float*)0x20000;
+#define IL(ll, rr, fd, td, r, hh, wsp, wsb) \
+  admmq_packed_ilrgemm(c, &qm, 8, 8, ll, rr, fd, td, r, hh, ux, &xq8, rs, 4, NULL, fy, NULL, NULL, NULL, wsp, wsb, NULL)
+        fails += IL(lp, rp, F32, F32, 8, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;   /* t_dtype not a half type */
+        fails += IL(lp, rp, F32, 3, 8, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(lp, rp, HF, BF, 8, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;     /* f_dtype neither float32 nor t_dtype */
+        fails += IL(lp, rp, F32, BF, 8, NULL, ws, 1 << 20) != ADMMQ_ERR_ARG;   /* NULL rho */
+        fails += IL(lp, rp, F32, BF, 8, (const float*)0x60002, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(NULL, rp, F32, BF, 8, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(lp, rp, F32, BF, 0, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(lp, rp, F32, BF, 257, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(lp, (const void*)0x50001, BF, BF, 8, rho, ws, 1 << 20) != ADMMQ_ERR_ARG;
+        fails += IL(lp, rp, F32, BF, 8, rho, (void*)0x100004, 1 << 20) != ADMMQ_ERR_ARG;   /* workspace not 16-byte aligned */
+        fails += IL(lp, rp, F32, BF, 8, rho, ws, 4 * 4 * 32 - 1) != ADMMQ_ERR_WORKSPACE;
+        fails += IL(lp, rp, F32, BF, 8, rho, NULL, 0) != ADMMQ_ERR_WORKSPACE;
+#undef IL
+        fails += admmq_packed_ilrgemm(c, &qx, 8, 8, lp, rp, F32, BF, 8, rho, ux, &xq8, rs, 4, NULL, fy, NULL, NULL, NULL, ws, 1 << 20,
+                                      NULL) != ADMMQ_ERR_SCHEME;
+        fails += admmq_packed_lowrank_factorsums(rp, F32, F32, 8, 64, (float*)0x60000, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lowrank_factorsums(rp, HF, BF, 8, 64, (float*)0x60000, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lowrank_factorsums(NULL, F32, BF, 8, 64, (float*)0x60000, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lowrank_factorsums(rp, F32, BF, 8, 64, NULL, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lowrank_factorsums(rp, F32, BF, 257, 64, (float*)0x60000, NULL) != ADMMQ_ERR_ARG;
+        fails += admmq_packed_lowrank_factorsums(rp, F32, BF, 8, 65537, (float*)0x60000, NULL) != ADMMQ_ERR_ARG;
+      }
     }
     /* the fused depthwise + 1x1 stage: the same workspace as the GEMM on (M, K, Ho Wo, nb),
      * and every refusal before any launch */
