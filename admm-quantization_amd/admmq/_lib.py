@@ -175,6 +175,9 @@ def load() -> ctypes.CDLL:
         "admmq_packed_ilrgemm_workspace_size": (S, [I64, I64, I64, I32]),
         "admmq_packed_ilrgemm_plan": (I32, [I64, I64, I64, I32, P]),
         "admmq_packed_ilrgemm": (I32, [P, P, I64, I64, P, P, I32, I32, I32, P, P, P, P, I64, P, P, P, P, P, P, S, P]),
+        "admmq_packed_ilrgemv_workspace_size": (S, [P, I64, I64, I64, I32]),
+        "admmq_packed_ilrgemv_plan": (I32, [P, I64, I64, I32, P]),
+        "admmq_packed_ilrgemv": (I32, [P, P, I64, I64, P, P, I32, I32, I32, P, P, P, P, I64, P, P, P, P, P, P, S, P]),
         "admmq_packed_taps_i8_bytes": (S, [I32, I64]),
         "admmq_packed_taps_i8": (I32, [P, P, I32, I64, P, P]),
         "admmq_packed_idwgemm_workspace_size": (S, [I64, I64, I64, I64, I32]),

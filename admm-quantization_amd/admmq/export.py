@@ -237,7 +237,10 @@ class IntegerPackedLowRank(nn.Module):
     MFMA in ``tail_dtype``; the output is float32. The child ``linear`` is the float layer's ``PackedLowRankLinear``
     (codes, factors, bias); ``in_act``, the tail type, the weight's integer row sums and the factor sums travel in
     this module's extra state, in ``IntegerPackedPair``'s manner. ``last_clamped``: the device counter of the last
-    forward's input encoding; no forward reads it."""
+    forward's input encoding; no forward reads it. ``skinny`` (an attribute, default ``False``, not part of the extra
+    state): send an input of at most ``GEMV_N_MAX`` rows to ``packed_ilrgemv`` (the decode kernels, DESIGN.md 2.38:
+    other bits than the default route's wherever ``L != 0``)."""
+    skinny = False
 
     def __init__(self, linear: "PackedLowRankLinear", in_act, tail_dtype=torch.bfloat16):
         super().__init__()
@@ -287,11 +290,12 @@ class IntegerPackedLowRank(nn.Module):
         xq = act_encode(x, _lib.ActQ(self._in_act[0], 1, self._in_act[1], self._in_act[2]), check=False)
         self.last_clamped = xq.clamped
         return _ilrgemm(st.codes, st._meta, st.out_features, st.in_features, st.L, st.Rt, self._factorsums(), xq.codes,
-                        self._in_act, self._rowsums(), st.bias, (0, 0.0, 0.0), False, self.tail_dtype)
+                        self._in_act, self._rowsums(), st.bias, (0, 0.0, 0.0), False, self.tail_dtype,
+                        self.skinny and skinny_rows(xq.codes, st.in_features))
 
     def extra_repr(self):
         return (f"integer, in_act=(bits={self._in_act[0]}, mn={self._in_act[1]}, rng={self._in_act[2]}), "
-                f"tail_dtype={self.tail_dtype}")
+                f"tail_dtype={self.tail_dtype}" + (", skinny=True" if self.skinny else ""))
 
 
 def build_qlr_layer(p: PackedLowRank, bias: Optional[torch.Tensor] = None, integer: bool = False, in_act=None,

@@ -51,7 +51,7 @@ __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed"
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_igemv", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
            "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear",
-           "packed_lowrank_factorsums", "packed_ilrgemm", "packed_lowrank_linear_int", "save_packed_lowrank", "load_packed_lowrank"]
+           "packed_lowrank_factorsums", "packed_ilrgemm", "packed_ilrgemv", "packed_lowrank_linear_int", "save_packed_lowrank", "load_packed_lowrank"]
 
 _NAMES = {v: k for k, v in _lib.SCHEMES.items()}
 FORMAT = "admmq.packed.v1"
@@ -1389,42 +1389,65 @@ def packed_ilrgemm(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int
     return _ilrgemm(codes, meta_words, int(M), int(K), L, Rt, rho, xq.codes, x3, rowsums, bias, o3, bool(out_codes), tail_dtype)
 
 
-def _ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype):
-    """The call behind ``packed_ilrgemm`` on checked quantizers ``x3`` / ``o3 = (bits, mn, rng)``."""
-    tdt = _tail_code(tail_dtype, "packed_ilrgemm")
+def packed_ilrgemv(codes: torch.Tensor, meta_words: torch.Tensor, M: int, K: int, L: torch.Tensor, Rt: torch.Tensor,
+                   rho: torch.Tensor, xq: QuantizedActivation, rowsums: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                   act=None, out_codes: bool = False, tail_dtype=torch.bfloat16):
+    """The skinny quant + low-rank product on activation codes for decode shapes (``admmq_packed_ilrgemv``, DESIGN.md
+    2.38): ``packed_ilrgemm``'s parameters and result for ``xq.codes [..., K]`` of at most ``GEMV_N_MAX`` rows. The
+    code product is ``packed_igemv``'s exact integer on the dot4 unit; the rank-``r`` branch is float32 FMA chains on
+    the factors as rounded to ``tail_dtype`` (float32 factors are rounded as they are read, factors stored in
+    ``tail_dtype`` give the same bits), and ``t`` is not rounded to ``tail_dtype`` - so with ``L != 0`` the bits are
+    not ``packed_ilrgemm``'s (both approximate the same value); with ``L = 0`` they are ``packed_igemv``'s and
+    ``packed_igemm``'s. A row's bits never depend on the row count. Inference only."""
+    x3 = _in_triple(xq, "packed_ilrgemv")
+    o3 = _out_triple(act, out_codes, "packed_ilrgemv")
+    return _ilrgemm(codes, meta_words, int(M), int(K), L, Rt, rho, xq.codes, x3, rowsums, bias, o3, bool(out_codes), tail_dtype,
+                    True)
+
+
+def _ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype, skinny=False):
+    """The call behind ``packed_ilrgemm`` and, with ``skinny``, ``packed_ilrgemv`` on checked quantizers ``x3`` /
+    ``o3 = (bits, mn, rng)``."""
+    who = "packed_ilrgemv" if skinny else "packed_ilrgemm"
+    tdt = _tail_code(tail_dtype, who)
     if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8:
-        raise TypeError("packed_ilrgemm: xq.codes must be a uint8 tensor")
-    _require_gpu("packed_ilrgemm", "codes, factors and activations", x, codes, L, Rt, rho)
-    _inference_only("packed_ilrgemm", L, "L")
-    _inference_only("packed_ilrgemm", Rt, "Rt")
+        raise TypeError(f"{who}: xq.codes must be a uint8 tensor")
+    _require_gpu(who, "codes, factors and activations", x, codes, L, Rt, rho)
+    _inference_only(who, L, "L")
+    _inference_only(who, Rt, "Rt")
     if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_igemm
-        return _opaque_ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype)
+        return _opaque_ilrgemm(codes, meta_words, M, K, L, Rt, rho, x, x3, rowsums, bias, o3, out_codes, tail_dtype, skinny)
     L, Rt = L.detach(), Rt.detach()
-    r = _tail_factors("packed_ilrgemm", L, Rt, M, K, tail_dtype)
-    oshape, _, N, xc = _gemm_geometry("packed_ilrgemm", x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    r = _tail_factors(who, L, Rt, M, K, tail_dtype)
+    oshape, _, N, xc = _gemm_geometry(who, x, M, K, 1)   # (before the dispatch: one refusal on both routes)
+    if skinny and N > GEMV_N_MAX:
+        raise ValueError(f"{who}: xq.codes must hold 1..{GEMV_N_MAX} rows, got {N}")
     if bias is not None:
         bias = bias.detach()
-    if _lib.use_ops():   # torch.ops.admmq.packed_ilrgemm (csrc/torch_ops.cpp) -> admmq_packed_ilrgemm
-        y, clamped = _lib.ops().packed_ilrgemm(codes, meta_words, M, K, L, Rt, rho, tdt, xc, x3[0], x3[1], x3[2], rowsums, bias,
+    if _lib.use_ops():   # torch.ops.admmq.packed_ilrgemm / packed_ilrgemv (csrc/torch_ops.cpp) -> the C call of that name
+        y, clamped = getattr(_lib.ops(), who)(codes, meta_words, M, K, L, Rt, rho, tdt, xc, x3[0], x3[1], x3[2], rowsums, bias,
                                                o3[0], o3[1], o3[2], out_codes)
     else:
         lib = _lib.load()
-        (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg("packed_ilrgemm", bias, M)
+        (cc, meta), bc = _weight_arg(codes, meta_words), _bias_arg(who, bias, M)
         if rowsums.dtype != torch.int32 or tuple(rowsums.shape) != (M,):
-            raise ValueError(f"packed_ilrgemm: rowsums must be int32 [{M}]")
+            raise ValueError(f"{who}: rowsums must be int32 [{M}]")
         if rho.dtype != torch.float32 or tuple(rho.shape) != (r,):
-            raise ValueError(f"packed_ilrgemm: rho must be float32 [{r}]")
+            raise ValueError(f"{who}: rho must be float32 [{r}]")
         Lc, Rc = L.contiguous(), Rt.contiguous()
         xr, oq = _actq(x3), _actq(o3)
         y = torch.empty(oshape, dtype=torch.uint8 if out_codes else torch.float32, device=x.device)
         clamped = torch.empty(1 if out_codes else 0, dtype=torch.int32, device=x.device)
-        ws = _lib.workspace(lib.admmq_packed_ilrgemm_workspace_size(M, K, N, r), x.device)
-        rc = lib.admmq_packed_ilrgemm(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), GEMV_DTYPES[L.dtype],
+        if skinny:
+            ws = _lib.workspace(lib.admmq_packed_ilrgemv_workspace_size(ctypes.byref(meta), M, K, N, r), x.device)
+        else:
+            ws = _lib.workspace(lib.admmq_packed_ilrgemm_workspace_size(M, K, N, r), x.device)
+        rc = getattr(lib, "admmq_" + who)(_lib.ptr(cc), ctypes.byref(meta), M, K, _lib.ptr(Lc), _lib.ptr(Rc), GEMV_DTYPES[L.dtype],
                                       tdt, r, _lib.ptr(rho.contiguous()), _lib.ptr(xc), ctypes.byref(xr),
                                       _lib.ptr(rowsums.contiguous()), N, _lib.ptr(bc), _lib.ptr(None if out_codes else y),
                                       _lib.ptr(y if out_codes else None), _byref(oq), _lib.ptr(clamped if out_codes else None),
                                       _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
-        _lib.check(rc, "packed_ilrgemm")
+        _lib.check(rc, who)
     if out_codes:
         return QuantizedActivation(y, o3[0], o3[1], o3[2], clamped)
     return y
@@ -1434,11 +1457,14 @@ _opaque_ilrgemm = torch.compiler.disable(_ilrgemm)
 
 
 def packed_lowrank_linear_int(xq: QuantizedActivation, p: "PackedLowRank", bias: Optional[torch.Tensor] = None, act=None,
-                              out_codes: bool = False, tail_dtype=torch.bfloat16):
+                              out_codes: bool = False, tail_dtype=torch.bfloat16, skinny: bool = False):
     """``packed_lowrank_linear`` on activation codes: ``xq.codes [..., K] -> [..., M]`` through ``packed_ilrgemm``
     (int8 MFMA for ``W_q``, 16-bit MFMA in ``tail_dtype`` for ``L Rt``) - a float32 tensor, or with
     ``out_codes=True`` (which needs ``act``) a ``QuantizedActivation``. The weight's row sums and the factor sums are
-    computed on the first call and kept on ``p``. Opt-in: nothing routes here by itself. Inference only."""
+    computed on the first call and kept on ``p``. ``skinny=True`` sends codes of at most ``GEMV_N_MAX`` rows to
+    ``packed_ilrgemv`` (the decode kernels, DESIGN.md 2.38: ``t`` is not rounded to ``tail_dtype``, so other bits than
+    the default route's wherever ``L != 0``); everything else goes down the default route. Opt-in: nothing routes
+    here by itself. Inference only."""
     if not isinstance(p, PackedLowRank):
         raise TypeError("expected a PackedLowRank")
     e = _int_plan(p.q, False, "packed_lowrank_linear_int")
@@ -1448,7 +1474,8 @@ def packed_lowrank_linear_int(xq: QuantizedActivation, p: "PackedLowRank", bias:
     _tail_factors("packed_lowrank_linear_int", p.L, p.Rt, e[0], e[1], tail_dtype)
     rs = e[2] if e[2] is not None else packed_rowsums(p.q, False)
     rho = packed_lowrank_factorsums(p, tail_dtype)
-    return _ilrgemm(p.q.codes, _meta_words(p.q), e[0], e[1], p.L, p.Rt, rho, xq.codes, x3, rs, bias, o3, bool(out_codes), tail_dtype)
+    sk = bool(skinny) and skinny_rows(xq.codes, e[1])
+    return _ilrgemm(p.q.codes, _meta_words(p.q), e[0], e[1], p.L, p.Rt, rho, xq.codes, x3, rs, bias, o3, bool(out_codes), tail_dtype, sk)
 
 
 def save_packed_lowrank(path: str, p: "PackedLowRank") -> None:

@@ -18,6 +18,7 @@
 //   admmq::packed_hdwgemm          that stage on bfloat16 / float16 activations
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
 //   admmq::packed_lowrank_factorsums, packed_ilrgemm   the integer quant + low-rank GEMM on activation codes
+//   admmq::packed_ilrgemv   its skinny form for 1..8 rows
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
 //   admmq::packed_igemv            the skinny integer GEMV for 1..8 rows of activation codes
 //   admmq::packed_taps_i8, packed_idwgemm   int8 tap image and the integer fused depthwise + 1x1 stage
@@ -1052,73 +1053,96 @@ at::Tensor packed_lowrank_factorsums_meta(const at::Tensor& Rt, int64_t tail_dty
   return at::empty({factorsums_rank(Rt, tail_dtype)}, Rt.options().dtype(at::kFloat));
 }
 
-std::vector<int64_t> packed_ilrgemm_shape(const at::Tensor& x, const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& rho,
-                                          int64_t tail_dtype, int64_t M, int64_t K) {
-  TORCH_CHECK(x.scalar_type() == at::kByte, "admmq: packed_ilrgemm: x must be a uint8 code tensor, got ", x.scalar_type());
-  TORCH_CHECK(M > 0 && K > 0, "admmq: packed_ilrgemm: M and K must be positive");
+// who: packed_ilrgemm, or packed_ilrgemv (the skinny route, DESIGN.md 2.38: 1..8 rows)
+std::vector<int64_t> packed_ilrgemm_shape(const char* who, const at::Tensor& x, const at::Tensor& L, const at::Tensor& Rt,
+                                          const at::Tensor& rho, int64_t tail_dtype, int64_t M, int64_t K, bool skinny) {
+  TORCH_CHECK(x.scalar_type() == at::kByte, "admmq: ", who, ": x must be a uint8 code tensor, got ", x.scalar_type());
+  TORCH_CHECK(M > 0 && K > 0, "admmq: ", who, ": M and K must be positive");
   TORCH_CHECK(L.dim() == 2 && Rt.dim() == 2 && L.size(0) == M && Rt.size(1) == K && L.size(1) == Rt.size(0),
-              "admmq: packed_ilrgemm: L must be [", M, ", r] and Rt [r, ", K, "], got ", L.sizes(), " and ", Rt.sizes());
-  TORCH_CHECK(L.size(1) >= 1 && L.size(1) <= 256, "admmq: packed_ilrgemm: rank r must be 1..256, got ", L.size(1));
-  check_tail_factor(L, tail_dtype, "packed_ilrgemm");
-  TORCH_CHECK(L.scalar_type() == Rt.scalar_type(), "admmq: packed_ilrgemm: L and Rt must be of one dtype, got ", L.scalar_type(),
+              "admmq: ", who, ": L must be [", M, ", r] and Rt [r, ", K, "], got ", L.sizes(), " and ", Rt.sizes());
+  TORCH_CHECK(L.size(1) >= 1 && L.size(1) <= 256, "admmq: ", who, ": rank r must be 1..256, got ", L.size(1));
+  check_tail_factor(L, tail_dtype, who);
+  TORCH_CHECK(L.scalar_type() == Rt.scalar_type(), "admmq: ", who, ": L and Rt must be of one dtype, got ", L.scalar_type(),
               " and ", Rt.scalar_type());
   TORCH_CHECK(rho.scalar_type() == at::kFloat && rho.dim() == 1 && rho.size(0) == L.size(1),
-              "admmq: packed_ilrgemm: rho must be float32 [", L.size(1), "] (packed_lowrank_factorsums)");
-  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K && x.numel() > 0, "admmq: packed_ilrgemm: x must be [..., ", K,
+              "admmq: ", who, ": rho must be float32 [", L.size(1), "] (packed_lowrank_factorsums)");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) == K && x.numel() > 0, "admmq: ", who, ": x must be [..., ", K,
               "] with at least one row, got ", x.sizes());
+  TORCH_CHECK(!skinny || x.numel() / K <= ADMMQ_GEMV_N_MAX, "admmq: ", who, ": x must hold 1..", ADMMQ_GEMV_N_MAX, " rows, got ",
+              x.numel() / K);
   std::vector<int64_t> shape(x.sizes().begin(), x.sizes().end());
   shape.back() = M;
   return shape;
 }
 
-std::tuple<at::Tensor, at::Tensor> packed_ilrgemm_cuda(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
-                                                       const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& rho,
-                                                       int64_t tail_dtype, const at::Tensor& x, int64_t x_bits, double x_mn,
-                                                       double x_rng, const at::Tensor& rowsums,
-                                                       const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
-                                                       double out_rng, bool out_codes) {
+// The frame of both routes: the checks, the outputs, the workspace and the one C call
+std::tuple<at::Tensor, at::Tensor> ilr_run(const char* who, bool skinny, const at::Tensor& codes, const at::Tensor& meta_words,
+                                           int64_t M, int64_t K, const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& rho,
+                                           int64_t tail_dtype, const at::Tensor& x, int64_t x_bits, double x_mn, double x_rng,
+                                           const at::Tensor& rowsums, const std::optional<at::Tensor>& bias, int64_t out_bits,
+                                           double out_mn, double out_rng, bool out_codes) {
   TORCH_CHECK(x.is_cuda() && L.is_cuda() && Rt.is_cuda() && rho.is_cuda(),
               "admmq: x, L, Rt and rho must live on a ROCm GPU (the MI355X path has no CPU implementation)");
-  check_inference_only(L.requires_grad() || Rt.requires_grad(), "packed_ilrgemm", "L and Rt");
-  const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, "packed_ilrgemm");
-  const admmq_actq oq = outq_of(out_codes, out_bits, out_mn, out_rng, "packed_ilrgemm");
+  check_inference_only(L.requires_grad() || Rt.requires_grad(), who, "L and Rt");
+  const admmq_actq xq = codeq_of(x_bits, x_mn, x_rng, who);
+  const admmq_actq oq = outq_of(out_codes, out_bits, out_mn, out_rng, who);
   admmq_qmeta meta;
-  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, "packed_ilrgemm", meta);
+  const at::Tensor cc = int_weight_of(codes, meta_words, M, K, who, meta);
   check_same_device(codes, x, "codes");
   check_same_device(L, x, "L");
   check_same_device(Rt, x, "Rt");
   check_same_device(rho, x, "rho");
-  check_rowsums(rowsums, x, M, "packed_ilrgemm");
-  const std::vector<int64_t> oshape = packed_ilrgemm_shape(x, L, Rt, rho, tail_dtype, M, K);
+  check_rowsums(rowsums, x, M, who);
+  const std::vector<int64_t> oshape = packed_ilrgemm_shape(who, x, L, Rt, rho, tail_dtype, M, K, skinny);
   const c10::DeviceGuard guard(x.device());
   const at::Tensor xc = x.contiguous(), Lc = L.contiguous(), Rc = Rt.contiguous(), hc = rho.contiguous();
   const at::Tensor rc = rowsums.contiguous();
-  const at::Tensor bc = bias_of(bias, x, M, "packed_ilrgemm", true);
+  const at::Tensor bc = bias_of(bias, x, M, who, true);
   const int64_t N = xc.numel() / K;
   const int32_t r = static_cast<int32_t>(Lc.size(1));
   at::Tensor y = at::empty(oshape, xc.options().dtype(out_codes ? at::kByte : at::kFloat));
   at::Tensor clamped = at::empty({out_codes ? 1 : 0}, xc.options().dtype(at::kInt));
-  at::Tensor ws = workspace(admmq_packed_ilrgemm_workspace_size(M, K, N, r), xc);
-  check_rc(admmq_packed_ilrgemm(cc.data_ptr<uint8_t>(), &meta, M, K, Lc.data_ptr(), Rc.data_ptr(), dt_of(Lc),
-                                static_cast<int32_t>(tail_dtype), r, hc.data_ptr<float>(), xc.data_ptr<uint8_t>(), &xq,
-                                rc.data_ptr<int32_t>(), N, f32_or_null(bc), out_codes ? nullptr : y.data_ptr<float>(),
-                                out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq, out_codes ? clamped.data_ptr<int32_t>() : nullptr,
-                                ws.data_ptr(), static_cast<size_t>(ws.numel()), stream_of(xc)),
-           "packed_ilrgemm");
+  at::Tensor ws = workspace(skinny ? admmq_packed_ilrgemv_workspace_size(&meta, M, K, N, r)
+                                   : admmq_packed_ilrgemm_workspace_size(M, K, N, r), xc);
+  check_rc((skinny ? admmq_packed_ilrgemv : admmq_packed_ilrgemm)(
+               cc.data_ptr<uint8_t>(), &meta, M, K, Lc.data_ptr(), Rc.data_ptr(), dt_of(Lc), static_cast<int32_t>(tail_dtype), r,
+               hc.data_ptr<float>(), xc.data_ptr<uint8_t>(), &xq, rc.data_ptr<int32_t>(), N, f32_or_null(bc),
+               out_codes ? nullptr : y.data_ptr<float>(), out_codes ? y.data_ptr<uint8_t>() : nullptr, &oq,
+               out_codes ? clamped.data_ptr<int32_t>() : nullptr, ws.data_ptr(), static_cast<size_t>(ws.numel()), stream_of(xc)),
+           who);
   return {y, clamped};
 }
 
-std::tuple<at::Tensor, at::Tensor> packed_ilrgemm_meta(const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K,
-                                                       const at::Tensor& L, const at::Tensor& Rt, const at::Tensor& rho,
-                                                       int64_t tail_dtype, const at::Tensor& x, int64_t x_bits, double x_mn,
-                                                       double x_rng, const at::Tensor& rowsums,
-                                                       const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn,
-                                                       double out_rng, bool out_codes) {
-  (void)codeq_of(x_bits, x_mn, x_rng, "packed_ilrgemm");
-  (void)outq_of(out_codes, out_bits, out_mn, out_rng, "packed_ilrgemm");
-  return {at::empty(packed_ilrgemm_shape(x, L, Rt, rho, tail_dtype, M, K), x.options().dtype(out_codes ? at::kByte : at::kFloat)),
+std::tuple<at::Tensor, at::Tensor> ilr_meta(const char* who, bool skinny, const at::Tensor& L, const at::Tensor& Rt,
+                                            const at::Tensor& rho, int64_t tail_dtype, const at::Tensor& x, int64_t M, int64_t K,
+                                            int64_t x_bits, double x_mn, double x_rng, int64_t out_bits, double out_mn,
+                                            double out_rng, bool out_codes) {
+  (void)codeq_of(x_bits, x_mn, x_rng, who);
+  (void)outq_of(out_codes, out_bits, out_mn, out_rng, who);
+  return {at::empty(packed_ilrgemm_shape(who, x, L, Rt, rho, tail_dtype, M, K, skinny),
+                    x.options().dtype(out_codes ? at::kByte : at::kFloat)),
           at::empty({out_codes ? 1 : 0}, x.options().dtype(at::kInt))};
 }
+
+#define ADMMQ_ILR_OP(NAME, SKINNY)                                                                                              \
+  std::tuple<at::Tensor, at::Tensor> NAME##_cuda(                                                                              \
+      const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const at::Tensor& L, const at::Tensor& Rt,  \
+      const at::Tensor& rho, int64_t tail_dtype, const at::Tensor& x, int64_t x_bits, double x_mn, double x_rng,               \
+      const at::Tensor& rowsums, const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn, double out_rng,       \
+      bool out_codes) {                                                                                                        \
+    return ilr_run(#NAME, SKINNY, codes, meta_words, M, K, L, Rt, rho, tail_dtype, x, x_bits, x_mn, x_rng, rowsums, bias,       \
+                   out_bits, out_mn, out_rng, out_codes);                                                                      \
+  }                                                                                                                            \
+  std::tuple<at::Tensor, at::Tensor> NAME##_meta(                                                                              \
+      const at::Tensor& codes, const at::Tensor& meta_words, int64_t M, int64_t K, const at::Tensor& L, const at::Tensor& Rt,  \
+      const at::Tensor& rho, int64_t tail_dtype, const at::Tensor& x, int64_t x_bits, double x_mn, double x_rng,               \
+      const at::Tensor& rowsums, const std::optional<at::Tensor>& bias, int64_t out_bits, double out_mn, double out_rng,       \
+      bool out_codes) {                                                                                                        \
+    return ilr_meta(#NAME, SKINNY, L, Rt, rho, tail_dtype, x, M, K, x_bits, x_mn, x_rng, out_bits, out_mn, out_rng, out_codes); \
+  }
+ADMMQ_ILR_OP(packed_ilrgemm, false)
+ADMMQ_ILR_OP(packed_ilrgemv, true)
+#undef ADMMQ_ILR_OP
 
 // --- packed_dwgemm --------------------------------------------------------------------------
 // The depthwise kh x kw stage (taps [kh kw, K]) and the 1x1 stage by the packed [M, K] weight
@@ -1427,6 +1451,9 @@ TORCH_LIBRARY(admmq, m) {
   m.def("packed_ilrgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor rho, int tail_dtype, "
         "Tensor x, int x_bits, float x_mn, float x_rng, Tensor rowsums, Tensor? bias, int out_bits, float out_mn, "
         "float out_rng, bool out_codes) -> (Tensor y, Tensor clamped)");
+  m.def("packed_ilrgemv(Tensor codes, Tensor meta_words, int M, int K, Tensor L, Tensor Rt, Tensor rho, int tail_dtype, "
+        "Tensor x, int x_bits, float x_mn, float x_rng, Tensor rowsums, Tensor? bias, int out_bits, float out_mn, "
+        "float out_rng, bool out_codes) -> (Tensor y, Tensor clamped)");
   m.def("packed_taps_i8(Tensor codes, Tensor meta_words, int ntaps, int K) -> Tensor");
   m.def("packed_idwgemm(Tensor codes, Tensor meta_words, int M, int K, Tensor x, int x_bits, float x_mn, float x_rng, "
         "Tensor taps_i8, float s_c, int kh, int kw, int sh, int sw, int ph, int pw, Tensor rowsums, Tensor? bias, "
@@ -1461,6 +1488,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("packed_igemv", &packed_igemv_cuda);
   m.impl("packed_lowrank_factorsums", &packed_lowrank_factorsums_cuda);
   m.impl("packed_ilrgemm", &packed_ilrgemm_cuda);
+  m.impl("packed_ilrgemv", &packed_ilrgemv_cuda);
   m.impl("packed_taps_i8", &packed_taps_i8_cuda);
   m.impl("packed_idwgemm", &packed_idwgemm_cuda);
   m.impl("quantize_channel", &quantize_channel_cuda);
@@ -1491,6 +1519,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("packed_igemv", &packed_igemv_meta);
   m.impl("packed_lowrank_factorsums", &packed_lowrank_factorsums_meta);
   m.impl("packed_ilrgemm", &packed_ilrgemm_meta);
+  m.impl("packed_ilrgemv", &packed_ilrgemv_meta);
   m.impl("packed_taps_i8", &packed_taps_i8_meta);
   m.impl("packed_idwgemm", &packed_idwgemm_meta);
   m.impl("quantize_channel", &quantize_channel_meta);

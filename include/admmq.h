@@ -754,6 +754,52 @@ int32_t admmq_packed_ilrgemm(const uint8_t* codes, const admmq_qmeta* meta, int6
                              float* y, uint8_t* y_codes, const admmq_actq* out_q, int32_t* clamped, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* Skinny integer quant + low-rank GEMV: admmq_packed_ilrgemm's product for decode
+ * shapes, 1 <= N <= ADMMQ_GEMV_N_MAX rows of activation codes x [N, K] (uint8, any address), W = D,
+ *   y[c, m] = x^ (D + L Rt)^T (+ bias),  x^ = g ux + mn_x,  g = rng_x / n_x,
+ * on the dot4 unit and float32 FMAs: no MFMA. The argument list, the weight schemes (bits 1..8,
+ * tensor_minmax refused, affine outside int8 refused, K <= 65536), the factor types (L / Rt both
+ * float32 or both of the tail type T = t_dtype), rho (admmq_packed_lowrank_factorsums), the three
+ * output forms and the clamp counter are admmq_packed_ilrgemm's. The value:
+ *   S = U - (q + zp) Sx in int64: admmq_packed_igemv's exact integer (the same v_dot4_u32_u8 sums);
+ *   U32[c][j] = sum_k Rt_T[j, k] float(ux[c, k]) in float32, one fmaf per term. Rt_T / L_T are the
+ *     factors as rounded to T: factors stored in T are widened exactly, float32 factors are rounded
+ *     to T (nearest even, the bits of tensor.to(T)) as they are read - required, since rho is the
+ *     sum of Rt_T and the code part and the affine part of x^ must meet the same matrix. The order
+ *     is a function of (K, r) and the plan, never of N: K is cut into nsd ranges of ksd k (a
+ *     multiple of 256); inside range z lane l of a wave adds k = z ksd + 1024 i + 256 s + 4 l + e
+ *     in increasing (i, s, e) from zero; the 64 lanes meet in the fixed tree of the skinny kernels
+ *     (v += row_shr 1, 2, 4, 8 of v, zeros from outside the 16-lane row; lane 15 holds the row's
+ *     sum) and the four row sums as ((s0 + s1) + s2) + s3;
+ *     the nsd range sums are added in range order;
+ *   t32 = float(gd double(U32) + double(mn_x) double(rho[j])): admmq_packed_ilrgemm's formula, but
+ *     t is NOT rounded to T (there is no matrix unit to feed). So with L != 0 the bits differ
+ *     from admmq_packed_ilrgemm's; both approximate the same exact value;
+ *   q = sum_j L_T[m, j] t32[c, j] in float32, one fmaf per term from zero: lane l of the 32 lanes of
+ *     a row adds j = l, l + 32, ... in increasing j; the 32 lanes meet in the same tree inside each
+ *     16-lane row and the two row sums as s0 + s1;
+ *   y = float(double(scale) (gd double(S) + double(mn_x) double(A[m])) + double(q) + double(bias)),
+ *     every double operation rounded on its own, then the output form of admmq_packed_igemm.
+ * With L = 0, q is an exact +0 and every output form has admmq_packed_igemv's bits (and therefore
+ * admmq_packed_igemm's) in both plans. No output's bits depend on N or on its column.
+ * Launches: k_ilr_down_gemv, k_packed_ilrgemv and, where the code sum is split over K (ns > 1),
+ * k_packed_ilrgemv_reduce; a codes output adds the one-thread kernel that zeroes the counter. No
+ * atomics on outputs, no workgroup waits for another, no entry point allocates or synchronises.
+ * admmq_packed_ilrgemv_workspace_size: 0 for arguments out of range, else 4 nsd N r bytes of U32's
+ * images, plus 4 ns N (M + 1) + 4 N M where ns > 1 (the uint32 images, Sx, q's image).
+ * admmq_packed_ilrgemv_plan writes out = (ks, ns, nsd, launches), launches = 2 or 3, a pure function
+ * of (meta->bits, M, K, r); ADMMQ_ERR_ARG (nothing written) for arguments out of range.
+ * Refusals, each before any launch and with its own admmq_last_error text: admmq_packed_ilrgemm's,
+ * plus N outside 1..8 (ADMMQ_ERR_ARG); the workspace NULL or short: ADMMQ_ERR_WORKSPACE; a
+ * workspace that is not 4-byte aligned: ADMMQ_ERR_ARG. */
+size_t admmq_packed_ilrgemv_workspace_size(const admmq_qmeta* meta, int64_t M, int64_t K, int64_t N, int32_t r);
+int32_t admmq_packed_ilrgemv_plan(const admmq_qmeta* meta, int64_t M, int64_t K, int32_t r, int32_t out[4]);
+int32_t admmq_packed_ilrgemv(const uint8_t* codes, const admmq_qmeta* meta, int64_t M, int64_t K, const void* L,
+                             const void* Rt, int32_t f_dtype, int32_t t_dtype, int32_t r, const float* rho,
+                             const uint8_t* x, const admmq_actq* x_q, const int32_t* rowsums, int64_t N, const float* bias,
+                             float* y, uint8_t* y_codes, const admmq_actq* out_q, int32_t* clamped, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* Per-channel schemes with an explicit dim (source/quantization.py:29-33, 91-106):
  * max / min of every row of unfold(x, dim) (source/utils.py:60-74), then the
  * tensor_symmetric / tensor_affine arithmetic with those shape[dim] statistics broadcast
