@@ -226,6 +226,8 @@ def load() -> ctypes.CDLL:
         "admmq_panel_outer": (I32, [P, P, I64, I64, I64, P, I64, P]),
         "admmq_gram64_workspace_size": (S, [I64, I64, I64]),
         "admmq_gram64": (I32, [P, I64, P, I64, I64, I64, I64, P, P, S, P]),
+        "admmq_cholqr64": (I32, [P, I64, I64, I64, P, ctypes.c_double, P, I64, P, P]),
+        "admmq_panel_reorth64": (I32, [P, I64, I64, I64, P, I64, P, I64, I64, P, I64, P]),
         "admmq_epc_mu": (I32, [P, P, I64, ctypes.c_double, ctypes.c_double, P, P]),
         "admmq_cp_colnorm64": (I32, [P, I64, P, I64, I64, P, P, P]),
         "admmq_solve64_workspace_size": (S, [I64, I64]),

@@ -117,14 +117,30 @@ def _chol_step(Z: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
     return torch.linalg.solve_triangular(L, Z.T, upper=False).T.contiguous()
 
 
-def orthonormalize(Z: torch.Tensor) -> torch.Tensor:
+def orthonormalize(Z: torch.Tensor, fused: bool = False, also: Optional[torch.Tensor] = None) -> torch.Tensor:
     """An orthonormal basis of span(Z) (m x k, float64) by shifted Cholesky QR followed by
     two plain passes (sCholQR3, Fukaya et al. 2020): three k x k Gram products, Cholesky
     factors and triangular solves instead of a Householder QR's O(k) launch-bound reflector
     steps; orthogonal to ~1e-15 for cond(Z) up to ~1e15. The basis differs from the QR's by a
     k x k rotation (the Krylov subspace, hence the projection, does not). No host sync: a
-    failure shows as a non-orthonormal K at the next Rayleigh-Ritz check, which repairs it."""
+    failure shows as a non-orthonormal K at the next Rayleigh-Ritz check, which repairs it.
+
+    ``fused=True`` with k <= ``panel.CHOLQR_K_MAX`` runs each pass as ``panel.gram`` then
+    ``panel.cholqr``: the shift ``11 (m k + k (k + 1)) 2^-53 tr(G)`` is formed
+    in the kernel, passes 2 and 3 write in place, and nothing but this library's kernels is
+    launched. The bits differ from the default route's (another factorisation order). A wider
+    Z takes the default route. ``also`` (fused route only): a float64 m x k view, e.g. a column
+    block of a wider basis, that receives the same Q by a second launch of the last pass."""
     m, k = Z.shape
+    if fused and k <= panel.CHOLQR_K_MAX:
+        Q = panel.cholqr(Z, panel.gram(Z, Z), shift_scale=11.0 * (m * k + k * (k + 1)) * 2.0 ** -53)
+        panel.cholqr(Q, panel.gram(Q, Q), out=Q)
+        G = panel.gram(Q, Q)
+        if also is not None:
+            panel.cholqr(Q, G, out=also)
+        return panel.cholqr(Q, G, out=Q)
+    if also is not None:
+        raise ValueError("admmq.lowrank.orthonormalize: `also` needs the fused route")
     eye = torch.eye(k, dtype=Z.dtype, device=Z.device)
     G = panel.gram(Z, Z)
     shift = 11.0 * (m * k + k * (k + 1)) * 2.0 ** -53 * torch.trace(G)
@@ -152,11 +168,17 @@ class KrylovProjector:
     orthonormalized by Cholesky QR (``orthonormalize``); the re-orthogonalization and the
     small eigenproblem are float64 library calls on panels. Each check also measures
     ||K^T K - I|| (same host sync as the residual) and, past ``ortho_tol``, rebuilds K by a
-    Householder QR and repeats the check."""
+    Householder QR and repeats the check.
+
+    ``fused=True`` (block width <= ``panel.CHOLQR_K_MAX``, else the default route) keeps a
+    block step on this library's kernels alone: ``orthonormalize(fused=True)``,
+    the re-orthogonalization as ``panel.reorth`` in place, and K as one preallocated buffer that a
+    new block is written into, not concatenated. The Rayleigh-Ritz check is the same code."""
 
     def __init__(self, rank: int, block: int = 32, tol: float = 2e-5, check_every: int = 4, max_blocks: int = 64,
-                 seed: int = 0, ortho_tol: float = 1e-9):
+                 seed: int = 0, ortho_tol: float = 1e-9, fused: bool = False):
         self.rank, self.block, self.tol = rank, block, tol
+        self.fused = fused
         self.check_every, self.max_blocks, self.seed = check_every, max_blocks, seed
         self.ortho_tol = ortho_tol
         self.Q: Optional[torch.Tensor] = None
@@ -177,18 +199,31 @@ class KrylovProjector:
         # pairs (a narrower K would index past its eigenpairs and wrap to the top ones)
         k = min(max(self.block, r), m, n)
         Xf = X.float().contiguous()
+        fused = self.fused and k <= panel.CHOLQR_K_MAX
         if self.Q is None or self.Q.shape != (m, k):
             g = torch.Generator().manual_seed(self.seed)
-            self.Q = orthonormalize(panel.xy(Xf, torch.randn(n, k, generator=g, dtype=torch.float64).to(X.device)))
+            self.Q = orthonormalize(panel.xy(Xf, torch.randn(n, k, generator=g, dtype=torch.float64).to(X.device)), fused)
         blocks = [self.Q]
         K = self.Q
         Q = self.Q
+        if fused:   # every column K can reach (the growth rule below), block nb at columns nb k
+            Kbuf = torch.empty(m, max(1, min(self.max_blocks, min(m, n) // k)) * k, dtype=torch.float64, device=X.device)
+            Kbuf[:, :k] = Q
+            K = Kbuf[:, :k]
         res = float("inf")
         nb = 1
         recheck = False
         while True:
             if recheck or nb >= self.max_blocks or K.shape[1] + k > min(m, n):
                 do_check = True
+            elif fused:
+                Z = panel.xy(Xf, panel.xtq(Xf, Q))
+                for _ in range(2):
+                    panel.reorth(K, panel.gram(K, Z), Z, out=Z)
+                Q = orthonormalize(Z, True, also=Kbuf[:, nb * k:(nb + 1) * k])
+                nb += 1
+                K = Kbuf[:, :nb * k]
+                do_check = nb % self.check_every == 0
             else:
                 Z = panel.xy(Xf, panel.xtq(Xf, Q))             # X (X^T Q)
                 for _ in range(2):   # full re-orthogonalization against every block so far
@@ -215,11 +250,14 @@ class KrylovProjector:
                 K = torch.linalg.qr(K)[0]
                 blocks = [K]
                 Q = K[:, -k:]
+                if fused:
+                    Kbuf[:, :K.shape[1]] = K
+                    K, Q = Kbuf[:, :K.shape[1]], Q.contiguous()
                 self.repairs += 1
                 recheck = True
                 continue
             if res <= self.tol or nb >= self.max_blocks or K.shape[1] + k > min(m, n):
-                self.Q = orthonormalize(K @ Ub[:, :k])   # warm start: the leading Ritz vectors
+                self.Q = orthonormalize(K @ Ub[:, :k], fused)   # warm start: the leading Ritz vectors
                 self.blocks.append(nb)
                 self.residuals.append(res)
                 self._last = (U, S[:r], V.T)
@@ -301,7 +339,9 @@ def factorize_lowrank(W: torch.Tensor, bits: int, rank: int, qscheme: str = "ten
     device block-Krylov projector on the hand-written fp64-MFMA panel kernels (DESIGN.md
     §2.18; pinned to the reference's own trajectory band F10); ``"svd"`` is the exact
     library SVD truncation (``project_rank``, the reference's arithmetic) for callers that
-    want it explicitly; ``"subspace"`` the cheaper subspace iteration (comparison only)."""
+    want it explicitly; ``"subspace"`` the cheaper subspace iteration (comparison only);
+    ``"krylov-fused"`` is ``"krylov"`` with every launch of a Krylov block step on this library's
+    kernels (``KrylovProjector(fused=True)``; same subspace, other bits)."""
     if return_packed:   # (quantize_packed's refusals, before any device work)
         from . import packed as _packed
         _packed._validate(bits, qscheme)
@@ -313,7 +353,9 @@ def factorize_lowrank(W: torch.Tensor, bits: int, rank: int, qscheme: str = "ten
     quant = partial(quantize_tensor, qscheme=qscheme, bits=bits)
     kept = {} if return_packed else None
     proj = (SvdProjector(rank) if projection == "svd" else
-            KrylovProjector(rank, seed=seed) if projection == "krylov" else SubspaceProjector(rank, seed=seed))
+            KrylovProjector(rank, seed=seed) if projection == "krylov" else
+            KrylovProjector(rank, seed=seed, fused=True) if projection == "krylov-fused" else
+            SubspaceProjector(rank, seed=seed))
     W_q = torch.randn(*W.shape, generator=g).to(dev)
     U_q = torch.zeros_like(W_q)
     W_r = proj(torch.randn(*W.shape, generator=g).to(dev))
@@ -366,9 +408,10 @@ def main(argv=None):
     ap.add_argument("--qscheme", type=str, default="tensor_minmax")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--weights", type=str, default=None)
-    ap.add_argument("--projection", choices=["svd", "krylov", "subspace"], default="krylov",
-                    help="rank projection: device block-Krylov on the panel kernels (default) or the exact library "
-                         "SVD truncation of the reference (svd)")
+    ap.add_argument("--projection", choices=["svd", "krylov", "krylov-fused", "subspace"], default="krylov",
+                    help="rank projection: device block-Krylov on the panel kernels (default; krylov-fused: its block "
+                         "steps on the library's own kernels only) or the exact library SVD truncation of the "
+                         "reference (svd)")
     ap.add_argument("--save-packed", action="store_true",
                     help="also write {layer}_{bits}_{rank}_{rel}_QR_packed.pt: W_q as packed codes and W_r as its two thin "
                          "factors (admmq.load_packed_lowrank, admmq.export.build_qlr_layer)")

@@ -121,6 +121,64 @@ def gram(A: torch.Tensor, B: torch.Tensor, out: Optional[torch.Tensor] = None) -
     return C
 
 
+CHOLQR_K_MAX = 64   # ADMMQ_CHOLQR_K_MAX (include/admmq.h): the widest panel of cholqr / reorth
+
+
+def _check_f64(what: str, *ts: torch.Tensor):
+    """gram's checks for the float64 panels of cholqr / reorth; rows may be strided."""
+    if any(not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.device != ts[0].device for t in ts):
+        raise RuntimeError(f"admmq.panel.{what}: the panels must be tensors on one ROCm GPU")
+    if any(t.dim() != 2 or t.dtype != torch.float64 for t in ts):
+        raise ValueError(f"admmq.panel.{what}: the panels must be 2-D float64")
+    return [t if t.stride(1) == 1 else t.contiguous() for t in ts]
+
+
+def _check_out(what: str, out: Optional[torch.Tensor], like: torch.Tensor) -> torch.Tensor:
+    if out is None:
+        return torch.empty(like.shape, dtype=torch.float64, device=like.device)
+    if (not isinstance(out, torch.Tensor) or out.shape != like.shape or out.dtype != torch.float64
+            or out.device != like.device or out.stride(1) != 1):
+        raise ValueError(f"admmq.panel.{what}: out must be a float64 tensor of Z's shape on its device with unit column stride")
+    return out
+
+
+def cholqr(Z: torch.Tensor, G: torch.Tensor, shift_scale: float = 0.0, info: Optional[torch.Tensor] = None,
+           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One Cholesky-QR pass in one launch (``admmq_cholqr64``): ``Z L^-T`` (m x k float64) with
+    ``L L^T = G + shift_scale tr(G) I`` for ``G = gram(Z, Z)``, k <= ``CHOLQR_K_MAX``. ``out`` may be
+    ``Z`` (rows may be strided). A ``G`` that is not numerically positive definite fills the result
+    with NaN and sets ``info`` (a one-element int32 device tensor) to 1."""
+    Zc, G = _check_f64("cholqr", Z, G)
+    m, k = Zc.shape
+    if G.shape != (k, k):
+        raise ValueError("admmq.panel.cholqr: G must be k x k for Z m x k")
+    if k > CHOLQR_K_MAX:
+        raise ValueError(f"admmq.panel.cholqr: k = {k} above {CHOLQR_K_MAX}")
+    G = G.contiguous()
+    Q = _check_out("cholqr", out, Zc)
+    _lib.check(_lib.load().admmq_cholqr64(_lib.ptr(Zc), Zc.stride(0), m, k, _lib.ptr(G), float(shift_scale), _lib.ptr(Q),
+                                          Q.stride(0), _info_ptr(info), _lib.stream_handle(Zc.device)), "cholqr64")
+    return Q
+
+
+def reorth(K: torch.Tensor, C: torch.Tensor, Z: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``Z - K C`` (m x k float64) in one launch (``admmq_panel_reorth64``) for tall ``K`` (m x p),
+    ``C = gram(K, Z)`` (p x k) and k <= ``CHOLQR_K_MAX``: a re-orthogonalisation pass of a Krylov
+    block against every block so far. ``out`` may be ``Z``; the bits are the same on every call."""
+    K, C, Zc = _check_f64("reorth", K, C, Z)
+    m, k = Zc.shape
+    p = K.shape[1]
+    if K.shape[0] != m or C.shape != (p, k):
+        raise ValueError("admmq.panel.reorth: K (m x p), C (p x k) and Z (m x k) must fit")
+    if k > CHOLQR_K_MAX:
+        raise ValueError(f"admmq.panel.reorth: k = {k} above {CHOLQR_K_MAX}")
+    O = _check_out("reorth", out, Zc)
+    _lib.check(_lib.load().admmq_panel_reorth64(_lib.ptr(K), K.stride(0), m, p, _lib.ptr(C), C.stride(0), _lib.ptr(Zc),
+                                                Zc.stride(0), k, _lib.ptr(O), O.stride(0),
+                                                _lib.stream_handle(Zc.device)), "panel_reorth64")
+    return O
+
+
 def epc_mu(c: torch.Tensor, s: torch.Tensor, normY2: float, delta2: float) -> torch.Tensor:
     """The EPC multiplier (``admmq.parafac_epc._solve_mu``) on the device: a 0-dim float64
     tensor, with no host synchronisation."""

@@ -944,6 +944,22 @@ size_t admmq_gram64_workspace_size(int64_t m, int64_t p, int64_t q);
 int32_t admmq_gram64(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t m, int64_t p, int64_t q,
                      double* C, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The rest of a Krylov block step (admmq.lowrank.KrylovProjector(fused=True); csrc/ortho_kernels.hip),
+ * each one launch with no workspace. Row-major float64 with row strides; k <= ADMMQ_CHOLQR_K_MAX.
+ *   admmq_cholqr64        one Cholesky-QR pass: Q = Z L^-T with L L^T = G + shift_scale tr(G) I, G = Z^T Z
+ *                         (k x k, ld k, from admmq_gram64). Every workgroup factors G itself (fp64, correctly
+ *                         rounded sqrt and division) and solves its 64 rows. Q may be Z. A pivot that is not
+ *                         positive (NaN included) fills Q with NaN and sets *info (device int, may be NULL;
+ *                         never written otherwise) to 1; the call still returns ADMMQ_OK.
+ *   admmq_panel_reorth64  Zout = Z - K C for tall K (m x p, p <= 8192) and C = K^T Z (p x k) on
+ *                         v_mfma_f64_16x16x4_f64, the p-sum in index order (the same bits on every call).
+ *                         Zout may be Z, with the same bits as out of place. */
+#define ADMMQ_CHOLQR_K_MAX 64
+int32_t admmq_cholqr64(const double* Z, int64_t ldz, int64_t m, int64_t k, const double* G, double shift_scale, double* Q,
+                       int64_t ldq, int32_t* info, void* stream);
+int32_t admmq_panel_reorth64(const double* K, int64_t ldk, int64_t m, int64_t p, const double* C, int64_t ldc,
+                             const double* Z, int64_t ldz, int64_t k, double* Zout, int64_t ldo, void* stream);
+
 /* The EPC step's multiplier (cp_anc, source/parafac_epc.py:61-74): *mu (device double) = the
  * root mu >= 0 of normY2 - sum_i c_i (s_i + 2 mu) / (s_i + mu)^2 = delta2 (0 when already
  * below), by bracket doubling and bisection to fp64 resolution; c, s: n device doubles. */
