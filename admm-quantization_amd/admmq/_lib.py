@@ -163,6 +163,8 @@ def load() -> ctypes.CDLL:
         "admmq_packed_gemm_act": (I32, [P, P, I32, I64, I64, P, I32, I64, I32, P, P, P, P, S, P]),
         "admmq_packed_dwgemm_act": (I32, [P, P, I64, I64, P, I32, I64, I64, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P,
                                           S, P]),
+        "admmq_packed_pairgemm_plan": (I32, [I64, I64, I64, I64, I64, P]),
+        "admmq_packed_pairgemm": (I32, [P, P, I32, P, P, I64, I64, I64, P, I32, I64, I32, P, P, P, P, P]),
         "admmq_act_encode": (I32, [P, P, I64, P, P, P]),
         "admmq_act_decode": (I32, [P, P, I64, P, P]),
         "admmq_packed_rowsums": (I32, [P, P, I32, I64, I64, P, P]),

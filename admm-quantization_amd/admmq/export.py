@@ -20,6 +20,8 @@ the CP builders accept them in place of float tensors: the 1x1 convs / linears t
 (inference only); no float32 copy of such a factor is ever made. ``fused=True`` replaces a
 3-way layer's ``conv2`` / ``conv3`` by one ``PackedDepthwiseConv1x1`` (``k_packed_dwgemm``; on a
 bfloat16 / float16 input ``k_packed_hdwgemm``).
+``fused=True`` of the 2-way builders returns one ``PackedPair`` (``k_packed_pairgemm``: both stages in one kernel, the
+rank-R tensor in LDS).
 ``integer=True`` (2-way builders) returns an ``IntegerPackedPair``: the input is encoded to
 activation codes once and both stages run on ``k_packed_igemm`` (int8 MFMA), codes to codes to float.
 ``build_qlr_layer`` turns the ``PackedLowRank`` of ``admmq.lowrank`` (``W ~ W_q + L Rt``) into a
@@ -39,8 +41,8 @@ from torch import nn
 
 from . import _lib
 from .packed import (HALF_DTYPES, PackedLowRank, PackedTensor, QuantizedActivation, _idwgemm, _int_weight_dims, _lowrank_dims,
-                     _meta_words, _pair, _weight_dims, _factorsums, _igemm, _igemv, _ilrgemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
-                     packed_gemm, packed_gemv, packed_hlrgemm, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
+                     _meta_words, _pair, _pair_dims, _weight_dims, _factorsums, _igemm, _igemv, _ilrgemm, act_encode, load_packed, packed_bytes, packed_dwgemm,
+                     packed_gemm, packed_gemv, packed_hlrgemm, packed_pairgemm, RANK_MAX, packed_lrgemm, packed_lrgemv, packed_rowsums, packed_taps_int, skinny_rows, taps_kp)
 
 
 def _param(t: torch.Tensor) -> nn.Parameter:
@@ -691,6 +693,113 @@ def _packed_cp_layer(rank, factors, bias, cin, cout, kernel_size, padding, strid
     ]))
 
 
+_QKEYS = ("shape", "bits", "qscheme", "scale", "zero_point", "mn", "rng", "index")
+
+
+class PackedPair(nn.Module):
+    """Both stages of a 2-way packed layer as one kernel (``packed_pairgemm``):
+    ``y = W2 q_mid(W1 x) (+ bias)``, then the output quantizer. ``W1 [R, in]`` is ``p1``'s de-quantization
+    (``transpose1``: ``p1`` holds ``[in, R]``), ``W2 [out, R]`` is ``p2``'s; the rank-``R`` tensor between them stays in
+    LDS. ``layout`` 0: a pair of 1x1 convolutions (``x [n, in, H, W]``, ``stride`` sub-samples ``x``); 1: a pair of linear
+    layers (``x [..., in]``). ``codes1`` / ``codes2`` are uint8 buffers; the two quantization records, the layout, the
+    stride and the quantizers travel in the extra state, as ``_PackedWeight``'s do; ``bias`` is an optional frozen
+    parameter. Float32 activations, ``R <= 256``, inference only. The bits are not those of the two-module layer
+    (whose first stage may split K); the error bound is the same."""
+
+    def __init__(self, p1: PackedTensor, p2: PackedTensor, bias: Optional[torch.Tensor] = None, transpose1: bool = True,
+                 layout: int = 0, stride=1):
+        super().__init__()
+        self.transpose1, self.layout = bool(transpose1), int(layout)
+        self.out_features, self.in_features, self.rank = _pair_dims(p1, p2, self.transpose1, "PackedPair")
+        if self.rank > RANK_MAX:
+            raise ValueError(f"PackedPair: rank {self.rank} is past the fused pair's limit of {RANK_MAX} (the rank-R "
+                             "tile is held in LDS)")
+        self.stride = _pair(stride, "stride")
+        self.register_buffer("codes1", p1.codes.detach().clone().contiguous())
+        self.register_buffer("codes2", p2.codes.detach().clone().contiguous())
+        self._set_quant(p1, p2)
+        self._mid_act = self._act = None   # (bits, mn, rng) as resolved float32 values, or None
+        if bias is not None:
+            _expect_shape((self.out_features,), bias.shape)
+            self.bias = nn.Parameter(bias.detach().clone().to(self.codes1.device).contiguous(), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    def _set_quant(self, p1, p2):
+        self._q = [dict(shape=[int(s) for s in p.shape], bits=int(p.bits), qscheme=str(p.qscheme), scale=float(p.scale),
+                        zero_point=int(p.zero_point), mn=float(p.mn), rng=float(p.rng), index=int(p.index))
+                   for p in (p1, p2)]
+        self._meta = [_meta_words(p) for p in self.packed()]
+
+    def packed(self) -> Tuple[PackedTensor, PackedTensor]:
+        """The two weights as ``PackedTensor`` s sharing the code buffers."""
+        return tuple(PackedTensor(codes=c, shape=tuple(q["shape"]), bits=q["bits"], qscheme=q["qscheme"], scale=q["scale"],
+                                  zero_point=q["zero_point"], mn=q["mn"], rng=q["rng"], index=q["index"])
+                     for c, q in zip((self.codes1, self.codes2), self._q))
+
+    def set_mid_activation_quant(self, bits=None, min_val=None, max_val=None):
+        """The fixed-range quantizer of the first stage's output, applied before the tile is parked; ``None`` clears it."""
+        self._mid_act = _PackedWeight._resolve_act(bits, min_val, max_val)
+
+    def set_activation_quant(self, bits=None, min_val=None, max_val=None):
+        """The fixed-range quantizer of the layer's output, applied in the kernel's epilogue; ``None`` clears it."""
+        self._act = _PackedWeight._resolve_act(bits, min_val, max_val)
+
+    def get_extra_state(self):
+        return dict(first=self._q[0], second=self._q[1], transpose1=self.transpose1, layout=self.layout,
+                    stride=list(self.stride), mid_act=list(self._mid_act) if self._mid_act else None,
+                    act=list(self._act) if self._act else None)
+
+    def set_extra_state(self, state):
+        qs = [{k: state[n][k] for k in _QKEYS} for n in ("first", "second")]
+        for q, mine, codes in zip(qs, self._q, (self.codes1, self.codes2)):
+            numel = int(mine["shape"][0]) * int(mine["shape"][1])
+            if [int(s) for s in q["shape"]] != mine["shape"] or packed_bytes(numel, int(q["bits"])) != codes.numel():
+                raise ValueError(f"packed state of shape {tuple(q['shape'])}, {q['bits']} bits does not fit this layer "
+                                 f"({tuple(mine['shape'])}, {mine['bits']} bits)")
+        if bool(state["transpose1"]) != self.transpose1 or int(state["layout"]) != self.layout:
+            raise ValueError(f"packed pair state with transpose1={state['transpose1']}, layout={state['layout']} does not "
+                             f"fit this layer (transpose1={self.transpose1}, layout={self.layout})")
+        self._set_quant(*(PackedTensor(codes=c, shape=tuple(q["shape"]), bits=int(q["bits"]), qscheme=q["qscheme"],
+                                       scale=float(q["scale"]), zero_point=int(q["zero_point"]), mn=float(q["mn"]),
+                                       rng=float(q["rng"]), index=int(q["index"]))
+                          for c, q in zip((self.codes1, self.codes2), qs)))
+        self.stride = _pair(state["stride"], "stride")
+        m, a = state.get("mid_act"), state.get("act")
+        self._mid_act = (int(m[0]), float(m[1]), float(m[2])) if m else None
+        self._act = (int(a[0]), float(a[1]), float(a[2])) if a else None
+
+    def forward(self, x):
+        if self.layout == 0 and self.stride != (1, 1):
+            x = x[:, :, ::self.stride[0], ::self.stride[1]]
+        return packed_pairgemm(self.codes1, self._meta[0], self.transpose1, self.codes2, self._meta[1], self.out_features,
+                               self.in_features, self.rank, x, self.layout, self.bias,
+                               _PackedWeight._act_arg(self._mid_act), _PackedWeight._act_arg(self._act))
+
+    def extra_repr(self):
+        return (f"{self.in_features}, {self.rank}, {self.out_features}, bits=({self._q[0]['bits']}, {self._q[1]['bits']}), "
+                f"layout={self.layout}, stride={self.stride}, bias={self.bias is not None}")
+
+
+def _fused_pair(who, p1, p2, bias, acts, integer, layout, stride=1, padding=0):
+    """The ``fused=True`` form of a 2-way builder: its refusals, then the ``PackedPair`` with both quantizers set."""
+    if integer:
+        raise ValueError(f"{who}: fused=True cannot be combined with integer=True (the fused pair runs on float32 "
+                         "activations; the integer route keeps its two stages)")
+    if not _is_packed([p1, p2]):
+        raise ValueError(f"{who}: fused=True needs PackedTensor factors (the fused pair runs from packed codes)")
+    if _pair(padding, "padding") != (0, 0):
+        raise ValueError(f"{who}: fused=True needs padding 0 (the fused pair does not pad its input), got {padding}")
+    rank = int(p2.shape[1])
+    if rank > RANK_MAX:
+        raise ValueError(f"{who}: fused=True needs rank <= {RANK_MAX} (the rank-R tile is held in LDS), got {rank}; "
+                         "keep the two-stage layer")
+    m = PackedPair(p1, p2, bias, transpose1=True, layout=layout, stride=stride)
+    if acts[0] is not None:
+        m.set_mid_activation_quant(*acts[0])
+    return _with_act(m, acts[1])
+
+
 def _packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride, acts=(None,) * 2):
     A, B = factors
     _expect_shape((rank, cin, 1, 1), (B.shape[1], B.shape[0], 1, 1))
@@ -759,12 +868,21 @@ def build_cp_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: O
 
 
 def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bias: Optional[torch.Tensor], cin: int,
-                        cout: int, padding, stride, act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
+                        cout: int, padding, stride, act_quant=None, integer: bool = False, in_act=None,
+                        fused: bool = False) -> nn.Module:
     """1x1 (cin -> R, with the original padding/stride) -> 1x1 (R -> cout); source/models.py:54-77.
     ``PackedTensor`` factors: both stages become ``PackedConv1x1`` (B transposed, A).
     ``integer`` (``PackedTensor`` factors, ``in_act = (bits, min_val, max_val)`` of the input and the
-    ``conv1`` entry of ``act_quant``, both with bits 2..8): an ``IntegerPackedPair`` of the same two stages."""
+    ``conv1`` entry of ``act_quant``, both with bits 2..8): an ``IntegerPackedPair`` of the same two stages.
+    ``fused`` (``PackedTensor`` factors, padding 0, rank <= 256, not with ``integer``): a Sequential with the one
+    child ``conv12``, a ``PackedPair`` that runs both stages as one kernel (``act_quant``'s entries are
+    its mid and output quantizers). Other bits than the two-stage layer's (another sum order, the same bound)."""
     acts = _stage_acts(act_quant, 2, "build_cp2conv_layer")   # [conv1, conv2], as build_cp_layer's
+    if fused:
+        A, B = factors if factors else (None, None)
+        pair = _fused_pair("build_cp2conv_layer", B, A, bias, acts, integer, 0, stride, padding)
+        _expect_shape((rank, cin, cout), (pair.rank, pair.in_features, pair.out_features))
+        return nn.Sequential(OrderedDict([('conv12', pair)]))
     if integer:
         return _integer_pair("build_cp2conv_layer", ("conv1", "conv2"), factors, acts, in_act,
                              lambda: tuple(_packed_cp2conv_layer(rank, factors, bias, cin, cout, padding, stride,
@@ -792,11 +910,17 @@ def build_cp2conv_layer(rank: int, factors: Optional[Sequence[torch.Tensor]], bi
 
 
 def build_cpfc_layer(rank: int, factors: Sequence[torch.Tensor], bias: Optional[torch.Tensor], fin: int,
-                     fout: int, act_quant=None, integer: bool = False, in_act=None) -> nn.Module:
+                     fout: int, act_quant=None, integer: bool = False, in_act=None, fused: bool = False) -> nn.Module:
     """Linear fin -> R (A^T) -> Linear R -> fout (B); source/models.py:80-99 (factors = [B, A]).
     ``PackedTensor`` factors: both stages become ``PackedLinear`` (A transposed, B).
-    ``integer``: as ``build_cp2conv_layer``'s, an ``IntegerPackedPair`` of ``fc1`` / ``fc2``."""
+    ``integer``: as ``build_cp2conv_layer``'s, an ``IntegerPackedPair`` of ``fc1`` / ``fc2``.
+    ``fused``: as ``build_cp2conv_layer``'s, a Sequential with the one child ``fc12`` (a ``PackedPair``)."""
     acts = _stage_acts(act_quant, 2, "build_cpfc_layer")   # [fc1, fc2], as build_cp_layer's
+    if fused:
+        B, A = factors if factors else (None, None)
+        pair = _fused_pair("build_cpfc_layer", A, B, bias, acts, integer, 1)
+        _expect_shape((rank, fin, fout), (pair.rank, pair.in_features, pair.out_features))
+        return nn.Sequential(OrderedDict([('fc12', pair)]))
     if integer:
         return _integer_pair("build_cpfc_layer", ("fc1", "fc2"), factors, acts, in_act,
                              lambda: tuple(_packed_cpfc_layer(rank, factors, bias, fin, fout, acts).children()))

@@ -12,6 +12,9 @@ a second guess at the float32 result.
 ``packed_depthwise_conv1x1`` runs a depthwise ``k x k`` convolution and the 1x1 convolution by
 such a weight as one kernel (``k_packed_dwgemm``: the tensor between them is never written).
 
+``packed_linear_pair`` / ``packed_conv1x1_pair`` run the two chained products of a 2-way layer as one kernel
+(``k_packed_pairgemm``: the rank-R tensor between them stays in LDS).
+
 ``act_encode`` turns a float activation into ``QuantizedActivation`` codes (one uint8 per element, the
 fixed-range quantizer's level clamped to ``0 .. 2^bits - 1``), and ``packed_linear_int`` /
 ``packed_conv1x1_int`` multiply such codes by a packed weight in integer arithmetic
@@ -47,7 +50,8 @@ import torch
 from . import _lib
 
 __all__ = ["PackedTensor", "quantize_packed", "dequantize_packed", "save_packed", "load_packed", "packed_bytes",
-           "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_dwgemm", "packed_depthwise_conv1x1",
+           "packed_gemm", "packed_gemv", "packed_linear", "packed_conv1x1", "packed_pairgemm", "packed_linear_pair",
+           "packed_conv1x1_pair", "packed_pairgemm_plan", "packed_dwgemm", "packed_depthwise_conv1x1",
            "QuantizedActivation", "act_encode", "act_decode", "packed_rowsums", "packed_igemm", "packed_igemv", "packed_linear_int",
            "packed_conv1x1_int", "packed_taps_int", "packed_depthwise_conv1x1_int", "PackedLowRank",
            "packed_lrgemm", "packed_lrgemv", "packed_hlrgemm", "packed_lowrank_linear",
@@ -520,6 +524,93 @@ def packed_conv1x1(x: torch.Tensor, p: "PackedTensor", bias: Optional[torch.Tens
     if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
         x = x[:, :, ::sh, ::sw]
     return packed_gemm(p.codes, _meta_words(p), transpose, M, K, x, 0, bias, act, out_dtype)
+
+
+# --- fused pair: both 1x1 stages of a 2-way layer in one kernel ---------------
+def _act_triple(act) -> Tuple[int, float, float]:
+    """``(bits, mn, rng)`` of ``act`` as ``packed_gemm`` takes it; bits 0: none."""
+    q = _act_record(act)
+    return (0, 0.0, 0.0) if q is None else (int(q.bits), float(q.mn), float(q.rng))
+
+
+def packed_pairgemm(codes1: torch.Tensor, meta1: torch.Tensor, trans1: bool, codes2: torch.Tensor, meta2: torch.Tensor,
+                    M: int, K: int, R: int, x: torch.Tensor, x_layout: int, bias: Optional[torch.Tensor] = None,
+                    mid_act=None, act=None) -> torch.Tensor:
+    """``Y = D2 q_mid(D1 X) (+ bias)``, then ``act``: the two products of a 2-way packed layer as one kernel
+    (``admmq_packed_pairgemm``). ``D1 [R, K]`` is the de-quantization of ``codes1`` (``trans1``: of
+    the ``[K, R]`` packed tensor's transpose), ``D2 [M, R]`` that of ``codes2``; ``meta1`` / ``meta2`` are their 8
+    int32 meta words on the CPU (any bits and tensor scheme each). ``x`` and ``x_layout`` as ``packed_gemm``;
+    ``mid_act`` / ``act = (bits, min_val, max_val)``: the fixed-range quantizers behind the first and the second
+    product. The rank-``R`` tensor between the products stays in LDS, ``1 <= R <= RANK_MAX``. Float32 ``x`` only.
+    Every output's bits depend on its own column of ``x`` only; they are not the bits of two ``packed_gemm`` calls
+    (whose first stage may split K: another sum order, the same error bound). Inference only."""
+    if isinstance(x, torch.Tensor) and x.dtype != torch.float32:
+        raise TypeError(f"admmq: packed_pairgemm: x must be float32 (the fused pair has no bfloat16 / float16 form), "
+                        f"got {x.dtype}")
+    _require_gpu("packed_pairgemm", "codes and activations", x, codes1, codes2)
+    _inference_only("packed_pairgemm", x, "x")
+    if torch.compiler.is_compiling():   # opaque under torch.compile, like packed_gemm
+        return _opaque_packed_pairgemm(codes1, meta1, trans1, codes2, meta2, M, K, R, x, x_layout, bias, mid_act, act)
+    M, K, R, x_layout = int(M), int(K), int(R), int(x_layout)
+    if not 1 <= R <= RANK_MAX:
+        raise ValueError(f"packed_pairgemm: R = {R} is outside 1..{RANK_MAX} (the rank-R tile is held in LDS); "
+                         "run the two stages as separate packed_gemm calls")
+    if bias is not None:
+        bias = bias.detach()
+    m3, o3 = _act_triple(mid_act), _act_triple(act)
+    if _lib.use_ops():   # torch.ops.admmq.packed_pairgemm (csrc/torch_ops.cpp) -> admmq_packed_pairgemm
+        return _lib.ops().packed_pairgemm(codes1, meta1, bool(trans1), codes2, meta2, M, K, R, x, x_layout, bias, *m3, *o3)
+    lib = _lib.load()
+    oshape, nb, N, xc = _gemm_geometry("packed_pairgemm", x, M, K, x_layout)
+    (c1, r1), (c2, r2), bc = _weight_arg(codes1, meta1), _weight_arg(codes2, meta2), _bias_arg("packed_pairgemm", bias, M)
+    mq, oq = _actq(m3), _actq(o3)
+    y = torch.empty(oshape, dtype=torch.float32, device=x.device)
+    rc = lib.admmq_packed_pairgemm(_lib.ptr(c1), ctypes.byref(r1), 1 if trans1 else 0, _lib.ptr(c2), ctypes.byref(r2), M, K,
+                                   R, _lib.ptr(xc), x_layout, N, nb, _lib.ptr(bc), _lib.ptr(y), _byref(mq), _byref(oq),
+                                   _lib.stream_handle(x.device))
+    _lib.check(rc, "packed_pairgemm")
+    return y
+
+
+_opaque_packed_pairgemm = torch.compiler.disable(packed_pairgemm)
+
+
+def _pair_dims(p1: "PackedTensor", p2: "PackedTensor", transpose1: bool, who: str) -> Tuple[int, int, int]:
+    """``(M, K, R)`` of the pair ``D2 [M, R]``, ``D1 [R, K]`` (``transpose1``: ``p1`` is ``[K, R]``)."""
+    R, K = _weight_dims(p1, transpose1)
+    M, R2 = _weight_dims(p2, False)
+    if R != R2:
+        raise ValueError(f"{who}: the factors do not chain: the first gives rank {R}, the second takes {R2}")
+    return M, K, R
+
+
+def packed_linear_pair(x: torch.Tensor, p1: "PackedTensor", p2: "PackedTensor", bias: Optional[torch.Tensor] = None,
+                       transpose1: bool = True, mid_act=None, act=None) -> torch.Tensor:
+    """``F.linear(q_mid(F.linear(x, W1)), W2, bias)`` then ``act``, with ``W1 = p1.dequantize()`` (``transpose1``: its
+    transpose) and ``W2 = p2.dequantize()``, as one kernel (``packed_pairgemm``): ``x [..., K] -> [..., M]``."""
+    M, K, R = _pair_dims(p1, p2, transpose1, "packed_linear_pair")
+    return packed_pairgemm(p1.codes, _meta_words(p1), transpose1, p2.codes, _meta_words(p2), M, K, R, x, 1, bias, mid_act, act)
+
+
+def packed_conv1x1_pair(x: torch.Tensor, p1: "PackedTensor", p2: "PackedTensor", bias: Optional[torch.Tensor] = None,
+                        transpose1: bool = True, stride=1, mid_act=None, act=None) -> torch.Tensor:
+    """Two chained 1x1 convolutions (weights as ``packed_linear_pair``; ``stride`` on the first, sub-sampling ``x`` as
+    ``packed_conv1x1`` does) as one kernel (``packed_pairgemm``): ``x [n, K, H, W] -> [n, M, H', W']``."""
+    M, K, R = _pair_dims(p1, p2, transpose1, "packed_conv1x1_pair")
+    if isinstance(x, torch.Tensor) and x.dim() != 4:
+        raise ValueError(f"packed_conv1x1_pair: x must be [n, {K}, H, W], got {tuple(x.shape)}")
+    sh, sw = (stride, stride) if isinstance(stride, int) else tuple(stride)
+    if (sh, sw) != (1, 1) and isinstance(x, torch.Tensor):
+        x = x[:, :, ::sh, ::sw]
+    return packed_pairgemm(p1.codes, _meta_words(p1), transpose1, p2.codes, _meta_words(p2), M, K, R, x, 0, bias, mid_act, act)
+
+
+def packed_pairgemm_plan(M: int, K: int, N: int, nb: int, R: int) -> Tuple[int, int, int, int]:
+    """``(ntile, ms, LDS bytes, workgroups)`` of a ``packed_pairgemm`` call (``admmq_packed_pairgemm_plan``: a pure
+    host function of the sizes; include/admmq.h states the rule)."""
+    out = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.load().admmq_packed_pairgemm_plan(int(M), int(K), int(N), int(nb), int(R), out), "packed_pairgemm_plan")
+    return tuple(out)
 
 
 # --- integer route (DESIGN.md 2.25) -------------------------------------------------------------

@@ -17,6 +17,7 @@
 //   admmq::packed_dwgemm           depthwise k x k + packed 1x1 stage of a CP layer, fused
 //   admmq::packed_hdwgemm          that stage on bfloat16 / float16 activations
 //   admmq::fixed_quantize, packed_gemm_act, packed_dwgemm_act   fixed-range activation quantizers
+//   admmq::packed_pairgemm            both 1x1 stages of a 2-way packed layer in one kernel
 //   admmq::packed_lowrank_factorsums, packed_ilrgemm   the integer quant + low-rank GEMM on activation codes
 //   admmq::packed_ilrgemv   its skinny form for 1..8 rows
 //   admmq::act_encode, act_decode, packed_rowsums, packed_igemm   activation codes and the int8-MFMA GEMM
@@ -448,6 +449,58 @@ at::Tensor packed_gemm_act_meta(const at::Tensor& codes, const at::Tensor& meta_
                                 const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
                                 int64_t out_bits, double out_mn, double out_rng) {
   (void)actq_of(out_bits, out_mn, out_rng, "packed_gemm_act");
+  return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
+}
+
+// --- packed_pairgemm ------------------------------------------------------------------------
+// Y = D2 q_mid(D1 X) (+ bias), then q_out: both 1x1 stages of a 2-way packed layer in one kernel
+// (admmq_packed_pairgemm). codes1 / meta_words1: the [R, K] weight (trans1: the
+// [K, R] tensor's transpose); codes2 / meta_words2: the [M, R] weight. Shapes and layouts as
+// packed_gemm; quantizer bits 0: none. Inference only.
+at::Tensor packed_pairgemm_cuda(const at::Tensor& codes1, const at::Tensor& meta_words1, bool trans1,
+                                const at::Tensor& codes2, const at::Tensor& meta_words2, int64_t M, int64_t K, int64_t R,
+                                const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
+                                int64_t mid_bits, double mid_mn, double mid_rng, int64_t out_bits, double out_mn,
+                                double out_rng) {
+  const char* const who = "packed_pairgemm";
+  const admmq_actq mq = actq_of(mid_bits, mid_mn, mid_rng, who);
+  const admmq_actq oq = actq_of(out_bits, out_mn, out_rng, who);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() != at::kHalf && x.scalar_type() != at::kBFloat16, "admmq: ", who,
+              ": x must be a float32 tensor on the GPU (the fused pair has no bfloat16 / float16 form), got ",
+              x.scalar_type());
+  check_f32_device(x, "x");
+  check_inference_only(x.requires_grad(), who, "x");
+  check_codes(codes1, who);
+  check_codes(codes2, who);
+  check_same_device(codes1, x, "codes1");
+  check_same_device(codes2, x, "codes2");
+  check_meta_words(meta_words1, who);
+  check_meta_words(meta_words2, who);
+  TORCH_CHECK(R >= 1 && R <= 256, "admmq: ", who, ": R must be 1..256 (the rank-R tile is held in LDS), got ", R);
+  const std::vector<int64_t> oshape = packed_gemm_shape(x, M, K, x_layout);
+  admmq_qmeta meta1, meta2;
+  const at::Tensor c1 = packed_weight_of(codes1, meta_words1, R, K, who, meta1);
+  const at::Tensor c2 = packed_weight_of(codes2, meta_words2, M, R, who, meta2);
+  const c10::DeviceGuard guard(x.device());
+  const at::Tensor xc = x.contiguous();
+  const at::Tensor bc = bias_of(bias, x, M, who, false);
+  const auto [nb, N] = gemm_extent(xc, K, x_layout, who);
+  at::Tensor y = at::empty(oshape, xc.options());
+  check_rc(admmq_packed_pairgemm(c1.data_ptr<uint8_t>(), &meta1, trans1 ? 1 : 0, c2.data_ptr<uint8_t>(), &meta2, M, K, R,
+                                 xc.data_ptr<float>(), static_cast<int32_t>(x_layout), N, nb, f32_or_null(bc),
+                                 y.data_ptr<float>(), &mq, &oq, stream_of(xc)),
+           who);
+  return y;
+}
+
+at::Tensor packed_pairgemm_meta(const at::Tensor& codes1, const at::Tensor& meta_words1, bool trans1,
+                                const at::Tensor& codes2, const at::Tensor& meta_words2, int64_t M, int64_t K, int64_t R,
+                                const at::Tensor& x, int64_t x_layout, const std::optional<at::Tensor>& bias,
+                                int64_t mid_bits, double mid_mn, double mid_rng, int64_t out_bits, double out_mn,
+                                double out_rng) {
+  (void)actq_of(mid_bits, mid_mn, mid_rng, "packed_pairgemm");
+  (void)actq_of(out_bits, out_mn, out_rng, "packed_pairgemm");
+  TORCH_CHECK(R >= 1 && R <= 256, "admmq: packed_pairgemm: R must be 1..256 (the rank-R tile is held in LDS), got ", R);
   return at::empty(packed_gemm_shape(x, M, K, x_layout), x.options().dtype(at::kFloat));
 }
 
@@ -1437,6 +1490,9 @@ TORCH_LIBRARY(admmq, m) {
   m.def("packed_dwgemm_act(Tensor codes, Tensor meta_words, int M, int K, Tensor x, Tensor taps, int kh, int kw, int sh, "
         "int sw, int ph, int pw, Tensor? bias, int mid_bits, float mid_mn, float mid_rng, int out_bits, float out_mn, "
         "float out_rng) -> Tensor");
+  m.def("packed_pairgemm(Tensor codes1, Tensor meta_words1, bool trans1, Tensor codes2, Tensor meta_words2, int M, int K, "
+        "int R, Tensor x, int x_layout, Tensor? bias, int mid_bits, float mid_mn, float mid_rng, int out_bits, "
+        "float out_mn, float out_rng) -> Tensor");
   m.def("fixed_quantize(Tensor x, int bits, float mn, float rng) -> Tensor");
   m.def("act_encode(Tensor x, int bits, float mn, float rng) -> (Tensor codes, Tensor clamped)");
   m.def("act_decode(Tensor codes, int bits, float mn, float rng) -> Tensor");
@@ -1480,6 +1536,7 @@ TORCH_LIBRARY_IMPL(admmq, CUDA, m) {
   m.impl("packed_hdwgemm", &packed_hdwgemm_cuda);
   m.impl("packed_gemm_act", &packed_gemm_act_cuda);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_cuda);
+  m.impl("packed_pairgemm", &packed_pairgemm_cuda);
   m.impl("fixed_quantize", &fixed_quantize_cuda);
   m.impl("act_encode", &act_encode_cuda);
   m.impl("act_decode", &act_decode_cuda);
@@ -1511,6 +1568,7 @@ TORCH_LIBRARY_IMPL(admmq, Meta, m) {
   m.impl("packed_hdwgemm", &packed_hdwgemm_meta);
   m.impl("packed_gemm_act", &packed_gemm_act_meta);
   m.impl("packed_dwgemm_act", &packed_dwgemm_act_meta);
+  m.impl("packed_pairgemm", &packed_pairgemm_meta);
   m.impl("fixed_quantize", &fixed_quantize_meta);
   m.impl("act_encode", &act_encode_meta);
   m.impl("act_decode", &act_decode_meta);

@@ -293,6 +293,45 @@ int32_t admmq_packed_dwgemm_act(const uint8_t* codes, const admmq_qmeta* meta, i
                                 const admmq_actq* mid_q, const admmq_actq* out_q, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* Fused packed pair: the two 1x1 stages of a 2-way packed layer as one kernel,
+ *   Y_b[M, N] = q_out( D2[M, R] . q_mid( D1[R, K] . X_b[K, N] ) (+ bias[M]) ),  b = 0 .. nb-1
+ * with D1 and D2 the table de-quantizations of two packed tensors, each with a HOST meta record of
+ * its own (bits 1..8 and the four tensor schemes, independently). trans1 = 0: the first tensor is
+ * [R, K]; trans1 = 1: it is [K, R] and D1 is its transpose. The second tensor is [M, R].
+ * x_layout, N, nb, x, y and bias are admmq_packed_gemm's. The rank-R tensor between the two
+ * products is held in LDS and never written to memory: one launch, no workspace.
+ * 1. t[r, n] = sum_k D1[r, k] x[k, n] in float32 on the fp32 MFMA: one accumulation chain per
+ *    output from zero over increasing k. There is no K split.
+ * 2. mid_q on: t = q_mid(t), admmq_fixed_quantize's float32 expressions element by element.
+ * 3. y[m, n] = sum_r D2[m, r] t[r, n], one chain from zero over increasing r, then + bias[m], then
+ *    q_out as in admmq_packed_gemm_act.
+ * Every output's bits depend on its own column of x and its own row of D2 only: not on N, nb, the
+ * batch index or the plan below. They are NOT the bits of two admmq_packed_gemm calls, whose
+ * first stage may cut K into pieces; the error bound is the same.
+ * Plan (a function of the sizes alone), with C = nb N and tm = ceil(M / 64):
+ *   ntile = 32 if ceil(C / 64) < 128 (64-column tiles would leave over half of 256 CUs idle), else 64
+ *   tn    = ceil(C / ntile)                       column tiles
+ *   want  = max(1, min(tm, floor(256 / tn)))      M splits that fit beside the column tiles on 256 CUs
+ *   mt    = ceil(tm / want);  ms = ceil(tm / mt)  64-row M tiles per split; splits
+ * A workgroup owns one column tile and one split and recomputes step 1 for its columns: the M
+ * range is only split onto CUs that the column tiles leave idle, so the recompute never displaces
+ * other work of the call. Dynamic LDS, with Rp = 32 ceil(R / 32):
+ *   4 (Rp (ntile + 1) + max(64 (Rp + 1) + 64 (ntile + 1), 64 * 65)) bytes
+ * (148992 at R = 256, ntile = 64: one workgroup per CU).
+ * admmq_packed_pairgemm_plan writes out = (ntile, ms, LDS bytes, workgroups = tn ms) - a pure
+ * host function; ADMMQ_ERR_ARG (and nothing written) for a NULL out or arguments out of range.
+ * Limits: 1 <= R <= 256 (a larger rank is refused with a text that names the limit: such layers
+ * keep the two-call route); M <= 2^22, K <= 2^24, nb*N <= 2^30. codes1, codes2: device, 16-byte
+ * aligned; x, y, bias (may be NULL): device, float aligned. ADMMQ_ERR_ARG for NULL codes / meta /
+ * x / y, sizes outside the limits, what admmq_packed_gemm refuses of a meta record, trans1 or
+ * x_layout other than 0 / 1, x_layout 1 with nb != 1, misaligned pointers, a quantizer that is on
+ * with bits outside 1..24 - all before any launch, each with its own admmq_last_error text. */
+int32_t admmq_packed_pairgemm_plan(int64_t M, int64_t K, int64_t N, int64_t nb, int64_t R, int32_t* out);
+int32_t admmq_packed_pairgemm(const uint8_t* codes1, const admmq_qmeta* meta1, int32_t trans1, const uint8_t* codes2,
+                              const admmq_qmeta* meta2, int64_t M, int64_t K, int64_t R, const float* x, int32_t x_layout,
+                              int64_t N, int32_t nb, const float* bias, float* y, const admmq_actq* mid_q,
+                              const admmq_actq* out_q, void* stream);
+
 /* Integer packed GEMM: activation codes as a tensor of their own, and the
  * product of a packed weight with such codes in integer arithmetic (v_mfma_i32_32x32x32_i8).
  *
